@@ -7,8 +7,11 @@ path (march -> shade -> composite) with rays and weights resident in HBM. With -
 of a small-baseline trajectory (weak scaling: independent ray tiles) and the rgb+depth tiles are all-gathered with
 RCCL inside the timed region.
 
-Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json plus `roofline` for the dominant kernel and
-`cpu_baseline` (the oracle — a PyTorch CPU restatement of the reference path — on a bounded sample of the workload).
+Prints ONE JSON line (rank 0): metric/value/unit per BASELINE.json. A plain run sets up, warms up, times exactly `--steps` frames
+in one window (ms_per_step = window / steps) and reports that. `--full` adds everything else: `roofline` for the dominant kernel,
+per-kernel times, the secondary legs (sustained, bf16, weights materialised, exact fp32, early termination, train steps,
+scaling_prediction) and `cpu_baseline` (the oracle — a PyTorch CPU restatement of the reference path — on a bounded sample of the
+workload). `--dump-outputs DIR` writes what the last timed frame returned as DIR/<name>.npy (float32).
 """
 import argparse
 import faulthandler
@@ -711,6 +714,31 @@ def self_launch(n):
     return rc
 
 
+WARMUP_S = 0.5               # untimed frames before the timed window: at least --warmup of them and about this much time
+DUMP_BYTES = 60 * 10 ** 6    # --dump-outputs: all arrays together stay under 64 MB, .npy headers included
+# config keys filled by the legs behind --full (per-kernel timing, PMC record, secondary legs): a plain run leaves them out
+FULL_ONLY_CONFIG = {"sustained_ms_per_step", "kernel_ms_per_frame_sum", "host_gap_ms_per_step", "issue_model_ms", "exact_fp32_ms_per_step",
+                    "weights_materialised_ms_per_step", "bf16_factor_storage_ms_per_step", "c5_circle_48_views_bf16_ms_per_view",
+                    "train_ms_per_iter", "train_ms_per_iter_fused_optim", "train_ms_per_iter_fused_step",
+                    "train_ms_per_iter_fused_step_2048_rays", "train_iters_per_s_fused_step", "memory_reserved_GiB_train", "pmc_blob",
+                    "kernel_ms_per_frame", "issue_model_ms_by_kernel", "kernel_rooflines", "pmc_record"}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` that is not None as <path>/<name>.npy in float32. One whose share of DUMP_BYTES is too small
+    for it is written as a fixed sample of its rows (seeded, sorted: the same rows in every run with the same arguments)."""
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        row_bytes = 4 * (t[0].numel() if t.dim() and t.shape[0] else 1)
+        if t.dim() and t.shape[0] * row_bytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=max(1, share // row_bytes), replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def device_identity(dev):
     """What tells two GPUs apart (for the rank evidence in the JSON line): index, name, uuid / PCI ids where torch exposes them."""
     pr = torch.cuda.get_device_properties(dev)
@@ -733,9 +761,9 @@ def main():
                     help="bf16: BASELINE configs[4] storage mode (render == fp32 render of the bf16-rounded factor tensors)")
     ap.add_argument("--per-ray-marcher", action="store_true",
                     help="disable the 8x8-tile marcher (default for whole row-major frames: field.frame_width = W)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="skip the secondary measurements (sustained, bf16, materialised, exact fp32)")
-    ap.add_argument("--no-train", action="store_true", help="skip the C3-shaped train-step timing (iters/s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--quick", action="store_true", help="--full: skip the secondary measurements (sustained, bf16, materialised, exact fp32)")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the C3-shaped train-step timing (iters/s)")
     ap.add_argument("--mode", default="weak", choices=["weak", "c4"],
                     help="weak: one 800x800 view per GPU (C2, the headline); c4: BASELINE configs[3] — ONE 1600x1600 frame split "
                          "into contiguous ray tiles over the ranks, all-gather of the rgb+depth tiles inside every step "
@@ -746,11 +774,21 @@ def main():
     ap.add_argument("--check-c4", action="store_true",
                     help="c4 mode: rank 0 also renders the whole frame alone and compares it bitwise with the gathered one")
     ap.add_argument("--no-inregion-timing", action="store_true",
-                    help="no HIP timing events inside the timed region (the head's launch time then comes from the untimed pass behind it)")
+                    help="--full: no HIP timing events inside the timed region (the head's launch time then comes from the untimed pass "
+                         "behind it; a plain run places none)")
     ap.add_argument("--train-iters", type=int, default=20)
     ap.add_argument("--train-warmup", type=int, default=3)
     ap.add_argument("--aux-train-dp", type=int, default=0, help=argparse.SUPPRESS)   # (internal: child of scaling_prediction)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (per-kernel times and roofline, sustained, bf16, weights "
+                         "materialised, exact fp32, early termination, train steps, scaling_prediction, cpu_baseline); a plain run "
+                         "times the headline frames only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed frame returned as DIR/<name>.npy (float32, at most 64 MB in all: larger "
+                         "outputs as a fixed, seeded sample of rows)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.aux_train_dp:
         aux_train_dp(args.aux_train_dp)
         return
@@ -852,15 +890,19 @@ def main():
     # N > 1: the all-gather of frame k's [rays, 4] tile runs asynchronously (RCCL's own stream) while frame k+1 is rendered;
     # a step waits for the PREVIOUS frame's gather, and the timed region ends only after the last gather has completed.
     pending = []
+    last = {}   # what the latest step() computed (released when the next one starts): --dump-outputs writes the timed window's last
 
     def step():
+        last.clear()
         with torch.no_grad():
             rgb, depth, z, w = field(rays, white_bg=True, is_train=False, N_samples=-1)
+            last.update(rgb=rgb, depth=depth, z_vals=z, weights=w)   # z / w: None unless --weights 1
             if c4 and grouped:   # strong scaling: the frame is complete only when every tile has arrived
                 tile = torch.zeros((cap, 4), dtype=rgb.dtype, device=rgb.device)
                 tile[:R, :3], tile[:R, 3] = rgb, depth
                 out = torch.empty((world * cap, 4), dtype=tile.dtype, device=tile.device)
                 dist.all_gather_into_tensor(out, tile)
+                last["gathered_rgb_depth"] = out
                 return out
             if grouped:
                 tile = torch.cat([rgb, depth[:, None]], 1)
@@ -869,6 +911,7 @@ def main():
                 pending.append((work, out, tile))
                 if len(pending) > 1:
                     pending.pop(0)[0].wait()
+                last["gathered_rgb_depth"] = out
                 return out
             return rgb
 
@@ -879,51 +922,68 @@ def main():
     for _ in range(max(args.warmup, 1)):   # at least one untimed frame: allocations + the per-frame sample counters
         step()
     drain()
-    st = field.stats()
-    # HIP events on the launch stream around the DOMINANT kernel only inside the timed region (the roofline's kernel: the head); an event
-    # pair costs the stream ~10 us of bubble per bracketed kernel group — all four groups of a frame were 1.8 % of it
-    # (profiles/round4_frame_timeline.txt). The other kernels' times come from a short untimed pass below.
-    if args.no_inregion_timing:
-        field.timing(False)
-    else:
-        field.timing(True, kernels=("shade",))
-    field.read_timing(reset=True)
-    # THREE back-to-back blocks of `steps` frames, each bracketed by barrier + synchronize on both sides; ms_per_step is the MEDIAN block
-    # (max over ranks per block). One 20-frame block is ~50 ms of wall clock: a single descheduling of this process (the boxes run
-    # under a cgroup CPU quota) inside it would be the whole figure.
-    block_dt = []
-    for _ in range(3):
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        drain()
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-        block_dt.append(time.perf_counter() - t0)
-    timing = {k: (v[0] / 3.0, v[1] / 3.0) for k, v in field.read_timing(reset=True).items()}   # three blocks -> per block of `steps` frames
-    field.timing(True)
-    aux_steps = max(min(args.steps, 30), 1)
-    with torch.no_grad():
-        for _ in range(min(aux_steps, 10)):   # (the clocks sag while the host reads the timed region's events: not part of this pass)
-            field(rays, white_bg=True, is_train=False, N_samples=-1)
-        torch.cuda.synchronize()
-        field.read_timing(reset=True)
-        for _ in range(aux_steps):
-            field(rays, white_bg=True, is_train=False, N_samples=-1)
+    # then more untimed frames, up to ~WARMUP_S of them (the same count on every rank): the first ~20 frames of a process run ~4 % slow
+    # (clocks), and the timed window starts at steady state
     torch.cuda.synchronize()
-    for k, v in field.read_timing(reset=True).items():   # scaled to the timed region's step count (what the per-step figures below divide by)
-        if k not in timing:
-            timing[k] = (v[0] * args.steps / aux_steps, v[1] * args.steps / aux_steps)
-    field.timing(False)
+    t0 = time.perf_counter()
+    step()
+    drain()
+    torch.cuda.synchronize()
+    extra = min(int(WARMUP_S / max(time.perf_counter() - t0, 1e-4)), 5000)
     if dist is not None:
-        t = torch.tensor(block_dt, device=dev, dtype=torch.float64)
+        t = torch.tensor([float(extra)], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        block_dt = [float(x) for x in t.tolist()]
-    dt = sorted(block_dt)[1]
+        extra = int(t.item())
+    for _ in range(extra):
+        step()
+    drain()
+    warmup_frames = max(args.warmup, 1) + 1 + extra
+    st = field.stats()
+    if args.full:
+        # HIP events on the launch stream around the DOMINANT kernel only inside the timed region (the roofline's kernel: the head); an
+        # event pair costs the stream ~10 us of bubble per bracketed kernel group — all four groups of a frame were 1.8 % of it
+        # (profiles/round4_frame_timeline.txt). The other kernels' times come from a short untimed pass below.
+        if args.no_inregion_timing:
+            field.timing(False)
+        else:
+            field.timing(True, kernels=("shade",))
+        field.read_timing(reset=True)
+    # ONE window of exactly `steps` frames, bracketed by barrier + synchronize on both sides; ms_per_step = window / steps (max over ranks)
+    if dist is not None:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    drain()
+    if dist is not None:
+        dist.barrier()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+    last.clear()
+    timing = {}
+    if args.full:
+        timing = dict(field.read_timing(reset=True))   # per window of `steps` frames
+        field.timing(True)
+        aux_steps = max(min(args.steps, 30), 1)
+        with torch.no_grad():
+            for _ in range(min(aux_steps, 10)):   # (the clocks sag while the host reads the timed region's events: not part of this pass)
+                field(rays, white_bg=True, is_train=False, N_samples=-1)
+            torch.cuda.synchronize()
+            field.read_timing(reset=True)
+            for _ in range(aux_steps):
+                field(rays, white_bg=True, is_train=False, N_samples=-1)
+        torch.cuda.synchronize()
+        for k, v in field.read_timing(reset=True).items():   # scaled to the timed region's step count (what the per-step figures below divide by)
+            if k not in timing:
+                timing[k] = (v[0] * args.steps / aux_steps, v[1] * args.steps / aux_steps)
+        field.timing(False)
+    if dist is not None:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
 
     c4_equal = None
     if c4 and args.check_c4:   # the gathered frame against the whole frame rendered by rank 0 alone (untimed; every rank gathers)
@@ -943,7 +1003,7 @@ def main():
                 c4_equal = bool(torch.equal(g, s_rgb))
             del s_rgb, s_depth
     dp = {}
-    if dist is not None and not args.no_train:   # every rank takes part in the data-parallel train step
+    if dist is not None and args.full and not args.no_train:   # every rank takes part in the data-parallel train step
         try:
             dp = train_bench(dev, iters=args.train_iters, warmup=args.train_warmup, fused_step=True, dist=dist)
         except BaseException:
@@ -960,7 +1020,8 @@ def main():
         k_ms = {k: v[0] / max(v[1], 1) for k, v in timing.items()}        # avg ms per launch
         k_per_step = {k: v[1] / args.steps for k, v in timing.items()}     # launches per step
         frame_ms = {k: v[0] / args.steps for k, v in timing.items()}       # kernel ms per frame
-        pmc, pmc_rec = load_pmc()   # per-launch PMC figures of the same command (tools/pmc_round2.sh), committed under profiles/
+        # per-launch PMC figures of the same command (tools/pmc_round2.sh), committed under profiles/
+        pmc, pmc_rec = load_pmc() if args.full else ({}, {})
         split = not field.mlp_exact_fp32
         two_kernel = "app_features" in frame_ms    # default path: gather + basis kernel, then the sample-stationary head
         roofs = {}
@@ -1029,7 +1090,6 @@ def main():
             # the driver's record keeps the first 24 keys of `config` and only their scalar values: the figures a reader needs come first
             "workload": (f"C4 300^3 ONE 1600x1600 frame in {world} ray tiles" if c4 else "C2 300^3 800x800 view/GPU") +
                         f", N={N}, S1-soft seed 0, white_bg, weights={int(bool(args.weights))}, {'per-ray' if args.per_ray_marcher else 'tile'} marcher",
-            "ms_per_step_blocks": " / ".join(f"{b / args.steps * 1e3:.4f}" for b in block_dt) + " (three blocks of `steps` frames; ms_per_step = median)",
             "sustained_ms_per_step": None,
             "kernel_ms_per_frame_sum": kernel_sum,
             "host_gap_ms_per_step": ms_step - kernel_sum,
@@ -1059,8 +1119,8 @@ def main():
                                f"{N} samples/ray, render_only, scene {args.scene} seed 0, white_bg, weights/z_vals materialised: "
                                f"{bool(args.weights)}, marcher: {'per-ray' if args.per_ray_marcher else '8x8-pixel tiles'}",
             "rays_per_gpu": R, "samples_per_ray": N,
-            "ms_per_step_block_list": [round(b / args.steps * 1e3, 4) for b in block_dt],
-            "inregion_timing": "none" if args.no_inregion_timing else "head only",
+            "warmup_frames": warmup_frames,
+            "inregion_timing": "none" if args.no_inregion_timing or not args.full else "head only",
             "parallelism": f"ray-tile x{world}" + ((" + RCCL all-gather of rgb+depth tiles inside every step" if c4 else
                                                     " + RCCL all-gather of rgb+depth tiles (async, overlapped with the "
                                                     "next frame's render)") if grouped else ""),
@@ -1070,6 +1130,8 @@ def main():
             # which counter record fed roofline.traffic / mfma_busy_frac_pmc / the march's `achieved` (not measured in THIS run)
             "pmc_record": pmc_rec,
         }
+        if not args.full:   # a plain run reports the headline: what only the legs behind --full measure stays out of its line
+            cfg = {k: v for k, v in cfg.items() if k not in FULL_ONLY_CONFIG}
         out = {
             "metric": "ray-samples/s (render) + iters/s (train), 300^3 VM-split, 800x800",
             "value": nominal, "unit": "ray-samples/s",
@@ -1086,6 +1148,8 @@ def main():
             "notes": {"scaling_measured": "the builder has 1-GPU boxes only: see scaling_prediction (N = 1 line) for what one GPU can "
                                           "say about N = 8, and config.rccl (N > 1 lines) for the devices the ranks actually ran on"},
         }
+        if not args.full:
+            del out["roofline"], out["notes"]
         out["config"].update(dp)
         if rccl is not None:
             try:
@@ -1098,18 +1162,19 @@ def main():
             if dp:
                 rccl["all_reduce_bytes_per_train_step"] = int(sum(p.numel() for p in field._all_params()[:12]) * 4)
             out["config"]["rccl"] = rccl
-        try:   # render scratch actually reserved (appearance lists budgeted from the previous frame) next to the worst-case figure
-            from text2nerf_amd import _lib as _L, tensorf as _tf
-            _l = _L.load()
-            out["config"]["workspace"] = {
-                "reserved_GiB": round(_tf.workspace_reserved(dev) / 2 ** 30, 2),
-                "worst_case_GiB": round(int(_l.t2n_render_workspace_bytes(R, N)) / 2 ** 30, 2),
-                "steady_state_hint_GiB": round(int(_l.t2n_render_workspace_bytes_hint(field.sync_params(), R, N)) / 2 ** 30, 2),
-                "list_retries": int(_l.t2n_field_list_retries(field.sync_params())),
-                "note": "image-ordered frames run as one launch with appearance lists sized from earlier frames' counters (read back "
-                        "without waiting); rays that find no room are finished on the device (frames with such rays: list_retries)"}
-        except Exception as e:   # reporting only
-            out["config"]["workspace"] = {"error": repr(e)}
+        if args.full:
+            try:   # render scratch actually reserved (appearance lists budgeted from the previous frame) next to the worst-case figure
+                from text2nerf_amd import _lib as _L, tensorf as _tf
+                _l = _L.load()
+                out["config"]["workspace"] = {
+                    "reserved_GiB": round(_tf.workspace_reserved(dev) / 2 ** 30, 2),
+                    "worst_case_GiB": round(int(_l.t2n_render_workspace_bytes(R, N)) / 2 ** 30, 2),
+                    "steady_state_hint_GiB": round(int(_l.t2n_render_workspace_bytes_hint(field.sync_params(), R, N)) / 2 ** 30, 2),
+                    "list_retries": int(_l.t2n_field_list_retries(field.sync_params())),
+                    "note": "image-ordered frames run as one launch with appearance lists sized from earlier frames' counters (read back "
+                            "without waiting); rays that find no room are finished on the device (frames with such rays: list_retries)"}
+            except Exception as e:   # reporting only
+                out["config"]["workspace"] = {"error": repr(e)}
         if c4_equal is not None:
             out["config"]["c4_gathered_equals_single_rank"] = c4_equal
 
@@ -1123,7 +1188,7 @@ def main():
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) / n * 1e3
 
-        if not grouped and not c4 and not args.quick:
+        if args.full and not grouped and not c4 and not args.quick:
             # sustained clocks: the same frame for >= 2 s
             n_sus = max(int(2200.0 / max(ms_step, 0.1)), args.steps)
             out["config"]["sustained_ms_per_step"] = timed_frames(n_sus)
@@ -1206,7 +1271,7 @@ def main():
                 out["config"]["exact_fp32_ms_per_step"] = ms_exact
                 out["config"]["exact_fp32_value_ray_samples_per_s"] = R * N / (ms_exact * 1e-3)
                 out["config"]["exact_fp32_shade_frac_of_f32_mfma_peak"] = ex.get("frac")
-        if not grouped and not c4 and not args.quick:
+        if args.full and not grouped and not c4 and not args.quick:
             # early ray termination (eval renders without weights / z_vals; the mirror's default eps 1e-6): frame time and evaluated
             # samples with it on and off, on the bench scene (soft walls: T ~ 4e-4 behind them, nothing to skip), on fog (S2) and on
             # opaque walls (S1-sharp)
@@ -1248,7 +1313,7 @@ def main():
                 out["config"]["general_shape_ms"] = general_shape_ms(dev)
             except Exception as e:  # noqa: BLE001
                 out["config"]["general_shape_ms"] = {"error": repr(e)[:300]}
-        if not grouped and not args.no_train:
+        if args.full and not grouped and not args.no_train:
             # the fused step first, from a clean allocator: its peak reserved memory is the train figure (the render legs above
             # leave 2.65-GB weight tensors and worst-case workspaces in torch's cache)
             try:
@@ -1274,7 +1339,7 @@ def main():
             out["config"].update(train_bench(dev, iters=args.train_iters, warmup=args.train_warmup))
             out["config"].update(train_bench(dev, iters=args.train_iters, warmup=args.train_warmup, fused_optim=True))
             out["config"].update(train_bench(dev, iters=args.train_iters, warmup=args.train_warmup, fused_step=True, resident=True))
-        if not grouped and not c4 and not args.quick:
+        if args.full and not grouped and not c4 and not args.quick:
             out["scaling_prediction"] = sp = scaling_prediction(field, dev, out["config"].get("train_ms_per_iter_fused_step"))
             out["config"]["train_ms_per_iter_fused_step_2048_rays"] = sp.get("train_dp", {}).get("fused_step_ms_by_rays_per_gpu", {}).get("2048")
             out["config"]["scaling_prediction_headline"] = {
@@ -1284,7 +1349,7 @@ def main():
                 "train_dp_step_ms_at_2048_rays": sp.get("train_dp", {}).get("fused_step_ms_by_rays_per_gpu", {}).get("2048"),
                 "train_dp_all_reduce_estimate_ms": sp.get("train_dp", {}).get("all_reduce_estimate_ms"),
                 "note": "one-GPU predictions (tile times, link-rate estimates), not measurements: see scaling_prediction"}
-        if not grouped and not args.no_cpu_baseline:
+        if args.full and not grouped and not args.no_cpu_baseline:
             def hip_render(r):
                 with torch.no_grad():
                     a, b, _, _ = field(r.to(dev), white_bg=True, is_train=False, N_samples=-1)

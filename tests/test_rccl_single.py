@@ -43,7 +43,7 @@ def test_bench_py_over_rccl_with_one_rank(tmp_path, mode):
         port = s.getsockname()[1]
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), T2N_BENCH_FORCE_GROUP="1",
                HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="8", T2N_BENCH_DEADLINE_S="200", PYTHONFAULTHANDLER="1")
-    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--train-iters", "2", "--train-warmup", "1"]
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--train-iters", "2", "--train-warmup", "1"]
     if mode == "c4":
         args += ["--mode", "c4", "--check-c4", "--no-train"]
     p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, cwd=ROOT, stdout=subprocess.PIPE,

@@ -77,7 +77,7 @@ def one_json_line(outs):
 
 
 def test_two_ranks_on_one_gpu_over_gloo(tmp_path):
-    rcs, outs, errs = run_ranks(tmp_path, ["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--train-iters", "2",
+    rcs, outs, errs = run_ranks(tmp_path, ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--train-iters", "2",
                                            "--train-warmup", "1"])
     check_finished(rcs, outs, errs)
     d = one_json_line(outs)
@@ -96,7 +96,7 @@ def test_two_ranks_on_one_gpu_over_gloo(tmp_path):
 def test_c4_mode_two_ranks_on_one_gpu_over_gloo(tmp_path):
     """BASELINE configs[3]: ONE 1600x1600 frame split into ray tiles, all-gather inside the timed region, gathered frame
     bitwise equal to the single-rank render (checked by bench.py itself on rank 0 with --check-c4)."""
-    rcs, outs, errs = run_ranks(tmp_path, ["--mode", "c4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-train",
+    rcs, outs, errs = run_ranks(tmp_path, ["--mode", "c4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-train",
                                            "--check-c4"])
     check_finished(rcs, outs, errs)
     d = one_json_line(outs)

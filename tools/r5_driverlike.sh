@@ -5,7 +5,7 @@ out=gpurun_out/r5_driverlike_$tag
 mkdir -p $out
 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; tail -1 $out/smoke.log
 for i in $(seq 1 $n); do
-  ( time python3 bench.py --gpus 1 --steps 20 --warmup 5 $extra ) > $out/bench_$i.json 2> $out/bench_$i.err
+  ( time python3 bench.py --gpus 1 --steps 20 --warmup 5 --full $extra ) > $out/bench_$i.json 2> $out/bench_$i.err
   python3 - <<PY
 import json
 d=json.loads(open("$out/bench_$i.json").read().strip().splitlines()[-1])
