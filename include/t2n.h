@@ -250,14 +250,22 @@ int t2n_render_forward(t2n_field* f, const float* rays, int64_t n_rays, int ray_
  * shapes the reference accepts through n_lamb_sigma / n_lamb_sh / data_dim_color / fea_pe / featureC (models/tensoRF.py:144-160,
  * models/tensorBase.py:62-159, e_opt.py:83-107). No field handle: the parameters are read in place in the reference's layouts and the
  * gradients are ACCUMULATED (atomics) into tensors of the same layouts. One thread per ray / per appearance sample, no MFMA: a slow
- * path. Heads: MLP_Fea_noview, MLP_Fea, MLP, SH, RGB. No NDC sampling, no AlphaGridMask. `weights` / `z_vals` may be NULL in the forward
- * (kept in the workspace then); the backward takes the forward's workspace (and the same weights / z_vals pointers) unchanged. */
+ * path. Heads: MLP_Fea_noview, MLP_Fea, MLP, SH, RGB. NDC sampling (T2N_FLAG_NDC: `jitter` is then the [n_samples] depth table, as in
+ * t2n_render_forward) and the AlphaGridMask (the descriptor's alpha_volume: masked samples are neither evaluated nor differentiated,
+ * models/tensorBase.py:451-456) in forward and backward. `weights` / `z_vals` may be NULL in the forward (kept in the workspace then);
+ * the backward takes the forward's workspace (and the same weights / z_vals pointers) unchanged.
+ * alpha_volume: NULL (no mask: a zeroed tail behaves as before it existed) or the AlphaGridMask occupancy volume on the device,
+ * [alpha_dims[0] = D (z)][alpha_dims[1] = H (y)][alpha_dims[2] = W (x)] fp32, over the box alpha_aabb_min / alpha_aabb_max
+ * (models/tensorBase.py:41-59). */
 typedef struct t2n_generic_desc {
     float aabb_min[3], aabb_max[3], inv_aabb_size[3];
     int32_t grid[3];
     int32_t density_n_comp[3], app_n_comp[3];
     int32_t app_dim, shading, fea_pe, view_pe, feature_c, act;
     float density_shift, distance_scale, weight_thres, step_size, near, far, z_gate;
+    const float* alpha_volume;
+    int32_t alpha_dims[3];
+    float alpha_aabb_min[3], alpha_aabb_max[3];
 } t2n_generic_desc;
 size_t t2n_generic_workspace_bytes(int64_t n_rays, int n_samples);
 /* the same + room for channel-last staging copies of the factor tensors and the appearance-sample list: with this much workspace the
@@ -271,6 +279,17 @@ int t2n_generic_backward(const t2n_generic_desc* desc, const t2n_field_params* p
                          int n_samples, uint32_t flags, const float* jitter, const float* weights, const float* z_vals,
                          const float* d_rgb, const float* d_depth, const float* d_weights, const t2n_field_grads* grads,
                          void* workspace, size_t workspace_bytes, t2n_stream stream);
+/* getDenseAlpha on the general-shape path (models/tensorBase.py:328-344, compute_alpha :412-434): alpha = 1 - exp(-sigma * length) at
+ * the nodes aabb_min*(1-s) + aabb_max*s of a dense grid, s = (lin_x[i], lin_y[j], lin_z[k]) (device arrays holding torch.linspace(0,1,g));
+ * sigma = 0 where the descriptor's alpha_volume (if any) samples <= 0. alpha is [gx][gy][gz]. Only the density factors and the
+ * descriptor are read. Threshold, dilation and bounding box (updateAlphaMask, :346-370) are t2n_alpha_volume's. */
+int t2n_generic_dense_alpha(const t2n_generic_desc* desc, const t2n_field_params* params, const float* lin_x, const float* lin_y,
+                            const float* lin_z, int gx, int gy, int gz, float length, float* alpha, t2n_stream stream);
+/* filtering_rays on the general-shape path (models/tensorBase.py:372-404): bbox_only != 0 — the slab test t_max > t_min against
+ * aabb_min / aabb_max (:385-391); bbox_only == 0 — any of the ray's first n_samples eval samples (t_min + i * step, no box test) reads
+ * the descriptor's alpha_volume > 0 (:393-395; needs a mask). mask[r] = 0 / 1. No parameters are read. */
+int t2n_generic_filter_rays(const t2n_generic_desc* desc, const float* rays, int64_t n_rays, int ray_stride, int n_samples, int bbox_only,
+                            uint8_t* mask, t2n_stream stream);
 
 /* ndc_rays_blender (blender = 1) / ndc_rays (0) (dataLoader/ray_utils.py:88-124): [n,3] origins + directions -> NDC. */
 int t2n_ndc_rays(int H, int W, float focal, float near, int blender, const float* rays_o, const float* rays_d, int64_t n,

@@ -50,7 +50,9 @@ class GenericDesc(C.Structure):   # t2n_generic_desc: the general-shape path (cs
                 ("density_n_comp", C.c_int32 * 3), ("app_n_comp", C.c_int32 * 3), ("app_dim", C.c_int32), ("shading", C.c_int32),
                 ("fea_pe", C.c_int32), ("view_pe", C.c_int32), ("feature_c", C.c_int32), ("act", C.c_int32),
                 ("density_shift", C.c_float), ("distance_scale", C.c_float), ("weight_thres", C.c_float), ("step_size", C.c_float),
-                ("near", C.c_float), ("far", C.c_float), ("z_gate", C.c_float)]
+                ("near", C.c_float), ("far", C.c_float), ("z_gate", C.c_float),
+                ("alpha_volume", C.c_void_p), ("alpha_dims", C.c_int32 * 3), ("alpha_aabb_min", C.c_float * 3),
+                ("alpha_aabb_max", C.c_float * 3)]
 
 TRAIN_HYPER_FLOATS = 32
 TRAIN_HEAD_GRAD_FLOATS = 27 * 144 + 128 * 351 + 128 + 128 * 128 + 128 + 3 * 128 + 3 + 1   # + the vote word
@@ -169,6 +171,10 @@ SIGNATURES = {
     "t2n_generic_backward": (C.c_int, [C.POINTER(GenericDesc), C.POINTER(FieldParams), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FieldGrads),
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_generic_dense_alpha": (C.c_int, [C.POINTER(GenericDesc), C.POINTER(FieldParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "t2n_generic_filter_rays": (C.c_int, [C.POINTER(GenericDesc), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
     "t2n_train_step_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int, C.c_int64]),
     "t2n_train_step": (C.c_int, [C.c_void_p, C.POINTER(TrainStepArgs), C.c_void_p]),
     "t2n_field_train_set_step": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -3,10 +3,14 @@
 // (models/tensoRF.py:144-160, models/tensorBase.py:62-159, e_opt.py:83-107); here they run as a plain restatement — one thread per
 // ray for the march, one thread per appearance sample for the head, loops over the component / unit counts, parameters read in place
 // in the reference's own layouts ([1,C,H,W] planes, [1,C,L,1] lines), gradients accumulated with atomics into those layouts. No MFMA,
-// no LDS staging: a path that removes the shape limit, not a fast one (the driver's configuration never comes here).
+// no LDS staging: a path that removes the shape limit, not a fast one (the driver's configuration never comes here). NDC sampling (the
+// depth table in FieldDev::ztab, |d|-scaled distances, unit view directions) and the AlphaGridMask (the descriptor's volume, tested in
+// gen_point: masked samples are neither evaluated nor differentiated) in every kernel, forward and backward; getDenseAlpha on the
+// reference layouts (k_gen_dense_alpha) and filtering_rays from the descriptor (the field path's k_filter_bbox / k_filter_alpha).
 //
-// Replaces: models/tensorBase.py:304-323 (sample_ray), :436-507 (forward), :19-26 (raw2alpha), :406-410 (feature2density), :11-17 +
-// :62-159 (the heads), :29-39 (SH / RGB), models/tensoRF.py:205-239 (compute_densityfeature / compute_appfeature), and their autograd.
+// Replaces: models/tensorBase.py:293-323 (sample_ray_ndc, sample_ray), :436-507 (forward, its NDC and mask lines :441-456), :19-26
+// (raw2alpha), :406-410 (feature2density), :11-17 + :62-159 (the heads), :29-39 (SH / RGB), :328-344 + :412-434 (getDenseAlpha /
+// compute_alpha), :372-404 (filtering_rays), models/tensoRF.py:205-239 (compute_densityfeature / compute_appfeature), and their autograd.
 #include <stdlib.h>
 
 #include "t2n_device.h"
@@ -76,11 +80,24 @@ __device__ __forceinline__ float gen_density_feature(const GenArgs& a, const Tap
     return feat;
 }
 
+// box test, eval z gate and — when the field carries one — the AlphaGridMask (models/tensorBase.py:451-456): a masked sample is not
+// evaluated and gets no density gradient. MASK = false: coordinates of a sample already known to be valid (the appearance kernels)
+template <bool MASK = true>
 __device__ __forceinline__ bool gen_point(const GenArgs& a, const Ray& ray, float z, float& xn, float& yn, float& zn) {
-    return a.train ? sample_point<true>(a.F, ray, z, xn, yn, zn) : sample_point<false>(a.F, ray, z, xn, yn, zn);
+    bool ok = a.train ? sample_point<true>(a.F, ray, z, xn, yn, zn) : sample_point<false>(a.F, ray, z, xn, yn, zn);
+    if (MASK && a.F.alpha && ok) ok = alpha_pass(a.F, ray, z);
+    return ok;
 }
+// z_i: t_min + step (i [+ u]), or the NDC depth table (F.ztab) shared by all rays
 __device__ __forceinline__ float gen_z(const GenArgs& a, const Ray& ray, int i, float u) {
-    return a.train ? sample_z<true, true>(a.F, ray, i, u) : sample_z<false, true>(a.F, ray, i, 0.f);
+    return a.train ? sample_z<true>(a.F, ray, i, u) : sample_z<false>(a.F, ray, i, 0.f);
+}
+// the ray's jitter draw (train mode; on the NDC path `jitter` is the [N] depth table instead)
+__device__ __forceinline__ float gen_u(const GenArgs& a, long long r) { return (a.train && !a.F.ztab) ? a.jitter[r] : 0.f; }
+// the heads' view direction: the ray's d, divided by |d| on the NDC path (models/tensorBase.py:445)
+__device__ __forceinline__ void gen_dir(const GenArgs& a, const Ray& ray, float* dir) {
+    dir[0] = ray.dx; dir[1] = ray.dy; dir[2] = ray.dz;
+    if (a.F.ztab) { dir[0] = dir[0] / ray.norm; dir[1] = dir[1] / ray.norm; dir[2] = dir[2] / ray.norm; }
 }
 
 // ---- march: one thread per ray --------------------------------------------------------------------------------------------------
@@ -88,7 +105,7 @@ __global__ __launch_bounds__(64) void k_gen_march(const GenArgs a) {
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= a.n_rays) return;
     const Ray ray = load_ray(a.F, a.rays + r * a.ray_stride, a.ray_stride);
-    const float u = a.train ? a.jitter[r] : 0.f;
+    const float u = gen_u(a, r);
     const int N = a.N;
     float T = 1.f, acc = 0.f, dep = 0.f;
     unsigned long long nev = 0, napp = 0;
@@ -99,7 +116,7 @@ __global__ __launch_bounds__(64) void k_gen_march(const GenArgs a) {
         float sg = 0.f;
         if (ok) { sg = feature2density(a.F, gen_density_feature(a, gen_taps(a, xn, yn, zn))); ++nev; }
         const float dist = i < N - 1 ? gen_z(a, ray, i + 1, u) - z : 0.f;                 // :448
-        const float alpha = 1.f - expf((-sg) * (dist * a.F.dscale));                      // :19-26
+        const float alpha = 1.f - expf((-sg) * scaled_dist(a.F, ray, dist));              // :19-26, :443-444
         const float w = alpha * T;
         a.z[r * N + i] = z; a.sigma[r * N + i] = sg; a.T[r * N + i] = T; a.w[r * N + i] = w;
         T = T * ((1.f - alpha) + 1e-10f);
@@ -177,13 +194,14 @@ __global__ __launch_bounds__(64) void k_gen_shade(const GenArgs a) {
     const int i = (int)(t - r * N);
     const float* __restrict__ rp = a.rays + r * a.ray_stride;
     const Ray ray = load_ray(a.F, rp, a.ray_stride);
-    const float u = a.train ? a.jitter[r] : 0.f;
+    const float u = gen_u(a, r);
     float xn, yn, zn;
-    gen_point(a, ray, gen_z(a, ray, i, u), xn, yn, zn);
+    gen_point<false>(a, ray, gen_z(a, ray, i, u), xn, yn, zn);
     const Tap3 tp = gen_taps(a, xn, yn, zn);
     float feat[kGenDimMax];
     gen_features(a, tp, feat);
-    const float dir[3] = {rp[3], rp[4], rp[5]};
+    float dir[3];
+    gen_dir(a, ray, dir);
     float gfeat[kGenDimMax];
     if (BACKWARD) for (int f = 0; f < a.app_dim; ++f) gfeat[f] = 0.f;
     const float* __restrict__ go = BACKWARD ? a.go + t * 3 : nullptr;
@@ -320,7 +338,7 @@ __global__ __launch_bounds__(64) void k_gen_bwd_march(const GenArgs a) {
             }
         }
         const float dist = i < N - 1 ? a.z[t + 1] - z : 0.f;
-        const float sd = dist * a.F.dscale;
+        const float sd = scaled_dist(a.F, ray, dist);
         const float e = expf((-sg) * sd);                     // 1 - alpha
         const float fct = e + 1e-10f;                          // T_{i+1} = T_i * fct (fct = (1 - alpha) + 1e-10, alpha = 1 - e)
         const float dalpha = G * T - S / fct;
@@ -424,7 +442,7 @@ __global__ __launch_bounds__(256) void k_gen_sigma(const GenArgs a, const GenFas
     const long long r = t / N;
     const int i = (int)(t - r * N);
     const Ray ray = load_ray(a.F, a.rays + r * a.ray_stride, a.ray_stride);
-    const float u = a.train ? a.jitter[r] : 0.f;
+    const float u = gen_u(a, r);
     const float z = gen_z(a, ray, i, u);
     float xn, yn, zn;
     float sg = 0.f;
@@ -446,7 +464,7 @@ __global__ __launch_bounds__(64) void k_gen_scan(const GenArgs a) {
         const float sg = a.sigma[r * N + i];
         nev += a.T[r * N + i] != 0.f ? 1u : 0u;
         const float dist = i < N - 1 ? zn - z : 0.f;
-        const float alpha = 1.f - expf((-sg) * (dist * a.F.dscale));
+        const float alpha = 1.f - expf((-sg) * scaled_dist(a.F, ray, dist));
         const float w = alpha * T;
         a.T[r * N + i] = T; a.w[r * N + i] = w;
         T = T * ((1.f - alpha) + 1e-10f);
@@ -474,6 +492,9 @@ __global__ __launch_bounds__(256) void k_gen_scan_compact(const GenArgs a, const
     float carry = 1.f, acc = 0.f, dep = 0.f;
     unsigned nev = 0, napp = 0;
     if (live) {
+        Ray nray{};                   // |d| for the NDC distance scaling (:443-444); not read on the regular path
+        nray.norm = 1.f;
+        if (a.F.ztab) nray = load_ray(a.F, a.rays + r * a.ray_stride, a.ray_stride);
         for (int base = 0; base < N; base += 64) {
             const int i = base + lane;
             const bool in = i < N;
@@ -483,7 +504,7 @@ __global__ __launch_bounds__(256) void k_gen_scan_compact(const GenArgs a, const
             const float sg = in ? a.sigma[t] : 0.f;
             const bool box = in && a.T[t] != 0.f;
             const float dist = (in && i < N - 1) ? zn - z : 0.f;
-            const float alpha = 1.f - expf((-sg) * (dist * a.F.dscale));
+            const float alpha = 1.f - expf((-sg) * scaled_dist(a.F, nray, dist));
             const float f = in ? (1.f - alpha) + 1e-10f : 1.f;
             const float incl = wave_scan_mul(f, lane);
             float excl = __shfl_up(incl, 1);
@@ -616,11 +637,12 @@ __device__ __forceinline__ void gen_head_body(const GenArgs& a, const GenFast& f
         const int i = (int)(t - r * a.N);
         const float* __restrict__ rp = a.rays + r * a.ray_stride;
         const Ray ray = load_ray(a.F, rp, a.ray_stride);
-        const float u = a.train ? a.jitter[r] : 0.f;
+        const float u = gen_u(a, r);
         float xn, yn, zn;
-        gen_point(a, ray, gen_z(a, ray, i, u), xn, yn, zn);
+        gen_point<false>(a, ray, gen_z(a, ray, i, u), xn, yn, zn);
         const Tap3 tp = gen_taps(a, xn, yn, zn);
-        const float dir[3] = {rp[3], rp[4], rp[5]};
+        float dir[3];
+        gen_dir(a, ray, dir);
         // ---- appearance features: wave g takes a quarter of every plane's components ---------------------------------------------------
         {
             float fp[DMAX];
@@ -805,19 +827,35 @@ __global__ __launch_bounds__(256) void k_gen_out(const GenArgs a, const GenFast 
     }
 }
 
+// the scalars of a FieldDev from the descriptor (no factor sets), and the AlphaGridMask when the descriptor carries one: the same
+// fields t2n_field_set_alpha_mask fills, with the normalisation scale (1 / size) * 2 of AlphaGridMask.__init__ (models/tensorBase.py:46-47)
+static int gen_field(FieldDev& F, const t2n_generic_desc* d, const char* who) {
+    memset(&F, 0, sizeof(F));
+    for (int k = 0; k < 3; ++k) { F.aabb0[k] = d->aabb_min[k]; F.aabb1[k] = d->aabb_max[k]; F.inv[k] = d->inv_aabb_size[k]; }
+    F.shift = d->density_shift; F.dscale = d->distance_scale; F.thres = d->weight_thres; F.step = d->step_size;
+    F.near = d->near; F.far = d->far; F.zgate = d->z_gate; F.act = d->act; F.shading = d->shading; F.app_dim = d->app_dim;
+    if (d->alpha_volume) {
+        if (d->alpha_dims[0] < 1 || d->alpha_dims[1] < 1 || d->alpha_dims[2] < 1) { set_error("%s: bad alpha_dims", who); return T2N_ERR_INVALID; }
+        F.alpha = d->alpha_volume; F.aD = d->alpha_dims[0]; F.aH = d->alpha_dims[1]; F.aW = d->alpha_dims[2];
+        for (int k = 0; k < 3; ++k) {
+            const float size = d->alpha_aabb_max[k] - d->alpha_aabb_min[k];
+            F.a_min[k] = d->alpha_aabb_min[k]; F.a_inv[k] = (1.f / size) * 2.f;
+        }
+    }
+    return T2N_OK;
+}
+
 static int gen_fill(GenArgs& a, const t2n_generic_desc* d, const t2n_field_params* p, const char* who) {
     if (!d || !p) { set_error("%s: NULL argument", who); return T2N_ERR_INVALID; }
     memset(&a, 0, sizeof(a));
     FieldDev& F = a.F;
+    if (int rc = gen_field(F, d, who)) return rc;
     for (int k = 0; k < 3; ++k) {
-        F.aabb0[k] = d->aabb_min[k]; F.aabb1[k] = d->aabb_max[k]; F.inv[k] = d->inv_aabb_size[k];
         a.grid[k] = d->grid[k]; a.Cd[k] = d->density_n_comp[k]; a.Ca[k] = d->app_n_comp[k];
         if (d->grid[k] < 2 || a.Cd[k] < 1 || a.Ca[k] < 1) { set_error("%s: bad grid / component counts", who); return T2N_ERR_INVALID; }
         a.dp[k] = p->density_plane[k]; a.dl[k] = p->density_line[k]; a.ap[k] = p->app_plane[k]; a.al[k] = p->app_line[k];
         if (!a.dp[k] || !a.dl[k] || !a.ap[k] || !a.al[k]) { set_error("%s: NULL factor tensor", who); return T2N_ERR_INVALID; }
     }
-    F.shift = d->density_shift; F.dscale = d->distance_scale; F.thres = d->weight_thres; F.step = d->step_size;
-    F.near = d->near; F.far = d->far; F.zgate = d->z_gate; F.act = d->act; F.shading = d->shading; F.app_dim = d->app_dim;
     a.app_dim = d->app_dim; a.shading = d->shading; a.fea_pe = d->fea_pe; a.view_pe = d->view_pe; a.fC = d->feature_c;
     a.basis = p->basis_weight; a.w0 = p->mlp_w0; a.b0 = p->mlp_b0; a.w1 = p->mlp_w1; a.b1 = p->mlp_b1; a.w2 = p->mlp_w2; a.b2 = p->mlp_b2;
     if (!a.basis) { set_error("%s: NULL basis_weight", who); return T2N_ERR_INVALID; }
@@ -895,6 +933,29 @@ static size_t gen_head_lds(const t2n_generic_desc* d, bool rows_only = false) {
     return (ncol * D + D * 64 + 16 * 64 + hb * 64) * sizeof(float);
 }
 
+// getDenseAlpha on the reference layouts (models/tensorBase.py:328-344 -> compute_alpha :412-434): one thread per node
+// (i, j, k) = aabb0 * (1 - s) + aabb1 * s, s = (lin_x[i], lin_y[j], lin_z[k]) — the node arithmetic of k_compute_alpha —, sigma = 0 where
+// the field's mask (if any) samples <= 0, alpha = 1 - exp(-sigma * length); output index ((i * gy) + j) * gz + k
+__global__ __launch_bounds__(256) void k_gen_dense_alpha(const GenArgs a, const float* __restrict__ lin_x, const float* __restrict__ lin_y,
+                                                         const float* __restrict__ lin_z, int gy, int gz, long long n, float length,
+                                                         float* __restrict__ alpha) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const FieldDev& F = a.F;
+    const long long ij = p / gz;
+    const int k = (int)(p - ij * gz), j = (int)(ij % gy), i = (int)(ij / gy);
+    const float sx = lin_x[i], sy = lin_y[j], sz = lin_z[k];
+    const float px = F.aabb0[0] * (1.f - sx) + F.aabb1[0] * sx;
+    const float py = F.aabb0[1] * (1.f - sy) + F.aabb1[1] * sy;
+    const float pz = F.aabb0[2] * (1.f - sz) + F.aabb1[2] * sz;
+    float sg = 0.f;
+    if (!F.alpha || alpha_value(F, px, py, pz) > 0.f) {
+        const float xn = (px - F.aabb0[0]) * F.inv[0] - 1.f, yn = (py - F.aabb0[1]) * F.inv[1] - 1.f, zn = (pz - F.aabb0[2]) * F.inv[2] - 1.f;
+        sg = feature2density(F, gen_density_feature(a, gen_taps(a, xn, yn, zn)));
+    }
+    alpha[p] = 1.f - expf((-sg) * length);
+}
+
 }  // namespace t2n
 
 using namespace t2n;
@@ -914,14 +975,14 @@ extern "C" size_t t2n_generic_workspace_bytes(int64_t n_rays, int n_samples) {
 static int gen_bind(GenArgs& a, const float* rays, int64_t n_rays, int ray_stride, int n_samples, uint32_t flags, const float* jitter,
                     float* weights, float* z_vals, void* workspace, size_t workspace_bytes, const char* who) {
     if (!rays || !workspace || n_rays <= 0 || ray_stride < 6 || n_samples < 1) { set_error("%s: bad argument", who); return T2N_ERR_INVALID; }
-    if (flags & T2N_FLAG_NDC) { set_error("%s: NDC sampling is not available on the general-shape path", who); return T2N_ERR_UNSUPPORTED; }
-    if ((flags & T2N_FLAG_TRAIN) && !jitter) { set_error("%s: train mode needs the jitter draws", who); return T2N_ERR_INVALID; }
+    if ((flags & (T2N_FLAG_TRAIN | T2N_FLAG_NDC)) && !jitter) { set_error("%s: train / NDC mode needs the jitter draws / depth table", who); return T2N_ERR_INVALID; }
     if ((uint64_t)n_rays * (uint64_t)n_samples > 0x7fffffffull) { set_error("%s: more than 2^31 samples per call (chunk the rays)", who); return T2N_ERR_UNSUPPORTED; }
     const GenCarve c = gen_carve(n_rays, n_samples, true);
     if (c.total > workspace_bytes) { set_error("%s: workspace %zu B < %zu B", who, workspace_bytes, c.total); return T2N_ERR_WORKSPACE; }
     char* ws = (char*)workspace;
     a.rays = rays; a.n_rays = n_rays; a.ray_stride = ray_stride; a.N = n_samples;
     a.train = (flags & T2N_FLAG_TRAIN) ? 1 : 0; a.add_bg = (flags & T2N_FLAG_ADD_BG) ? 1 : 0; a.jitter = jitter;
+    a.F.ztab = (flags & T2N_FLAG_NDC) ? jitter : nullptr;       // NDC: `jitter` is the [n_samples] depth table (as t2n_render_forward)
     a.w = weights ? weights : (float*)(ws + c.w); a.z = z_vals ? z_vals : (float*)(ws + c.z);
     a.sigma = (float*)(ws + c.sigma); a.T = (float*)(ws + c.T); a.rgb_s = (float*)(ws + c.rgb_s); a.acc = (float*)(ws + c.acc);
     a.raw = (float*)(ws + c.raw); a.go = (float*)(ws + c.go);
@@ -1034,4 +1095,28 @@ extern "C" int t2n_generic_backward(const t2n_generic_desc* desc, const t2n_fiel
     hipLaunchKernelGGL(k_gen_shade<true>, dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, s, a);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
+}
+
+extern "C" int t2n_generic_dense_alpha(const t2n_generic_desc* desc, const t2n_field_params* params, const float* lin_x, const float* lin_y,
+                                       const float* lin_z, int gx, int gy, int gz, float length, float* alpha, t2n_stream stream) {
+    GenArgs a;
+    int rc = gen_fill(a, desc, params, "t2n_generic_dense_alpha");
+    if (rc) return rc;
+    if (!lin_x || !lin_y || !lin_z || !alpha || gx < 1 || gy < 1 || gz < 1) { set_error("t2n_generic_dense_alpha: bad argument"); return T2N_ERR_INVALID; }
+    const long long n = (long long)gx * gy * gz;
+    hipLaunchKernelGGL(k_gen_dense_alpha, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, lin_x, lin_y, lin_z, gy, gz,
+                       n, length, alpha);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
+extern "C" int t2n_generic_filter_rays(const t2n_generic_desc* desc, const float* rays, int64_t n_rays, int ray_stride, int n_samples, int bbox_only,
+                                       uint8_t* mask, t2n_stream stream) {
+    if (!desc || !rays || !mask || n_rays < 0 || ray_stride < 6 || (!bbox_only && n_samples < 1)) { set_error("t2n_generic_filter_rays: bad argument"); return T2N_ERR_INVALID; }
+    FieldDev F;
+    if (int rc = gen_field(F, desc, "t2n_generic_filter_rays")) return rc;
+    if (!bbox_only && !F.alpha) { set_error("t2n_generic_filter_rays: bbox_only = 0 needs the descriptor's alpha_volume"); return T2N_ERR_STATE; }
+    if (n_rays == 0) return T2N_OK;
+    return bbox_only ? launch_filter_bbox(F, rays, (long long)n_rays, ray_stride, mask, (hipStream_t)stream)
+                     : launch_filter_alpha(F, rays, (long long)n_rays, ray_stride, n_samples, mask, (hipStream_t)stream);
 }

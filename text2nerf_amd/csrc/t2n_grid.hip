@@ -155,6 +155,12 @@ __global__ __launch_bounds__(256) void k_filter_alpha(const FieldDev F, const fl
 
 using namespace t2n;
 
+int t2n::launch_filter_alpha(const FieldDev& F, const float* rays, long long n_rays, int ray_stride, int n_samples, uint8_t* mask, hipStream_t s) {
+    hipLaunchKernelGGL(k_filter_alpha, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, s, F, rays, n_rays, ray_stride, n_samples, mask);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
 static int launch_alpha(const t2n_field* f, const AlphaArgs& a, hipStream_t s) {
     const long long threads = a.n * 4;
     hipLaunchKernelGGL(k_compute_alpha, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
@@ -213,8 +219,5 @@ extern "C" int t2n_filter_rays_alpha(const t2n_field* f, const float* rays, int6
     if (!f || !rays || !mask || n_rays < 0 || ray_stride < 6 || n_samples < 1) { set_error("t2n_filter_rays_alpha: bad argument"); return T2N_ERR_INVALID; }
     if (!f->dev.alpha) { set_error("t2n_filter_rays_alpha: the field has no alpha mask"); return T2N_ERR_STATE; }
     if (n_rays == 0) return T2N_OK;
-    hipLaunchKernelGGL(k_filter_alpha, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, (hipStream_t)stream, f->dev, rays,
-                       (long long)n_rays, ray_stride, n_samples, mask);
-    T2N_HIP(hipGetLastError());
-    return T2N_OK;
+    return launch_filter_alpha(f->dev, rays, (long long)n_rays, ray_stride, n_samples, mask, (hipStream_t)stream);
 }

@@ -170,6 +170,10 @@ struct RenderLaunch {
 };
 int launch_march(t2n_field* f, const RenderLaunch& L, hipStream_t s);
 int launch_ray_stats(const RenderLaunch& L, hipStream_t s);
+// filtering_rays' two tests (models/tensorBase.py:385-395) on the scalars / mask of F (no factors read): k_filter_bbox (t2n_march.hip),
+// k_filter_alpha (t2n_grid.hip; F.alpha set, F.ztab NULL). Shared by the field-handle exports and the general-shape path's.
+int launch_filter_bbox(const FieldDev& F, const float* rays, long long n_rays, int ray_stride, uint8_t* mask, hipStream_t s);
+int launch_filter_alpha(const FieldDev& F, const float* rays, long long n_rays, int ray_stride, int n_samples, uint8_t* mask, hipStream_t s);
 // spill: [n_rays][n_samples] scratch rows (used only when L.weights is NULL); scratch: [n_rays][n_samples / 4] staging entries
 int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h, float* spill, float4* scratch, hipStream_t s);
 constexpr int kLists = 8;   // appearance sub-lists per sub-launch

@@ -433,6 +433,12 @@ int launch_march(t2n_field* f, const RenderLaunch& L, hipStream_t s) {
 #ifndef T2N_STATS_BLOCKS
 #define T2N_STATS_BLOCKS 128
 #endif
+int launch_filter_bbox(const FieldDev& F, const float* rays, long long n_rays, int ray_stride, uint8_t* mask, hipStream_t s) {
+    hipLaunchKernelGGL(k_filter_bbox, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, s, F, rays, n_rays, ray_stride, mask);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
 int launch_ray_stats(const RenderLaunch& L, hipStream_t s) {
     if (L.stats) {
         unsigned nb = (unsigned)((L.n_rays + 255) / 256);
@@ -525,10 +531,7 @@ extern "C" int t2n_filter_rays_bbox(const t2n_field* f, const float* rays, int64
                                     t2n_stream stream) {
     if (!f || !rays || !mask || n_rays < 0 || ray_stride < 6) { set_error("t2n_filter_rays_bbox: bad argument"); return T2N_ERR_INVALID; }
     if (n_rays == 0) return T2N_OK;
-    hipLaunchKernelGGL(k_filter_bbox, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f->dev,
-                       rays, (long long)n_rays, ray_stride, mask);
-    T2N_HIP(hipGetLastError());
-    return T2N_OK;
+    return launch_filter_bbox(f->dev, rays, (long long)n_rays, ray_stride, mask, (hipStream_t)stream);
 }
 
 extern "C" int t2n_alpha_at(const t2n_field* f, const float* xyz_world, int64_t n, float* alpha, t2n_stream stream) {

@@ -976,7 +976,9 @@ class TensorBase(nn.Module):
         if not bbox_only and self.alphaMask is None:
             raise T2NError("filtering_rays(bbox_only=False) needs an alphaMask (updateAlphaMask() or a checkpoint's)")
         lib = _lib.load()
-        h = self.sync_params()
+        general = self._is_general()
+        h = None if general else self.sync_params()
+        d = self._general_desc() if general else None
         dev = self.basis_mat.weight.device
         tt = time.time()
         flat = all_rays.reshape(-1, all_rays.shape[-1])
@@ -985,7 +987,11 @@ class TensorBase(nn.Module):
             r = flat[idx].to(dev).contiguous().float()
             m = torch.empty(r.shape[0], dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                if bbox_only:
+                if general:
+                    _lib.check(lib.t2n_generic_filter_rays(C.byref(d), _lib.ptr(r), r.shape[0], r.shape[1], int(N_samples),
+                                                           1 if bbox_only else 0, _lib.ptr(m), _lib.current_stream_ptr(dev)),
+                               "t2n_generic_filter_rays")
+                elif bbox_only:
                     _lib.check(lib.t2n_filter_rays_bbox(h, _lib.ptr(r), r.shape[0], r.shape[1], _lib.ptr(m),
                                                         _lib.current_stream_ptr(dev)), "t2n_filter_rays_bbox")
                 else:
@@ -1032,15 +1038,23 @@ class TensorBase(nn.Module):
         (alpha [gx,gy,gz], dense_xyz [gx,gy,gz,3]). Node positions are generated inside the kernel from the same
         torch.linspace(0, 1, g) values the reference lerps with."""
         lib = _lib.load()
-        h = self.sync_params()
+        general = self._is_general()
+        h = None if general else self.sync_params()
         dev = self.basis_mat.weight.device
         g = [int(x) for x in (self.gridSize if gridSize is None else gridSize)]
         lins = [torch.linspace(0, 1, n).to(dev) for n in g]
         alpha = torch.empty(g, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(lib.t2n_dense_alpha(h, _lib.ptr(lins[0]), _lib.ptr(lins[1]), _lib.ptr(lins[2]), g[0], g[1], g[2],
-                                           float(self.stepSize), _lib.ptr(alpha), _lib.current_stream_ptr(dev)),
-                       "t2n_dense_alpha")
+            if general:      # wide fields: the density factors in their reference layouts, the mask from the descriptor
+                d = self._general_desc()
+                st = self._param_struct([p.detach() for p in self._real_params()])
+                _lib.check(lib.t2n_generic_dense_alpha(C.byref(d), C.byref(st), _lib.ptr(lins[0]), _lib.ptr(lins[1]), _lib.ptr(lins[2]),
+                                                       g[0], g[1], g[2], float(self.stepSize), _lib.ptr(alpha),
+                                                       _lib.current_stream_ptr(dev)), "t2n_generic_dense_alpha")
+            else:
+                _lib.check(lib.t2n_dense_alpha(h, _lib.ptr(lins[0]), _lib.ptr(lins[1]), _lib.ptr(lins[2]), g[0], g[1], g[2],
+                                               float(self.stepSize), _lib.ptr(alpha), _lib.current_stream_ptr(dev)),
+                           "t2n_dense_alpha")
         samples = torch.stack(torch.meshgrid(*lins, indexing="ij"), -1)
         dense_xyz = self.aabb[0] * (1 - samples) + self.aabb[1] * samples
         return alpha, dense_xyz
@@ -1108,14 +1122,17 @@ class TensorBase(nn.Module):
         if not is_train and not ndc_ray and fw and R % fw == 0:
             flags |= FLAG_COHERENT
         if self._is_general():
-            if ndc_ray or self.alphaMask is not None:
-                raise T2NError("the general-shape path has no NDC sampling and no AlphaGridMask")
             flags &= ~FLAG_COHERENT
             ps = self._real_params()
             if torch.is_grad_enabled() and any(p.requires_grad for p in ps):
-                return _GeneralFn.apply(self, rays, N, flags, jitter, *ps)
-            rgb, depth, z, w, _ = self._general_forward(rays, N, flags, jitter)
-            return (rgb, depth, z, w) if self.materialize_weights or is_train else (rgb, depth, None, None)
+                rgb, depth, z, w = _GeneralFn.apply(self, rays, N, flags, jitter, *ps)
+            else:
+                rgb, depth, z, w, _ = self._general_forward(rays, N, flags, jitter)
+                if not (self.materialize_weights or is_train):
+                    z = w = None
+            if ndc_ray and z is not None:
+                z = z[:1]      # sample_ray_ndc's ONE [1,N] depth row
+            return rgb, depth, z, w
         needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._autograd_params())
         if needs_grad and self._needs_embed():
             # every differentiable forward gets its own embedding graph: a second forward + backward at an unchanged parameter version
@@ -1261,6 +1278,16 @@ class TensorBase(nn.Module):
         d.density_shift, d.distance_scale = float(self.density_shift), float(self.distance_scale)
         d.weight_thres, d.step_size = float(self.rayMarch_weight_thres), float(self.stepSize)
         d.near, d.far, d.z_gate = float(self.near_far[0]), float(self.near_far[1]), float(self.z_gate)
+        mask = self.alphaMask
+        if mask is not None:
+            # the descriptor holds a raw pointer: the volume it points to stays referenced by the field until the next descriptor
+            vol = mask.alpha_volume.reshape(mask.alpha_volume.shape[-3:]).contiguous().float().to(self.basis_mat.weight.device)
+            self.__dict__["_general_mask_vol"] = vol
+            d.alpha_volume = vol.data_ptr()
+            am = mask.aabb.detach().float().cpu()
+            for k in range(3):
+                d.alpha_dims[k] = int(vol.shape[k])
+                d.alpha_aabb_min[k], d.alpha_aabb_max[k] = float(am[0, k]), float(am[1, k])
         return d
 
     def _general_forward(self, rays, N, flags, jitter):
