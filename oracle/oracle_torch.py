@@ -326,14 +326,21 @@ def sample_ray_ndc(cfg: FieldConfig, rays_o, rays_d, n_samples, jitter_row=None)
 
 
 def forward(cfg: FieldConfig, params, rays, white_bg=True, is_train=False, n_samples=-1, jitter=None,
-            bg_coin: Optional[bool] = None, return_aux=False, ndc=False):
+            bg_coin: Optional[bool] = None, return_aux=False, ndc=False, geom_dtype=None):
     """models/tensorBase.py:436-507 (ndc_ray=False, alphaMask=None — the driver's configuration).
 
     ``jitter``: [R,1] uniform draw used when is_train. ``bg_coin``: outcome of the reference's
-    ``torch.rand((1,)) < 0.5`` (only consulted when white_bg is False and is_train)."""
+    ``torch.rand((1,)) < 0.5`` (only consulted when white_bg is False and is_train).
+    ``geom_dtype``: the sample geometry (z values, points, normalised and grid coordinates, bilinear weights) in this dtype, as the
+    reference computes it in float32, while everything that depends on the parameters runs in theirs (float64 arithmetic on the
+    reference's own sample positions: a texel that many rays cross sums contributions that cancel, and there a 1e-5 change of a grid
+    coordinate — one float32 ulp near 150 — moves its gradient by far more than the arithmetic under test)."""
     n = n_samples if n_samples > 0 else cfg.n_samples
     if is_train and jitter is None:
         raise ValueError("train-mode oracle needs the captured jitter draw")
+    if geom_dtype is not None:
+        rays = rays.to(geom_dtype)
+        jitter = None if jitter is None else jitter.to(geom_dtype)
     ro, rd = rays[:, :3], rays[:, 3:6]
     if ndc:     # models/tensorBase.py:441-446 (`jitter` is then the [1,N] shared row)
         pts, z, valid = sample_ray_ndc(cfg, ro, rd, n, jitter if is_train else None)
@@ -350,8 +357,9 @@ def forward(cfg: FieldConfig, params, rays, white_bg=True, is_train=False, n_sam
         valid[valid.clone()] = keep
     if not is_train:
         valid = valid & (pts[:, :, -1] > cfg.z_gate)
-    sigma = torch.zeros(pts.shape[:-1], dtype=pts.dtype)
-    rgb = torch.zeros(pts.shape[:2] + (3,), dtype=pts.dtype)
+    fdt = pts.dtype if geom_dtype is None else next(iter(params.values())).dtype
+    sigma = torch.zeros(pts.shape[:-1], dtype=fdt)
+    rgb = torch.zeros(pts.shape[:2] + (3,), dtype=fdt)
     xn = normalize_coord(cfg, pts)
     if valid.any():
         s = feature2density(cfg, density_feature(params, xn[valid]))

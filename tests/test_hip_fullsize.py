@@ -22,27 +22,54 @@ pytestmark = pytest.mark.gpu
 AABB = [[-8.0] * 3, [8.0] * 3]
 
 
-def oracle_driver_loss_and_grads(cfg, params, rays, jitter, rgb_t, dep_t, n_samples, chunk=2048, dtype=torch.float32):
+def oracle_driver_loss_and_grads(cfg, params, rays, jitter, rgb_t, dep_t, n_samples, chunk=2048, dtype=torch.float32, tv=None,
+                                 geom_f32=False):
     """The driver's loss and its gradient w.r.t. every parameter through oracle_torch's autograd, accumulated over ray chunks (the
     loss is a sum of per-ray terms over the batch size R): mse = sum (rgb - t)^2 / 3R, depth = sum (d - t)^2 / R,
-    transmittance = sum_r (mean_n w m)^2 / R with m = z - depth_t + 0.1 < 0 (utils.py:67-80)."""
+    transmittance = sum_r (mean_n w m)^2 / R with m = z - depth_t + 0.1 < 0 (utils.py:67-80).
+    `tv`: optional [("density_plane", w_d), ("app_plane", w_a)]: the gradient also holds sum_planes tv_loss(plane) * 1e-2 * w of each
+    term (TV_loss_density / TV_loss_app, models/tensoRF.py:193-203); the returned parts stay the three data terms.
+    `geom_f32`: the sample geometry and the transmittance mask in float32, as the reference computes them (oracle_torch.forward's
+    geom_dtype), everything that depends on the parameters in `dtype`."""
     from oracle import oracle_torch as O
     P = O.params_from_numpy(params, requires_grad=True, dtype=dtype)
-    rays, jitter, rgb_t, dep_t = rays.to(dtype), jitter.to(dtype), rgb_t.to(dtype), dep_t.to(dtype)
+    gdt = torch.float32 if geom_f32 else dtype
+    rays, jitter, rgb_t, dep_t = rays.to(gdt), jitter.to(gdt), rgb_t.to(dtype), dep_t.to(dtype)
+    dep_m = dep_t.to(gdt)
     R = rays.shape[0]
     parts = np.zeros(3)
     for lo in range(0, R, chunk):
         sl = slice(lo, min(lo + chunk, R))
-        rgb, depth, z, w = O.forward(cfg, P, rays[sl], white_bg=True, is_train=True, n_samples=n_samples, jitter=jitter[sl])
+        rgb, depth, z, w = O.forward(cfg, P, rays[sl], white_bg=True, is_train=True, n_samples=n_samples, jitter=jitter[sl],
+                                     geom_dtype=gdt if geom_f32 else None)
         depth = torch.where(torch.isnan(depth), torch.zeros_like(depth), depth)
         mse = ((rgb - rgb_t[sl]) ** 2).sum() / (3 * R)
         dl = ((depth - dep_t[sl]) ** 2).sum() / R
-        m = ((z - dep_t[sl][:, None] + 0.1) < 0).to(dtype)
+        m = ((z - dep_m[sl][:, None] + 0.1) < 0).to(dtype)
         tl = (torch.mean(w * m, dim=1) ** 2).sum() / R
         (mse + 0.005 * dl + 1e3 * tl).backward()
         parts += np.array([float(mse.detach()), float(dl.detach()), float(tl.detach())])
+    if tv:
+        sum(O.tv_loss(P[k]) * 1e-2 * float(w) for prefix, w in tv for k in P if k.startswith(prefix + ".")).backward()
     grads = {k: (v.grad.numpy().astype(np.float64) if v.grad is not None else np.zeros(tuple(v.shape), np.float64)) for k, v in P.items()}
     return parts, grads
+
+
+def c3_batch(R=16384):
+    """SURVEY.md 8(d) C3 batch: the 300^3 S1-soft field (AABB +-8, near / far 0.5 / 8, N = 259) and R rays drawn with
+    np.random.seed(1024) from the 9 x 512^2 support rays of the reference's local_fixed poses, targets rgb ~ U[0,1], depth ~ U[2,7].
+    Returns (params, cfg, rays, rgb_t, dep_t) on the host."""
+    from oracle import oracle_torch as O
+    params = synth.make_field_params(0, [300] * 3, scene="S1-soft", aabb=AABB)
+    poses = np.load(os.path.join(GOLDEN, "poses.npz"))["local_fixed"].astype(np.float32)
+    allr = np.concatenate([synth.frame_rays_np(512, 512, c2w=p) for p in poses])
+    np.random.seed(1024)
+    idx = np.random.permutation(allr.shape[0])[:R]
+    rays = torch.from_numpy(allr[idx])
+    g = np.random.Generator(np.random.PCG64(1024))
+    rgb_t = torch.from_numpy(g.uniform(0, 1, (R, 3)).astype(np.float32))
+    dep_t = torch.from_numpy(g.uniform(2, 7, (R,)).astype(np.float32))
+    return params, O.FieldConfig(aabb=AABB, grid_size=[300] * 3), rays, rgb_t, dep_t
 
 
 def hip_driver_loss(rgb, depth, z, w, rgb_t, dep_t):
@@ -57,17 +84,8 @@ def test_c3_full_batch_gradients_vs_oracle():
     """SURVEY.md 8(d) C3 batch: 16 384 rays drawn with np.random.seed(1024) from the 9 x 512^2 support rays of the reference's
     local_fixed poses, N = 259, is_train with the jitter of torch.manual_seed(1024), targets rgb ~ U[0,1], depth ~ U[2,7]. At this
     size the tile-binned f64 scatter, the forked side stream and the 8192-record segmenting all carry real load."""
-    from oracle import oracle_torch as O
-    params = synth.make_field_params(0, [300] * 3, scene="S1-soft", aabb=AABB)
+    params, cfg, rays, rgb_t, dep_t = c3_batch()
     f = make_field(params, [300] * 3, AABB, [0.5, 8.0])
-    poses = np.load(os.path.join(GOLDEN, "poses.npz"))["local_fixed"].astype(np.float32)
-    allr = np.concatenate([synth.frame_rays_np(512, 512, c2w=p) for p in poses])
-    np.random.seed(1024)
-    idx = np.random.permutation(allr.shape[0])[:16384]
-    rays = torch.from_numpy(allr[idx])
-    g = np.random.Generator(np.random.PCG64(1024))
-    rgb_t = torch.from_numpy(g.uniform(0, 1, (16384, 3)).astype(np.float32))
-    dep_t = torch.from_numpy(g.uniform(2, 7, (16384,)).astype(np.float32))
     torch.manual_seed(1024)
     jitter = torch.rand(16384, 1)
     torch.manual_seed(1024)                     # the HIP forward draws the same vector from the CPU generator
@@ -75,7 +93,6 @@ def test_c3_full_batch_gradients_vs_oracle():
     out = f(rays, is_train=True, white_bg=True, N_samples=259)
     mse, dl, tl, tot = hip_driver_loss(out[0], out[1], out[2], out[3], rgb_t.to(d), dep_t.to(d))
     tot.backward()
-    cfg = O.FieldConfig(aabb=AABB, grid_size=[300] * 3)
     parts, ref = oracle_driver_loss_and_grads(cfg, params, rays, jitter, rgb_t, dep_t, 259)
     got = np.array([float(mse), float(dl), float(tl)])
     np.testing.assert_allclose(got, parts, rtol=2e-5, atol=1e-9)

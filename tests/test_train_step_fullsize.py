@@ -1,0 +1,279 @@
+"""The one-call fused train step (t2n_train_step, what bench.py's training figure times) against the float64 oracle at the full C3 batch:
+16 384 rays x 259 samples of the 300^3 S1-soft field, the driver's loss plus both TV terms. At this size the step takes routes no smaller
+test reaches: density bins counted late (k_bwd_march COUNT form, more than 4 096 rays), the pipelined form from the second step on (the
+early part on the side stream, alternating workspace halves), full appearance / density segments, the composed step's TV seed on a
+side stream (8 192 rays and more) and a withheld step replayed at full size.
+
+The fused step leaves no gradient behind (its Adam consumes it): the gradient is read back from Adam's first moments in float64
+(tests/helpers/adam_readout.py). Gradient bounds per tensor are those test_c3_full_batch_gradients_vs_oracle holds the autograd form to."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests.helpers import adam_readout as A
+from tests.test_hip_fullsize import AABB, c3_batch, oracle_driver_loss_and_grads
+from tests.test_hip_parity import _grad_check, make_field
+
+pytestmark = pytest.mark.gpu
+R_C3, N = 16384, 259
+TV = (("density_plane", 0.1), ("app_plane", 0.01))
+SEEDS = (1024, 1025, 1026)          # torch.manual_seed in front of step t: the jitter draw of that step (step 1: the C3 test's)
+OMB1, OMB2 = A.one_minus(0.9), A.one_minus(0.99)
+
+
+@pytest.fixture(scope="module")
+def c3():
+    return c3_batch(R_C3)
+
+
+def _jitter(seed, R):
+    torch.manual_seed(seed)
+    return torch.rand(R, 1)         # what train_step draws first (white_bg=True: no background coin in front of it)
+
+
+def _oracle(c3, params, seed, R=R_C3):
+    """float64 oracle: the four loss values (mse, depth, transmittance, total) and the gradient of the data loss + TV terms."""
+    _, cfg, rays, rgb_t, dep_t = c3
+    parts, grads = oracle_driver_loss_and_grads(cfg, params, rays[:R], _jitter(seed, R), rgb_t[:R], dep_t[:R], N, chunk=2048,
+                                                dtype=torch.float64, tv=TV, geom_f32=True)
+    return np.array([parts[0], parts[1], parts[2], parts[0] + 0.005 * parts[1] + 1e3 * parts[2]]), grads
+
+
+@pytest.fixture(scope="module")
+def oracle0(c3):
+    """The oracle at the initial parameters with the jitter of SEEDS[0]: every test's first step starts there."""
+    return _oracle(c3, c3[0], SEEDS[0])
+
+
+def _field(c3):
+    from text2nerf_amd.optim import TVAdam
+    f = make_field(c3[0], [300] * 3, AABB, [0.5, 8.0])
+    return f, TVAdam(f.get_optparam_groups(0.02, 1e-3), betas=(0.9, 0.99), field=f)
+
+
+def _step(f, opt, c3, seed, R=R_C3, **kw):
+    _, _, rays, rgb_t, dep_t = c3
+    torch.manual_seed(seed)
+    return f.train_step(rays[:R], rgb_t[:R], dep_t[:R], opt, N_samples=N, white_bg=True,
+                        tv=[(getattr(f, name), w) for name, w in TV], **kw)
+
+
+def _presized_fused_step(f, opt, c3, seed, R=R_C3):
+    """The field's FusedStep made up front (as train_step would) with a row capacity that holds the batch: its appearance samples counted
+    by a train-mode render of the same rays and jitter. (The first-step guess, 12 rows per ray, is below a C3 batch's need.)"""
+    from text2nerf_amd.trainer import FusedStep, _ladder
+    torch.manual_seed(seed)
+    with torch.no_grad():
+        f(c3[2][:R], is_train=True, white_bg=True, N_samples=N)
+    need = int(f.stats()["appearance"])
+    fs = f.__dict__["_fused_step"] = FusedStep(f, opt)
+    fs.rows_cap = _ladder(int(need * 1.25) + 4096)
+    return fs
+
+
+def _check_losses(tag, got, want):
+    print(f"{tag}: losses {np.array2string(np.asarray(got), precision=7)} oracle {np.array2string(want, precision=7)}")
+    np.testing.assert_allclose(got, want, rtol=2e-5, atol=1e-9)
+
+
+def _check_grads(tag, got, ref):
+    """test_c3_full_batch_gradients_vs_oracle's bounds; all three metrics printed per tensor, pass or fail."""
+    try:
+        worst = _grad_check(got, ref, rel=1e-3, rel_l2=1e-4, cos_gap=1e-8)
+        assert max(v for k, v in worst.items() if k.startswith("density")) <= 1e-4, worst
+    finally:
+        last = _grad_check.last
+        print(f"{tag}: gradient vs float64 oracle (max |dg| / max |g|, relative L2, 1 - cosine)")
+        for k in last["max_rel"]:
+            print(f"   {k:28s} {last['max_rel'][k]:.1e}  {last['rel_l2'][k]:.1e}  {last['one_minus_cos'][k]:.1e}")
+
+
+def _autograd_form(c3, params, seed):
+    """The autograd form's gradient (forward, the driver's loss in torch, backward: what test_c3_full_batch_gradients_vs_oracle holds to
+    the oracle) at `params` with the jitter of `seed`, plus the float64 TV gradient: what the fused step must reproduce."""
+    from oracle import oracle_torch as O
+    from tests.test_hip_fullsize import hip_driver_loss
+    _, _, rays, rgb_t, dep_t = c3
+    f = make_field(params, [300] * 3, AABB, [0.5, 8.0])
+    torch.manual_seed(seed)
+    d = f.basis_mat.weight.device
+    out = f(rays, is_train=True, white_bg=True, N_samples=N)
+    hip_driver_loss(out[0], out[1], out[2], out[3], rgb_t.to(d), dep_t.to(d))[3].backward()
+    P = O.params_from_numpy({k: v for k, v in params.items() if "plane" in k}, dtype=torch.float64, requires_grad=True)
+    sum(O.tv_loss(P[k]) * 1e-2 * w for prefix, w in TV for k in P if k.startswith(prefix + ".")).backward()
+    return {k: p.grad.detach().cpu().numpy().astype(np.float64) + (P[k].grad.numpy() if k in P else 0.0) for k, p in f.named_parameters()}
+
+
+def _check_adam(f, opt, prev, cur, g, t):
+    """Adam's arithmetic of step t: every parameter == its float64 recomputation from p_{t-1}, the kernel's own m_t / v_t, the group's
+    learning rate and bias corrections of step t (within float32 rounding); v_t == beta2 v_{t-1} + (1 - beta2) g^2."""
+    b1, b2 = A.F32_BETAS
+    name = {id(p): k for k, p in f.named_parameters()}
+    lr = {name[id(p)]: float(grp["lr"]) for grp in opt.param_groups for p in grp["params"]}
+    eps = float(opt.param_groups[0]["eps"])
+    for k in cur["p"]:
+        want = A.adam_param(prev["p"][k], cur["m"][k], cur["v"][k], lr[k], t, b1, b2, eps)
+        tol = A.param_tolerance(cur["p"][k], want - prev["p"][k])
+        d = np.abs(cur["p"][k] - want)
+        assert np.all(d <= tol), (t, k, "parameter off its Adam update", float((d / tol).max()))
+        v = A.adam_second_moment(prev["v"][k], g[k], b2, OMB2)
+        dv = np.abs(v - cur["v"][k])
+        assert np.all(dv <= 1e-6 * np.abs(cur["v"][k]) + 1e-30), (t, k, "second moment", float(dv.max()))
+
+
+def _recovered(prev, cur):
+    return {k: A.recover_grad(prev["m"][k], cur["m"][k], OMB1) for k in cur["m"]}
+
+
+def _check_master_copies(f, cur):
+    """The channel-last master copies the kernels read == the reference-layout parameters the oracle reads, bit for bit."""
+    for k, v in A.master_copies(f).items():
+        assert np.array_equal(v, cur["p"][k].astype(np.float32)), k
+
+
+def test_fused_trajectory_three_steps_vs_oracle(c3, oracle0):
+    """Three single-call steps on host batches: step 1 serial, steps 2 and 3 pipelined on alternating workspace halves, density bins
+    counted late. At every step: the loss values and the gradient of all 19 tensors (from the moments) against the float64 oracle at
+    the parameters the step started from, Adam's arithmetic, the master copies, the step counts on the host and the device."""
+    assert "T2N_DEN_EARLY" not in os.environ and "T2N_COPY_KERNEL" not in os.environ     # (the routes this test claims to take)
+    f, opt = _field(c3)
+    prev = A.snapshot(f, opt)
+    for t, seed in enumerate(SEEDS, 1):
+        _step(f, opt, c3, seed, fused=True, graph=False)
+        fs = f._fused_step
+        fs.sync()
+        losses = fs.losses.cpu().numpy().astype(np.float64)
+        cur = A.snapshot(f, opt)
+        rec = A.train_record(f)
+        want, ref = oracle0 if t == 1 else _oracle(c3, {k: v.astype(np.float32) for k, v in prev["p"].items()}, seed)
+        print(f"step {t}: replays {fs.replays}, pipelined launches {fs.pipelined_launches}, row needs {fs.needs}, capacity {fs.rows_cap}")
+        _check_losses(f"fused step {t}", losses, want)
+        g = _recovered(prev, cur)
+        _check_adam(f, opt, prev, cur, g, t)
+        _check_master_copies(f, cur)
+        assert all(s == t for s in cur["step"].values()), cur["step"]
+        assert rec[1] == t and rec[2] == fs.replays, rec[:3]
+        if t == 1:
+            _check_grads(f"fused step {t}", g, ref)
+        else:
+            # past step 1 the appearance gradients of the autograd form itself miss the oracle bounds on this field (relative L2 ~2.5e-4 at
+            # step 2): the fused step is held to the autograd form's gradient at the same parameters and jitter, and both are printed
+            # against the oracle
+            auto = _autograd_form(c3, {k: v.astype(np.float32) for k, v in prev["p"].items()}, seed)
+            try:
+                _check_grads(f"autograd form, step {t}", auto, ref)
+            except AssertionError as e:
+                print(f"   (autograd form vs oracle, not asserted: {str(e).splitlines()[0][:160]})")
+            try:
+                _check_grads(f"fused step {t}", g, ref)
+            except AssertionError as e:
+                print(f"   (fused step vs oracle, not asserted: {str(e).splitlines()[0][:160]})")
+            _check_grads(f"fused step {t} vs autograd form", g, auto)
+        prev = cur
+    assert fs.pipelined_launches >= 2, fs.pipelined_launches
+
+
+def test_two_phase_step_gradient_vs_oracle(c3, oracle0):
+    """Phase 1 | identity all-reduce | phase 2 at step 1: the gradient read directly inside the callable (factor gradient buffer +
+    head .grad) against the oracle, and against the moment readout after phase 2 (float32 rounding: validates the readout on the
+    device). Nobody voted to withhold."""
+    f, opt = _field(c3)
+    fs = _presized_fused_step(f, opt, c3, SEEDS[0])
+    seen = {}
+
+    def all_reduce():
+        g = A.factor_grads_ref(f)
+        for k, p in A.kernel_named(f)[12:]:
+            g[k] = p.grad.detach().cpu().numpy().astype(np.float64)
+        seen["g"], seen["vote"] = g, float(fs.head_grads[-1])
+
+    prev = A.snapshot(f, opt)
+    _step(f, opt, c3, SEEDS[0], fused=True, all_reduce=all_reduce)
+    fs.sync()
+    assert seen and seen["vote"] == 0.0 and fs.replays == 0
+    cur = A.snapshot(f, opt)
+    want, ref = oracle0
+    _check_losses("two-phase step", fs.losses.cpu().numpy().astype(np.float64), want)
+    g = _recovered(prev, cur)
+    for k, direct in seen["g"].items():
+        assert np.all(np.abs(g[k] - direct) <= 2.5e-7 * np.abs(direct) + 1e-30), (k, float(np.abs(g[k] - direct).max()))
+    _check_adam(f, opt, prev, cur, g, 1)
+    assert all(s == 1 for s in cur["step"].values())
+    _check_grads("two-phase step, direct", seen["g"], ref)
+
+
+def test_composed_step_vs_oracle(c3, oracle0):
+    """The composed step (render, loss kernel, backward, TVAdam as separate calls) at 16 384 rays: the TV gradient is seeded into the
+    gradient buffer on a side stream in front of the backward (R >= _SEED_MIN_RAYS). Moment readout against the oracle."""
+    from text2nerf_amd import tensorf as tf
+    assert R_C3 >= tf._SEED_MIN_RAYS
+    f, opt = _field(c3)
+    prev = A.snapshot(f, opt)
+    losses = _step(f, opt, c3, SEEDS[0], fused=False).cpu().numpy().astype(np.float64)
+    torch.cuda.synchronize()
+    assert f.__dict__.get("_fused_step") is None and f.__dict__.get("_seed_stream") is not None     # (the seeded route)
+    cur = A.snapshot(f, opt)
+    want, ref = oracle0
+    _check_losses("composed step", losses, want)
+    g = _recovered(prev, cur)
+    _check_adam(f, opt, prev, cur, g, 1)
+    _check_grads("composed step", g, ref)
+    assert all(s == 1 for s in cur["step"].values())
+
+
+def test_withheld_first_step_replayed_at_full_size(c3, oracle0):
+    """A first step submitted with a capacity far below its rows applies nothing — parameters, moments, master copies bitwise unchanged,
+    the device records 0 applied and 1 withheld — and sync() replays it at full size (the workspace regrown first): then step 1 has been
+    applied and its gradient is the oracle's at the initial parameters."""
+    from text2nerf_amd.trainer import FusedStep
+    f, opt = _field(c3)
+    f.sync_params()
+    fs = f.__dict__["_fused_step"] = FusedStep(f, opt)
+    fs.cap_once = 256
+    prev = A.snapshot(f, opt)
+    mc0 = A.master_copies(f)
+    _step(f, opt, c3, SEEDS[0], fused=True, graph=False)
+    torch.cuda.synchronize()
+    rec = A.train_record(f)
+    assert (rec[1], rec[2]) == (0, 1), rec[:3]
+    assert fs.seen == 0 and fs.replays == 0            # (no poll yet)
+    mid = A.snapshot(f, opt)
+    for key in ("p", "m", "v"):
+        for k in prev[key]:
+            assert np.array_equal(mid[key][k], prev[key][k]), (key, k)
+    for k, v in A.master_copies(f).items():
+        assert np.array_equal(v, mc0[k]), k
+    ws0 = fs.ws.numel()
+    fs.sync()
+    assert fs.replays == 1 and fs.ws.numel() > ws0
+    rec = A.train_record(f)
+    assert (rec[1], rec[2]) == (1, 1), rec[:3]
+    cur = A.snapshot(f, opt)
+    assert all(s == 1 for s in cur["step"].values())
+    want, ref = oracle0
+    _check_losses("replayed step", fs.losses.cpu().numpy().astype(np.float64), want)
+    g = _recovered(prev, cur)
+    _check_adam(f, opt, prev, cur, g, 1)
+    _check_master_copies(f, cur)
+    _check_grads("replayed step", g, ref)
+
+
+@pytest.mark.parametrize("R", [4096, 4097])
+def test_fused_step_at_the_den_early_boundary(c3, R, seed=2024):
+    """t2n_train_step counts the density bins early up to 4 096 rays and late above: one fused step on the first 4 096 rays of the C3
+    batch and one on the first 4 097 (one ray in the last group of four), each against its own float64 oracle."""
+    assert "T2N_DEN_EARLY" not in os.environ
+    f, opt = _field(c3)
+    fs = _presized_fused_step(f, opt, c3, seed, R)
+    prev = A.snapshot(f, opt)
+    _step(f, opt, c3, seed, R=R, fused=True, graph=False)
+    fs.sync()
+    assert fs.replays == 0
+    cur = A.snapshot(f, opt)
+    want, ref = _oracle(c3, c3[0], seed, R)
+    _check_losses(f"fused step, {R} rays", fs.losses.cpu().numpy().astype(np.float64), want)
+    g = _recovered(prev, cur)
+    _check_adam(f, opt, prev, cur, g, 1)
+    _check_grads(f"fused step, {R} rays", g, ref)
