@@ -347,6 +347,43 @@ int t2n_dibr_filter_mask2(float* image, int32_t* known, double* depth, int H, in
  * place and in raster order (fronts t = col + 2 row). image [H,W,3] fp32, known [H,W] int32. */
 int t2n_dibr_filter_mask(float* image, int32_t* known, int H, int W, t2n_stream stream);
 
+/* ---- the support-set builder: from one inpainted RGB-D view to training rays (text2nerf_main.py:380-392,
+ * dataLoader/scene_gen.py:305-316), csrc/t2n_support.hip.
+ * t2n_warp_views = the bilinear_splat branch of gt_warping (utils.py:122-163): ONE source view forward-warped
+ * (Warper.forward_warp, scripts/Warper.py:21-180, fp64) to V target poses, every target an independent output, then the
+ * white background and / 255. Device inputs: rgb [H,W,3] fp32 in [0,1] (truncated to uint8 levels like the reference),
+ * depth [H,W] fp32, mask1 [H,W] u8 or NULL (the reference's mask_gt, 0 / non-zero: scales every weight), mask_aux [H,W] u8 or
+ * NULL (extra output only: aux_out = the mask a second call with mask1 = mask_aux would return, from the same geometry pass).
+ * Host inputs (row-major doubles): Ki9 = inv(K), T12 [V][12] = first three rows of inv(pose_tar[v]) inv(inv(pose_gt)), K9 = K.
+ * Device outputs: image_out [V,H,W,3] fp32; mask_out [V,H,W] int64 or NULL; depth_out [V,H,W] fp64 or NULL (0 where nothing
+ * landed); depth32_out [V,H,W] fp32 or NULL (depth_out rounded, what produce_formatted_data makes of it); aux_out [V,H,W]
+ * int64 or NULL (needs mask_aux). Masks are exact; image and depth sum fp64 atomics in an order that varies between runs (image
+ * within one uint8 level of numpy's add.at on round-half ties, depth ~1e-15 relative). Views are processed 8 per launch set
+ * (three kernels + one memset); workspace: t2n_warp_views_workspace_bytes(H, W, V) bytes of device memory (0 = bad argument).
+ * T2N_ERR_INVALID: NULL / non-positive argument, aux_out without mask_aux; T2N_ERR_WORKSPACE: workspace too small. */
+size_t t2n_warp_views_workspace_bytes(int H, int W, int V);
+int t2n_warp_views(const float* rgb, const float* depth, const uint8_t* mask1, const uint8_t* mask_aux, int H, int W, int V,
+                   const double* Ki9_host, const double* T12_host, const double* K9_host, float* image_out, int64_t* mask_out,
+                   double* depth_out, float* depth32_out, int64_t* aux_out, void* workspace, size_t workspace_bytes,
+                   t2n_stream stream);
+
+/* t2n_format_views = produce_formatted_data (dataLoader/scene_gen.py:31-98): rays of N poses (the arithmetic of
+ * t2n_generate_rays: rays_split[i] is bit-equal to it) and the rows whose mask is > 0.5, in the reference's order (view-major,
+ * raster order inside a view). Device inputs: images [N,H,W,3] fp32, depths [N,H,W] fp32, masks [N,H,W] of dtype mask_dtype
+ * (T2N_MASK_*); masks == NULL is mode 'test': only rays_split is written and images / depths / row buffers / record / workspace
+ * may be NULL. Host input: c2w_host [N][12] = first three rows of each camera-to-world matrix (fp32). Device outputs: rays_split
+ * [N,H*W,6] or NULL; all_rays [K,6], all_rgbs [K,3], all_depths [K] in buffers of capacity_rows >= N*H*W rows; record [1+N]
+ * int64 = {K, kept rows of view 0, ..., of view N-1} (K is data dependent: the caller reads the record once to slice).
+ * Deterministic (count, one-workgroup exclusive scan, scatter; no atomics). Workspace: t2n_format_views_workspace_bytes(H, W, N).
+ * T2N_ERR_INVALID: NULL / non-positive argument, unknown mask dtype, capacity_rows < N*H*W; T2N_ERR_WORKSPACE: workspace too
+ * small. */
+enum { T2N_MASK_U8 = 0, T2N_MASK_I32 = 1, T2N_MASK_I64 = 2, T2N_MASK_F32 = 3, T2N_MASK_F64 = 4 };
+size_t t2n_format_views_workspace_bytes(int H, int W, int N);
+int t2n_format_views(const float* images, const float* depths, const void* masks, int mask_dtype, int N, int H, int W,
+                     const float* c2w_host, float fx, float fy, float cx, float cy, float* rays_split, float* all_rays,
+                     float* all_rgbs, float* all_depths, int64_t capacity_rows, int64_t* record, void* workspace,
+                     size_t workspace_bytes, t2n_stream stream);
+
 /* ---- a-15: backward of the render call w.r.t. all field parameters (what autograd derives in the reference,
  * text2nerf_main.py:589; coordinates are detached there, models/tensoRF.py:208-210,226-228, so no ray gradients exist).
  * Protocol: (1) forward with T2N_FLAG_KEEP_CTX as ONE launch (workspace >= t2n_render_workspace_bytes_ctx), weights and

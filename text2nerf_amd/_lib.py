@@ -20,6 +20,7 @@ FLAG_DEVICE_ROWS = 32
 FLAG_PIPELINE = 64
 SHADE_IDS = {"MLP_Fea_noview": 0, "SH": 1, "RGB": 2, "MLP_Fea": 3, "MLP_PE": 4, "MLP": 5}   # MLP_PE: rejected in tensorf.py (broken upstream)
 ACT_IDS = {"softplus": 0, "relu": 1}
+MASK_U8, MASK_I32, MASK_I64, MASK_F32, MASK_F64 = 0, 1, 2, 3, 4   # T2N_MASK_*: dtypes t2n_format_views reads a mask in
 
 
 class T2NError(RuntimeError):
@@ -133,6 +134,14 @@ SIGNATURES = {
     "t2n_warp_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                 C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "t2n_warp_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2n_warp_views_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "t2n_warp_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_format_views_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "t2n_format_views": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "t2n_adam_step_multi": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                             C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "t2n_ray_marcher": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p,

@@ -184,15 +184,7 @@ __global__ __launch_bounds__(256) void k_ray_dirs(int H, int W, float fx, float 
     dirs[t * 3] = dx; dirs[t * 3 + 1] = dy; dirs[t * 3 + 2] = dz;
 }
 
-struct Pose { float m[12]; };
-
-__device__ __forceinline__ void rotate(const Pose& P, float dx, float dy, float dz, float& rx, float& ry, float& rz) {
-    // rays_d = directions @ c2w[:3,:3].T  (dataLoader/ray_utils.py:79)
-    rx = fmaf(dz, P.m[2], fmaf(dy, P.m[1], dx * P.m[0]));
-    ry = fmaf(dz, P.m[6], fmaf(dy, P.m[5], dx * P.m[4]));
-    rz = fmaf(dz, P.m[10], fmaf(dy, P.m[9], dx * P.m[8]));
-}
-
+// Pose / rotate / pixel_ray: t2n_device.h (shared with the support-set formatter, csrc/t2n_support.hip)
 __global__ __launch_bounds__(256) void k_get_rays(const float* __restrict__ dirs, long long n, const Pose P, float* ro, float* rd, float* r6) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
@@ -207,12 +199,8 @@ __global__ __launch_bounds__(256) void k_generate_rays(int H, int W, float fx, f
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)H * W) return;
     const int y = (int)(t / W), x = (int)(t - (long long)y * W);
-    const float i = (float)x + 0.5f, j = (float)y + 0.5f;
-    float dx = (i - cx) / fx, dy = (j - cy) / fy, dz = 1.f;
-    const float n = sqrtf((dx * dx + dy * dy) + dz * dz);
-    dx = dx / n; dy = dy / n; dz = dz / n;
     float rx, ry, rz;
-    rotate(P, dx, dy, dz, rx, ry, rz);
+    pixel_ray(P.m, x, y, fx, fy, cx, cy, rx, ry, rz);
     r6[t * 6] = P.m[3]; r6[t * 6 + 1] = P.m[7]; r6[t * 6 + 2] = P.m[11]; r6[t * 6 + 3] = rx; r6[t * 6 + 4] = ry; r6[t * 6 + 5] = rz;
 }
 

@@ -7,6 +7,28 @@
 
 namespace t2n {
 
+// ---- ray generation (t2n_generate_rays, t2n_format_views) ---------------------------------------------------------------
+struct Pose { float m[12]; };   // first three rows of a camera-to-world matrix
+
+// rays_d = directions @ c2w[:3,:3].T  (dataLoader/ray_utils.py:79); m = 3x4 row-major
+__device__ __forceinline__ void rotate(const float* m, float dx, float dy, float dz, float& rx, float& ry, float& rz) {
+    rx = fmaf(dz, m[2], fmaf(dy, m[1], dx * m[0]));
+    ry = fmaf(dz, m[6], fmaf(dy, m[5], dx * m[4]));
+    rz = fmaf(dz, m[10], fmaf(dy, m[9], dx * m[8]));
+}
+__device__ __forceinline__ void rotate(const Pose& P, float dx, float dy, float dz, float& rx, float& ry, float& rz) {
+    rotate(P.m, dx, dy, dz, rx, ry, rz);
+}
+// scene_gen.py:44-45,72: the normalised pixel-centre direction of pixel (x, y), rotated into the world
+__device__ __forceinline__ void pixel_ray(const float* m, int x, int y, float fx, float fy, float cx, float cy, float& rx, float& ry,
+                                          float& rz) {
+    const float i = (float)x + 0.5f, j = (float)y + 0.5f;
+    float dx = (i - cx) / fx, dy = (j - cy) / fy, dz = 1.f;
+    const float n = sqrtf((dx * dx + dy * dy) + dz * dz);
+    dx = dx / n; dy = dy / n; dz = dz / n;
+    rotate(m, dx, dy, dz, rx, ry, rz);
+}
+
 __device__ __forceinline__ float dpp_quad_xor1(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));  // quad_perm [1,0,3,2]
 }

@@ -6,10 +6,17 @@
 * ``dibr_filter_mask2`` — utils.py:393-409, the raster-order hole filling (skewed wavefronts on the GPU); ``dibr_filter_mask`` —
   utils.py:345-392, its four-stage sibling (unused by the driver)
 
+and the steps after inpainting that turn one inpainted RGB-D view into training rays (csrc/t2n_support.hip):
+
+* ``gt_warping`` — utils.py:122-163 (the bilinear_splat branch every call site takes): one source view to many target poses
+* ``produce_formatted_data`` — dataLoader/scene_gen.py:31-98: rays per pose and the ``mask > 0.5`` row selection
+* ``build_support_set`` — text2nerf_main.py:380-392 / scene_gen.py:305-316 as one device-resident call
+
 Inputs may be numpy arrays (as in the driver) or torch tensors; numpy in -> numpy out. No CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -155,3 +162,228 @@ def align_depth_global(depth_rendered, depth_est, pixel_sample, push_depth=2.0, 
                                               _lib.ptr(out), _lib.ptr(ss), _lib.current_stream_ptr(dev)), "t2n_depth_align_global")
     s = ss.cpu().tolist()
     return s[0], s[1], out
+
+
+# ---- after inpainting: one RGB-D view -> support views -> training rays -------------------------------------------------------------
+def _host(x):
+    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x)
+
+
+def _is01(m):
+    m = np.asarray(m)
+    return m.dtype == np.bool_ or bool(np.isin(m, (0, 1)).all())
+
+
+def _mask_u8(m, dev):
+    """A 0/1 (or boolean) mask as device uint8."""
+    if m is None:
+        return None
+    if isinstance(m, np.ndarray):
+        m = np.ascontiguousarray(m != 0).view(np.uint8)
+    return _to(m, dev, torch.uint8)
+
+
+def _warp_mats(pose_gt, poses_tar, intrinsic):
+    """The host matrices of gt_warping (utils.py:138-147) and Warper.compute_transformed_points (Warper.py:75,84), in numpy and the
+    inputs' dtype like the reference: inv(K), the first three rows of inv(pose_tar[v]) @ inv(inv(pose_gt)) per target, K."""
+    pose_gt, poses_tar = _host(pose_gt), _host(poses_tar)
+    T1 = np.linalg.inv(pose_gt)
+    K = np.eye(3).astype(np.float32)
+    K[0, 0], K[1, 1], K[0, 2], K[1, 2] = intrinsic[0], intrinsic[1], intrinsic[2], intrinsic[3]
+    T = [np.matmul(np.linalg.inv(poses_tar[v]), np.linalg.inv(T1)) for v in range(poses_tar.shape[0])]
+    T12 = np.stack([np.asarray(t, np.float64)[:3, :4] for t in T]).reshape(-1)
+    d9 = lambda m: (C.c_double * 9)(*np.asarray(m, np.float64).reshape(-1)[:9])       # noqa: E731
+    return d9(np.linalg.inv(K)), (C.c_double * T12.size)(*T12), d9(K), len(T)
+
+
+def _warp_views(lib, dev, rgb, depth, m1, maux, H, W, mats, image, mask, depth64, depth32, aux):
+    """t2n_warp_views on the current stream of `dev`; outputs are caller tensors (or None)."""
+    Ki, T12, K, V = mats
+    if rgb.shape != (H, W, 3) or depth.shape != (H, W):
+        raise T2NError(f"gt_warping: rgb_gt {tuple(rgb.shape)} / depth_gt {tuple(depth.shape)} do not match (H, W) = {(H, W)}")
+    for m in (m1, maux):
+        if m is not None and m.shape != (H, W):
+            raise T2NError(f"gt_warping: mask shape {tuple(m.shape)} does not match (H, W) = {(H, W)}")
+    ws = torch.empty(int(lib.t2n_warp_views_workspace_bytes(H, W, V)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_warp_views(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(m1), _lib.ptr(maux), H, W, V, Ki, T12, K, _lib.ptr(image),
+                                      _lib.ptr(mask), _lib.ptr(depth64), _lib.ptr(depth32), _lib.ptr(aux), _lib.ptr(ws), ws.numel(),
+                                      _lib.current_stream_ptr(dev)), "t2n_warp_views")
+
+
+def _png8(a):
+    """What imageio makes of a float array written as PNG (its lossy range conversion: min..max -> 0..255), so that the depth previews
+    do not depend on which image writer is installed."""
+    a = np.asarray(a, np.float64)
+    lo, hi = float(np.nanmin(a)), float(np.nanmax(a))
+    if hi == lo:
+        return a.astype(np.uint8)
+    if lo >= 0 and hi <= 1:
+        return (a * 255.0 + 0.499999999).astype(np.uint8)
+    return ((a - lo) / (hi - lo) * 255.0 + 0.499999999).astype(np.uint8)
+
+
+def gt_warping(rgb_gt, depth_gt, pose_gt, poses_tar, H, W, intrinsic, logpath=None, mask_gt=None, warp_depth=False, bilinear_splat=False,
+               device=None):
+    """Same signature / return as utils.py:122 (plus ``device``): one source view forward-warped to every pose of ``poses_tar``
+    [V,4,4] (camera-to-world, host arrays or tensors): ``(rgbs [V,H,W,3] float32 in [0,1], white where nothing landed, masks [V,H,W]
+    int64[, depths [V,H,W] float64 when warp_depth])``. All V targets are one launch set over one upload of the source.
+    ``bilinear_splat=False`` (the reference's default, its nearest-pixel raster loop) is not on the Text2NeRF path — every call site
+    passes True — and is rejected. ``mask_gt`` must be boolean or 0/1-valued (the reference multiplies the weights by it): checked for
+    numpy input, required of device input. ``rgb_gt`` is float32 in [0,1]. ``logpath``: the reference's previews,
+    ``DIBR_gt/{warped,mask,mask_inv,warped_depth}/%05d.png`` numbered from 1."""
+    if not bilinear_splat:
+        raise T2NError("gt_warping: bilinear_splat=False (the nearest-pixel raster loop) is not on the Text2NeRF path and is not "
+                       "implemented; every call site of the driver passes bilinear_splat=True")
+    if mask_gt is not None and isinstance(mask_gt, np.ndarray) and not _is01(mask_gt):
+        raise T2NError("gt_warping: mask_gt must be boolean or hold only 0 and 1 (it scales the splat weights)")
+    lib = _lib.load()
+    as_numpy = isinstance(rgb_gt, np.ndarray)
+    dev = _dev(device if device is not None else (None if as_numpy else rgb_gt.device))
+    mats = _warp_mats(pose_gt, poses_tar, intrinsic)
+    V = mats[3]
+    rgb, d, m1 = _to(rgb_gt, dev, torch.float32), _to(depth_gt, dev, torch.float32), _mask_u8(mask_gt, dev)
+    image = torch.empty(V, H, W, 3, dtype=torch.float32, device=dev)
+    mask = torch.empty(V, H, W, dtype=torch.int64, device=dev)
+    depth = torch.empty(V, H, W, dtype=torch.float64, device=dev) if warp_depth else None
+    if V > 0:
+        _warp_views(lib, dev, rgb, d, m1, None, H, W, mats, image, mask, depth, None, None)
+    if logpath is not None:
+        from .renderer import _imwrite
+        root = os.path.join(logpath, "DIBR_gt")
+        for sub in ("warped", "mask", "mask_inv") + (("warped_depth",) if warp_depth else ()):
+            os.makedirs(os.path.join(root, sub), exist_ok=True)
+        img_h, mask_h = image.cpu().numpy(), mask.cpu().numpy()
+        depth_h = depth.cpu().numpy() if warp_depth else None
+        for vv in range(V):
+            name = "%05d.png" % (vv + 1)
+            if warp_depth:
+                _imwrite(os.path.join(root, "warped_depth", name), _png8(depth_h[vv]))
+            _imwrite(os.path.join(root, "warped", name), np.rint(img_h[vv] * 255.0).astype(np.uint8))
+            _imwrite(os.path.join(root, "mask", name), (mask_h[vv] * 255).astype(np.uint8))
+            _imwrite(os.path.join(root, "mask_inv", name), ((1 - mask_h[vv]) * 255).astype(np.uint8))
+    out = (image, mask) + ((depth,) if warp_depth else ())
+    return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+
+_MASK_DTYPES = {torch.uint8: _lib.MASK_U8, torch.bool: _lib.MASK_U8, torch.int32: _lib.MASK_I32, torch.int64: _lib.MASK_I64,
+                torch.float32: _lib.MASK_F32, torch.float64: _lib.MASK_F64}
+
+
+def _stack(x):
+    if isinstance(x, (list, tuple)):
+        return torch.stack(list(x)) if isinstance(x[0], torch.Tensor) else np.stack([np.asarray(a) for a in x])
+    return x
+
+
+def _c2w_rows(poses):
+    p = np.ascontiguousarray(_host(poses), dtype=np.float32)
+    if p.ndim != 3 or p.shape[1:] != (4, 4):
+        raise T2NError(f"produce_formatted_data: poses must be [N,4,4] camera-to-world matrices, got {p.shape}")
+    rows = np.ascontiguousarray(p[:, :3, :4]).reshape(-1)
+    return p, (C.c_float * rows.size)(*rows.tolist())
+
+
+def _format_views(lib, dev, images, depths, masks, c2w, N, H, W, intrinsic, want_rows):
+    """t2n_format_views on the current stream of `dev`: (rays_split, all_rays, all_rgbs, all_depths, counts). The one host read is
+    the record {K, rows per view}; the row tensors are the first K rows of N*H*W-row buffers."""
+    fx, fy, cx, cy = [float(v) for v in intrinsic]
+    n = H * W
+    rays_split = torch.empty(N, n, 6, dtype=torch.float32, device=dev)
+    rows = rgbs = deps = record = ws = None
+    code = 0
+    if want_rows:
+        if masks.dtype not in _MASK_DTYPES:
+            masks = masks.to(torch.float32)
+        code = _MASK_DTYPES[masks.dtype]
+        rows = torch.empty(N * n, 6, dtype=torch.float32, device=dev)
+        rgbs = torch.empty(N * n, 3, dtype=torch.float32, device=dev)
+        deps = torch.empty(N * n, dtype=torch.float32, device=dev)
+        record = torch.empty(1 + N, dtype=torch.int64, device=dev)
+        ws = torch.empty(int(lib.t2n_format_views_workspace_bytes(H, W, N)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_format_views(_lib.ptr(images), _lib.ptr(depths), _lib.ptr(masks), code, N, H, W, c2w, fx, fy, cx, cy,
+                                        _lib.ptr(rays_split), _lib.ptr(rows), _lib.ptr(rgbs), _lib.ptr(deps), N * n, _lib.ptr(record),
+                                        _lib.ptr(ws), 0 if ws is None else ws.numel(), _lib.current_stream_ptr(dev)),
+                   "t2n_format_views")
+    if not want_rows:
+        return rays_split, None, None, None, None
+    rec = record.cpu().tolist()                 # K is data dependent: the one read-back
+    K = rec[0]
+    return rays_split, rows[:K], rgbs[:K], deps[:K], rec[1:]
+
+
+def produce_formatted_data(images, depths, masks, poses, intrinsic, H, W, mode='train', device=None):
+    """Same signature / return as dataLoader/scene_gen.py:31 (plus ``device``). ``mode='train'``: ``(all_rays [K,6], all_rgbs [K,3],
+    all_depths [K], all_rays_split [N,H*W,6], all_rgbs_split [N,H,W,3], all_depths_split [N,H,W], poses_tensor [N,4,4])``, all float32;
+    the K rows are the pixels with ``mask > 0.5`` in the reference's order (view-major, raster order inside a view). ``mode='test'``:
+    ``(all_rays_split, poses_tensor)``. numpy in -> CPU torch tensors (what the reference returns); device tensors in, or ``device=``
+    given -> device tensors. RGBA images (the reference's alpha-blend branch) are not on this path and are rejected."""
+    if mode not in ("train", "test"):
+        raise T2NError(f"produce_formatted_data: mode must be 'train' or 'test', got {mode!r}")
+    train = mode == "train"
+    if train:
+        images, depths, masks = _stack(images), _stack(depths), _stack(masks)
+        if images.shape[-1] == 4:
+            raise T2NError("produce_formatted_data: images with an alpha channel (RGBA) are not on the Text2NeRF path and are not "
+                           "implemented; blend them to RGB first")
+        if tuple(images.shape[1:]) != (H, W, 3) or tuple(depths.shape) != tuple(images.shape[:3]) or tuple(masks.shape) != tuple(depths.shape):
+            raise T2NError(f"produce_formatted_data: images {tuple(images.shape)}, depths {tuple(depths.shape)}, masks "
+                           f"{tuple(masks.shape)} must be [N,{H},{W},3], [N,{H},{W}], [N,{H},{W}]")
+    lead = images if train else poses
+    on_host = not isinstance(lead, torch.Tensor) or not lead.is_cuda
+    p44, c2w = _c2w_rows(poses)
+    N = p44.shape[0]
+    if train and images.shape[0] != N:
+        raise T2NError(f"produce_formatted_data: {images.shape[0]} images but {N} poses")
+    lib = _lib.load()
+    dev = _dev(device if device is not None else (None if on_host else lead.device))
+    to_host = on_host and device is None
+    img = dep = msk = None
+    if train:
+        img, dep = _to(images, dev, torch.float32), _to(depths, dev, torch.float32)
+        if isinstance(masks, np.ndarray):
+            masks = masks.view(np.uint8) if masks.dtype == np.bool_ else masks
+            if masks.dtype not in (np.uint8, np.int32, np.int64, np.float32, np.float64):
+                masks = masks.astype(np.float32)
+            masks = torch.from_numpy(np.ascontiguousarray(masks))
+        msk = masks.to(dev).contiguous()
+    rays_split, rows, rgbs, deps, _ = _format_views(lib, dev, img, dep, msk, c2w, N, H, W, intrinsic, train)
+    poses_tensor = torch.from_numpy(p44)
+    out = (rows, rgbs, deps, rays_split, img, dep, poses_tensor) if train else (rays_split, poses_tensor)
+    return tuple(t.cpu() if to_host else t.to(dev) for t in out)
+
+
+def build_support_set(img_new, depth_new, mask_inpainted, poses_support, intrinsic, H, W, device=None):
+    """The driver's support-set block (text2nerf_main.py:380-392) as one device-resident call: the new view ``img_new`` [H,W,3] /
+    ``depth_new`` [H,W] (float32) is warped from ``poses_support[0]`` to ``poses_support[1:]`` ONCE — unmasked colour and depth, plus the
+    coverage of the ``mask_inpainted`` pixels, which is the mask the driver's second, masked ``gt_warping`` call returns — the source
+    view is put in front (its mask: ``mask_inpainted``) and the N = 1 + V views go through the formatter. Returns
+    ``produce_formatted_data``'s 7-tuple as device tensors; ``all_depths_split[1:]`` is the warped depth rounded to float32.
+    ``mask_inpainted=None`` is the initial-view form (scene_gen.py:305-316): the source keeps every pixel and each warp its own unmasked
+    coverage. ``mask_inpainted`` must be boolean or 0/1-valued (checked for numpy input). ``poses_support`` should be a host array
+    (it is inverted on the host); the only device read-back is the row-count record."""
+    if mask_inpainted is not None and isinstance(mask_inpainted, np.ndarray) and not _is01(mask_inpainted):
+        raise T2NError("build_support_set: mask_inpainted must be boolean or hold only 0 and 1")
+    lib = _lib.load()
+    as_numpy = isinstance(img_new, np.ndarray)
+    dev = _dev(device if device is not None else (None if as_numpy else img_new.device))
+    p44, c2w = _c2w_rows(poses_support)
+    N = p44.shape[0]
+    poses_h = _host(poses_support)
+    rgb, d, maux = _to(img_new, dev, torch.float32), _to(depth_new, dev, torch.float32), _mask_u8(mask_inpainted, dev)
+    images = torch.empty(N, H, W, 3, dtype=torch.float32, device=dev)
+    depths = torch.empty(N, H, W, dtype=torch.float32, device=dev)
+    masks = torch.empty(N, H, W, dtype=torch.int64, device=dev)
+    images[0].copy_(rgb)
+    depths[0].copy_(d)
+    if maux is None:
+        masks[0].fill_(1)
+    else:
+        masks[0].copy_(maux)
+    if N > 1:
+        mats = _warp_mats(poses_h[0], poses_h[1:], intrinsic)
+        _warp_views(lib, dev, rgb, d, None, maux, H, W, mats, images[1:], masks[1:] if maux is None else None, None, depths[1:],
+                    None if maux is None else masks[1:])
+    rays_split, rows, rgbs, deps, _ = _format_views(lib, dev, images, depths, masks, c2w, N, H, W, intrinsic, True)
+    return rows, rgbs, deps, rays_split, images, depths, torch.from_numpy(p44).to(dev)
