@@ -66,6 +66,8 @@ enum {
                                * MLP_Fea_noview head (27/6/128, 48 comps), the binned scatters and all head gradient tensors. */
     T2N_FLAG_PIPELINE = 64u,  /* t2n_train_step only: the pipelined form is allowed (the caller has not touched the field since its previous
                                * t2n_train_step) */
+    T2N_FLAG_GATHER_BATCH = 128u, /* t2n_train_step only: the batch is gathered from the field's training source by row index
+                               * (t2n_field_set_train_source): rays / rgb_target / depth_target of the call are DESTINATIONS */
     T2N_FLAG_COHERENT = 8u    /* hint (eval): rays are a row-major image whose width was given by t2n_field_set_frame_width:
                                  march 8x8-pixel tiles whose rays share one texel x line-row dot-product table per step
                                  (f32 matrix cores). Same samples; the density feature is summed in table order and the
@@ -560,7 +562,7 @@ int t2n_depth_align_global(const float* depth_rendered, const float* depth_est, 
 #define T2N_TRAIN_HEAD_GRAD_FLOATS (27 * 144 + 128 * 351 + 128 + 128 * 128 + 128 + 3 * 128 + 3 + 1)
 typedef struct t2n_train_step_args {
     const float* rays; int64_t n_rays; int32_t ray_stride; int32_t n_samples;
-    uint32_t flags;            /* T2N_FLAG_ADD_BG, T2N_FLAG_PIPELINE or 0 (T2N_FLAG_TRAIN is implied) */
+    uint32_t flags;            /* T2N_FLAG_ADD_BG, T2N_FLAG_PIPELINE, T2N_FLAG_GATHER_BATCH or 0 (T2N_FLAG_TRAIN is implied) */
     uint32_t phases;           /* 1 | 2, or 4 alone (sharded optimiser: see shard_world) */
     const float* jitter; const float* rgb_target; const float* depth_target;
     float w_depth, w_trans, delta;
@@ -579,6 +581,25 @@ typedef struct t2n_train_step_args {
 } t2n_train_step_args;
 size_t t2n_train_step_workspace_bytes(const t2n_field* f, int64_t n_rays, int n_samples, int64_t rows_capacity);
 int t2n_train_step(t2n_field* f, const t2n_train_step_args* a, t2n_stream stream);
+/* A training set that lives on the device, and a step that takes ROW INDICES (T2N_FLAG_GATHER_BATCH): the field remembers where the set
+ * is (by value; NULL clears; host-only: no stream work, nothing is read here), and a flagged phases & 1 call fills its own batch —
+ * a->rays (ray_stride must be 6), a->rgb_target, a->depth_target, destinations inside batch_buffer — from the rows ids[0..n_rays) as its
+ * first device work: further rows of the step's zero-fill launch (no extra launch; a captured step keeps its DAG), on the stream the
+ * early part runs on, behind the engine copy of host_batch (always the engine copy: T2N_COPY_KERNEL is ignored by a gathering step),
+ * which then covers ids | jitter | hyper only (2 n_rays + 32 words where the plain form sends 11 n_rays + 32). An id outside [0, n_rows) is clamped into range by the kernel: a caller error, never an
+ * out-of-bounds read. The flag without a source: T2N_ERR_STATE; n_rows < 1 or ray_stride < 6: T2N_ERR_INVALID (both before anything is
+ * enqueued). phases = 2 and phases = 4 calls ignore the flag. The source's rows must have been written on `stream` (or be complete) when
+ * the step is submitted: the first gathering step after a source whose pointers or n_rows differ from the previous one orders its early
+ * part behind `stream` even in the pipelined form; the caller keeps the source's memory alive until the step has run. A captured graph
+ * freezes the source's pointers like every other: re-capture after a change. */
+typedef struct t2n_train_source {
+    const float* rays;  int32_t ray_stride;   /* [n_rows, ray_stride], ray_stride >= 6 (origin, direction first) */
+    const float* rgb;                         /* [n_rows, 3] */
+    const float* depth;                       /* [n_rows] */
+    int64_t n_rows;
+    const int32_t* ids;                       /* device, n_rays entries: normally inside batch_buffer, filled by the host_batch copy */
+} t2n_train_source;
+int t2n_field_set_train_source(t2n_field* f, const t2n_train_source* src);
 /* The sharded optimiser's partition for `world` ranks: out[3 t + 0] = offset of factor tensor t in the field's gradient buffer (floats),
  * out[3 t + 1] = floats of ONE rank's slice of its body (0 for the lines), out[3 t + 2] = its floats in all; t = 0..11 in the order density
  * planes, density lines, appearance planes, appearance lines (channel-last: position-major, C = 16 / 48 floats per position). */

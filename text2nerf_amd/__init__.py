@@ -10,3 +10,4 @@ from .tensorf import (AlphaGridMask, MLPRender, MLPRender_Fea, MLPRender_Fea_nov
 from .ray_utils import (get_ray_directions, get_ray_directions_blender, get_rays, generate_rays, dda, ray_marcher,  # noqa: F401
                         ndc_rays_blender, ndc_rays, sample_pdf, depth2dist, ndc2dist)
 from .sh import eval_sh_bases  # noqa: F401
+from .dataset import DeviceTrainSet  # noqa: F401

@@ -18,6 +18,7 @@ STAT_EVALUATED, STAT_APPEARANCE, STAT_RAYS, STAT_OVERFLOW, STAT_F16_REDO, STAT_L
 FLAG_TRAIN, FLAG_ADD_BG, FLAG_KEEP_CTX, FLAG_COHERENT, FLAG_NDC = 1, 2, 4, 8, 16
 FLAG_DEVICE_ROWS = 32
 FLAG_PIPELINE = 64
+FLAG_GATHER_BATCH = 128
 SHADE_IDS = {"MLP_Fea_noview": 0, "SH": 1, "RGB": 2, "MLP_Fea": 3, "MLP_PE": 4, "MLP": 5}   # MLP_PE: rejected in tensorf.py (broken upstream)
 ACT_IDS = {"softplus": 0, "relu": 1}
 MASK_U8, MASK_I32, MASK_I64, MASK_F32, MASK_F64 = 0, 1, 2, 3, 4   # T2N_MASK_*: dtypes t2n_format_views reads a mask in
@@ -71,6 +72,11 @@ class TrainStepArgs(C.Structure):   # t2n_train_step_args
                 ("head_grads", C.c_void_p), ("rows_capacity", C.c_int64),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("losses", C.c_void_p), ("host_batch", C.c_void_p), ("host_batch_bytes", C.c_size_t), ("batch_buffer", C.c_void_p),
                 ("shard_world", C.c_int32), ("shard_rank", C.c_int32)]
+
+
+class TrainSource(C.Structure):   # t2n_train_source
+    _fields_ = [("rays", C.c_void_p), ("ray_stride", C.c_int32), ("rgb", C.c_void_p), ("depth", C.c_void_p), ("n_rows", C.c_int64),
+                ("ids", C.c_void_p)]
 
 
 _lib = None
@@ -186,6 +192,7 @@ SIGNATURES = {
                                           C.c_void_p]),
     "t2n_train_step_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int64, C.c_int, C.c_int64]),
     "t2n_train_step": (C.c_int, [C.c_void_p, C.POINTER(TrainStepArgs), C.c_void_p]),
+    "t2n_field_set_train_source": (C.c_int, [C.c_void_p, C.POINTER(TrainSource)]),
     "t2n_field_train_set_step": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "t2n_field_train_record": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "t2n_field_shard_layout": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]),

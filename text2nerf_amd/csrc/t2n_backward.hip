@@ -1912,14 +1912,40 @@ namespace t2n {
 
 // zero fills of one step as ONE launch: region r = blockIdx.y (a uniform index into the kernel arguments)
 constexpr int kZeroRegions = 12;
+// T2N_FLAG_GATHER_BATCH: the batch rows of a device-resident training set, by index (one more grid row of the zero-fill launch)
+struct GatherOps { const float* rays; const float* rgb; const float* depth; const int* ids; float* d_rays; float* d_rgb; float* d_depth;
+    long long n_rows; unsigned n; int stride; int vec; };
 struct ZeroOps { unsigned* ptr[kZeroRegions]; unsigned long long words[kZeroRegions]; int n = 0;
     const uint4* up_src = nullptr; uint4* up_dst = nullptr; unsigned long long up_n16 = 0;   // optional upload: 16-byte words from pinned host memory (grid row n)
+    int g_row = -1; GatherOps g = {};   // optional gather (grid row g_row, behind the zero fills and the upload row)
     bool add(void* p, size_t bytes) { if (!p || !bytes) return true; if (n >= kZeroRegions) return false; ptr[n] = (unsigned*)p; words[n] = (bytes + 3) / 4; ++n; return true; } };
 __global__ __launch_bounds__(256) void k_zero_regions(const ZeroOps o) {
     const int r = blockIdx.y;
-    if (r == o.n) {   // the batch: read over the host link by the kernel itself (same steady-state time as an engine copy in front of the launch, which stalled the stream for ~5 ms once per process)
+    if (r == o.n && o.up_src) {   // the batch: read over the host link by the kernel itself (same steady-state time as an engine copy in front of the launch, which stalled the stream for ~5 ms once per process)
         for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < o.up_n16; i += (unsigned long long)gridDim.x * 256)
             o.up_dst[i] = o.up_src[i];
+        return;
+    }
+    if (r == o.g_row) {   // one thread per batch row: rays[id] (24 B, three 8-byte loads when source and destination allow), rgbs[id], depths[id]
+        const GatherOps& g = o.g;
+        for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < g.n; i += gridDim.x * 256u) {
+            long long id = g.ids[i];
+            id = id < 0 ? 0 : (id >= g.n_rows ? g.n_rows - 1 : id);     // (memory safety does not depend on the caller)
+            const float* __restrict__ sr = g.rays + id * g.stride;
+            float* __restrict__ dr = g.d_rays + (size_t)i * 6;
+            if (g.vec) {
+                const float2 a = reinterpret_cast<const float2*>(sr)[0], b = reinterpret_cast<const float2*>(sr)[1], c = reinterpret_cast<const float2*>(sr)[2];
+                reinterpret_cast<float2*>(dr)[0] = a; reinterpret_cast<float2*>(dr)[1] = b; reinterpret_cast<float2*>(dr)[2] = c;
+            } else {
+                const float a0 = sr[0], a1 = sr[1], a2 = sr[2], a3 = sr[3], a4 = sr[4], a5 = sr[5];
+                dr[0] = a0; dr[1] = a1; dr[2] = a2; dr[3] = a3; dr[4] = a4; dr[5] = a5;
+            }
+            const float* __restrict__ sc = g.rgb + id * 3;
+            const float c0 = sc[0], c1 = sc[1], c2 = sc[2];
+            float* __restrict__ dc = g.d_rgb + (size_t)i * 3;
+            dc[0] = c0; dc[1] = c1; dc[2] = c2;
+            g.d_depth[i] = g.depth[id];
+        }
         return;
     }
     unsigned* __restrict__ p = o.ptr[r];
@@ -2065,6 +2091,20 @@ extern "C" int t2n_field_train_set_step(t2n_field* f, uint32_t step, t2n_stream 
     return T2N_OK;
 }
 
+extern "C" int t2n_field_set_train_source(t2n_field* f, const t2n_train_source* src) {
+    if (!f) { set_error("t2n_field_set_train_source: NULL field"); return T2N_ERR_INVALID; }
+    if (!src) { f->train_src = t2n_train_source{}; f->train_src_set = false; f->train_src_fresh = false; return T2N_OK; }
+    if (src->n_rows < 1 || src->ray_stride < 6 || !src->rays || !src->rgb || !src->depth || !src->ids) {
+        set_error("t2n_field_set_train_source: n_rows %lld (>= 1), ray_stride %d (>= 6) or a NULL pointer", (long long)src->n_rows, src->ray_stride);
+        return T2N_ERR_INVALID;
+    }
+    const t2n_train_source& o = f->train_src;
+    if (!f->train_src_set || o.rays != src->rays || o.rgb != src->rgb || o.depth != src->depth || o.n_rows != src->n_rows || o.ray_stride != src->ray_stride)
+        f->train_src_fresh = true;
+    f->train_src = *src; f->train_src_set = true;
+    return T2N_OK;
+}
+
 extern "C" int t2n_field_train_record(const t2n_field* f, uint32_t out[36]) {
     if (!f || !out) { set_error("t2n_field_train_record: NULL argument"); return T2N_ERR_INVALID; }
     if (!f->train_host) { for (int i = 0; i < 36; ++i) out[i] = 0u; return T2N_OK; }
@@ -2120,6 +2160,14 @@ extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_st
     const TrainCarve T = train_carve(f, R, N, rows);
     if (T.total > A->workspace_bytes) { set_error("t2n_train_step: workspace %zu B < %zu B", A->workspace_bytes, T.total); return T2N_ERR_WORKSPACE; }
     if (!f->gbuf_all) { set_error("t2n_train_step: the field has no gradient buffer (t2n_field_set_grad_buffer)"); return T2N_ERR_STATE; }
+    // T2N_FLAG_GATHER_BATCH: refused before anything is enqueued
+    const bool gather = (A->flags & T2N_FLAG_GATHER_BATCH) && (A->phases & 1u);
+    if (gather) {
+        if (!f->train_src_set) { set_error("t2n_train_step: T2N_FLAG_GATHER_BATCH without a training source (t2n_field_set_train_source)"); return T2N_ERR_STATE; }
+        const t2n_train_source& S = f->train_src;
+        if (S.n_rows < 1 || S.ray_stride < 6 || !S.rays || !S.rgb || !S.depth || !S.ids) { set_error("t2n_train_step: training source with n_rows %lld, ray_stride %d or a NULL pointer", (long long)S.n_rows, S.ray_stride); return T2N_ERR_INVALID; }
+        if (A->ray_stride != 6) { set_error("t2n_train_step: T2N_FLAG_GATHER_BATCH fills a batch of ray_stride 6 (got %d)", A->ray_stride); return T2N_ERR_INVALID; }
+    }
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = train_ensure(f, s))) return rc;
@@ -2176,7 +2224,10 @@ extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_st
             f->train_packed = true;
         }
         T2N_HIP(hipEventRecord(ev[0], s));
-        if (pipe && !chain_prev) T2N_HIP(hipStreamWaitEvent(se, ev[0], 0));   // (the previous call left no density-Adam event on sa: behind `stream`)
+        // (the previous call left no density-Adam event on sa: behind `stream`; so is the first gather from a training source that changed —
+        // its rows were written on the caller's stream)
+        if (pipe && (!chain_prev || (gather && f->train_src_fresh))) T2N_HIP(hipStreamWaitEvent(se, ev[0], 0));
+        if (gather) f->train_src_fresh = false;
         const uint4* up_src = nullptr;
         if (A->host_batch) {
             if (!A->batch_buffer || !A->host_batch_bytes) { set_error("t2n_train_step: host_batch without batch_buffer / host_batch_bytes"); return T2N_ERR_INVALID; }
@@ -2186,7 +2237,9 @@ extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_st
             // runs (0 of 44 with the engine copy, 0 of 16 unpipelined; tools/r6_fault_loop.sh, profiles/round6_train_ab.txt); unexplained
             static const bool engine_copy = !(getenv("T2N_COPY_KERNEL") && atoi(getenv("T2N_COPY_KERNEL")) != 0);
             void* dp = nullptr;
-            if (!engine_copy && ((uintptr_t)A->host_batch & 15u) == 0 && ((uintptr_t)A->batch_buffer & 15u) == 0 && (A->host_batch_bytes & 15u) == 0 &&
+            // (a gathering step always takes the engine copy: the gather row of the zero-fill launch reads the ids this copy writes, and
+            // rows of one launch are not ordered against each other)
+            if (!engine_copy && !gather && ((uintptr_t)A->host_batch & 15u) == 0 && ((uintptr_t)A->batch_buffer & 15u) == 0 && (A->host_batch_bytes & 15u) == 0 &&
                 hipHostGetDevicePointer(&dp, const_cast<void*>((const void*)A->host_batch), 0) == hipSuccess && dp) up_src = (const uint4*)dp;
             else { (void)hipGetLastError(); T2N_HIP(hipMemcpyAsync(A->batch_buffer, A->host_batch, A->host_batch_bytes, hipMemcpyHostToDevice, se)); }
         }
@@ -2211,9 +2264,17 @@ extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_st
             unsigned long long mx = 1;
             for (int r = 0; r < zo.n; ++r) mx = zo.words[r] > mx ? zo.words[r] : mx;
             if (up_src) { zo.up_src = up_src; zo.up_dst = (uint4*)A->batch_buffer; zo.up_n16 = A->host_batch_bytes / 16; mx = zo.up_n16 * 16 > mx ? zo.up_n16 * 16 : mx; }   // (one 16-byte word per thread up to 256 workgroups)
+            if (gather) {   // behind the copy of ids | jitter | hyper on the same stream; device memory only
+                const t2n_train_source& S = f->train_src;
+                zo.g_row = zo.n + (up_src ? 1 : 0);
+                zo.g = GatherOps{S.rays, S.rgb, S.depth, (const int*)S.ids, const_cast<float*>(A->rays), const_cast<float*>(A->rgb_target), const_cast<float*>(A->depth_target),
+                                 (long long)S.n_rows, (unsigned)R, (int)S.ray_stride,
+                                 (((uintptr_t)S.rays | (uintptr_t)A->rays) & 7u) == 0 && (S.ray_stride & 1) == 0 ? 1 : 0};
+                mx = (unsigned long long)R * 16 > mx ? (unsigned long long)R * 16 : mx;   // (one thread per batch row up to 256 workgroups)
+            }
             unsigned bx = (unsigned)((mx + 4095) / 4096);
             bx = bx > 256 ? 256 : (bx < 1 ? 1 : bx);
-            hipLaunchKernelGGL(k_zero_regions, dim3(bx, (unsigned)zo.n + (up_src ? 1u : 0u)), dim3(256), 0, se, zo);
+            hipLaunchKernelGGL(k_zero_regions, dim3(bx, (unsigned)zo.n + (up_src ? 1u : 0u) + (gather ? 1u : 0u)), dim3(256), 0, se, zo);
         }
         // ---- forward: march
         if ((rc = launch_march(f, L, se))) return rc;

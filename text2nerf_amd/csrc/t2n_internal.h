@@ -136,6 +136,8 @@ struct t2n_field {
     void* train_dev = nullptr; unsigned* train_host = nullptr; void* train_ev[12] = {};
     unsigned train_calls = 0; bool train_chain = false;   // pipelined steps: stream of a step's early part; calls so far (workspace / scalar slot parity); the previous call left its density-Adam event
     bool train_packed = false;   // the backward chain's operands in train_dev are those of the current head weights
+    t2n_train_source train_src = {}; bool train_src_set = false;   // T2N_FLAG_GATHER_BATCH: where the device-resident training set is
+    bool train_src_fresh = false;    // its pointers / n_rows changed since the last gathering step (that step's early part goes behind the caller's stream)
     unsigned list_hint = 0;          // appearance entries per ray of the last budgeted launch (0: unknown)
     unsigned long long list_retries = 0;
 };

@@ -1355,18 +1355,9 @@ class TensorBase(nn.Module):
         0.86 ms per 16 384-ray step measured), so it is opt-in. The returned loss tensor is a fixed buffer the next step overwrites."""
         lib = _lib.load()
         params = self._autograd_params()
-        can_fuse = self._can_fuse_train_step(optimizer) and (all_reduce is None or all_reduce_averages) and not speculative
-        if fused and not can_fuse:
-            raise T2NError("train_step(fused=True): needs the tuned field shape with the MLP_Fea_noview head (split-f16 arithmetic), fp32 factor "
-                           "storage, no alpha mask, optim.TVAdam(field=tensorf) and an averaging all_reduce")
-        if can_fuse and fused is not False:
-            from .trainer import FusedStep
-            fs = self.__dict__.get("_fused_step")
-            if fs is None or fs.opt is not optimizer:
-                fs = self.__dict__["_fused_step"] = FusedStep(self, optimizer)
-            N = int(N_samples) if N_samples > 0 else self.nSamples
-            flags = FLAG_ADD_BG if (white_bg or bool(torch.rand((1,)) < 0.5)) else 0
-            use_graph = bool(graph) and all_reduce is None
+        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph)
+        if fuse is not None:
+            fs, N, flags, use_graph = fuse
             return fs.step(rays, rgb_target, depth_target, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce)
         if any(not p.is_leaf for p in params):
             raise T2NError("train_step needs the kernels' own field shape (the parameters ARE the kernel tensors); embedded shapes, "
@@ -1442,6 +1433,43 @@ class TensorBase(nn.Module):
                 if len(evs) > 2:
                     evs.pop(0).synchronize()
         return losses
+
+    def train_step_indexed(self, source, ids, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
+                           tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None):
+        """`train_step` on rows `ids` of a `dataset.DeviceTrainSet` (rays, colours and depths kept on the device): same keyword
+        arguments, same arithmetic, same draws from the CPU generator in the same order. `ids`: an int64 (as SimpleSampler returns it) or
+        int32 tensor. On the host its range is checked before anything is drawn or queued — an id outside [0, len(source)) or a
+        non-integer dtype raises T2NError and leaves the parameters, Adam's step count and the RNG state as they were — and, where the
+        fused step applies, the host sends ids | jitter | hyper (2 R + 32 words instead of 11 R + 32) and the step gathers its batch
+        itself, pipelined like a host batch. Device ids take the unpipelined route, as device batch tensors do in `train_step`. Where
+        the fused step does not apply this is `train_step(*source.rows(ids), ...)`."""
+        from .dataset import check_ids
+        ids = check_ids(ids, len(source))
+        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph)
+        if fuse is not None:
+            fs, N, flags, use_graph = fuse
+            return fs.step_indexed(source, ids, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce)
+        rays, rgb_t, dep_t = source.rows(ids)
+        return self.train_step(rays, rgb_t, dep_t, optimizer, N_samples=N_samples, white_bg=white_bg, w_depth=w_depth, w_trans=w_trans,
+                               delta=delta, tv=tv, all_reduce=all_reduce, all_reduce_averages=all_reduce_averages, speculative=speculative,
+                               fused=False if fused is None else fused, graph=graph)
+
+    def _fused_step_for(self, optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph):
+        """The fuse decision of train_step / train_step_indexed: None (the composed step), or (the field's FusedStep for this optimiser,
+        N, flags, use_graph) with the background coin drawn — the first draw of a fused step from the CPU generator."""
+        can_fuse = self._can_fuse_train_step(optimizer) and (all_reduce is None or all_reduce_averages) and not speculative
+        if fused and not can_fuse:
+            raise T2NError("train_step(fused=True): needs the tuned field shape with the MLP_Fea_noview head (split-f16 arithmetic), fp32 factor "
+                           "storage, no alpha mask, optim.TVAdam(field=tensorf) and an averaging all_reduce")
+        if not can_fuse or fused is False:
+            return None
+        from .trainer import FusedStep
+        fs = self.__dict__.get("_fused_step")
+        if fs is None or fs.opt is not optimizer:
+            fs = self.__dict__["_fused_step"] = FusedStep(self, optimizer)
+        N = int(N_samples) if N_samples > 0 else self.nSamples
+        flags = FLAG_ADD_BG if (white_bg or bool(torch.rand((1,)) < 0.5)) else 0
+        return fs, N, flags, bool(graph) and all_reduce is None
 
     def _can_fuse_train_step(self, optimizer):
         return (getattr(optimizer, "field", None) is self and self.supports_deferred_factor_grads() and self.shadingMode == "MLP_Fea_noview"

@@ -226,12 +226,51 @@ class FusedStep:
         except Exception:
             pass
 
-    def _args(self, slot_i, R, stride, N, flags, phases, cap, betas, eps, w_depth, w_trans, delta):
+    @staticmethod
+    def _layout(R, stride, indexed=False):
+        """Word offsets of an input buffer's sections, its size `n` and the leading words `host` the host copy covers. Plain form:
+        rays | jitter | rgb | depth | hyper, all of it copied. Indexed form: ids | jitter | hyper — what the host sends — in front,
+        then the rays | rgb | depth sections the step's gather fills; every section starts on a 16-byte boundary."""
+        H = _lib.TRAIN_HYPER_FLOATS
+        if not indexed:
+            n = R * stride + 5 * R + H
+            return dict(rays=0, jitter=R * stride, rgb=R * stride + R, depth=R * stride + 4 * R, hyper=n - H, n=n, host=n)
+        up = lambda k: (k + 3) // 4 * 4      # noqa: E731
+        host = 2 * up(R) + H
+        rgb = host + up(6 * R)
+        depth = rgb + up(3 * R)
+        return dict(ids=0, jitter=up(R), hyper=2 * up(R), rays=host, rgb=rgb, depth=depth, n=depth + up(R), host=host)
+
+    @staticmethod
+    def _source_key(m):
+        """(pointers of the training set's storage, its rows) of a gathering step, or None."""
+        src = m.get("source") if m is not None else None
+        if src is None:
+            return None
+        return tuple(t.data_ptr() for t in src.storage()) + (len(src),)
+
+    def _set_source(self, slot_i, m):
+        """Tell the field where a gathering step's rows and this slot's ids are (host-only call)."""
+        sk = self._source_key(m)
+        if sk is None:
+            return
+        ids = self.inbuf[slot_i].data_ptr() + 4 * self._layout(m["R"], m["stride"], True)["ids"]
+        ts = _lib.TrainSource(sk[0], 6, sk[1], sk[2], sk[3], ids)
+        _lib.check(_lib.load().t2n_field_set_train_source(self.field._handle, C.byref(ts)), "t2n_field_set_train_source")
+
+    def _args_of(self, slot_i, m, phases, cap):
+        return self._args(slot_i, m["R"], m["stride"], m["N"], m["flags"], phases, cap, m["betas"], m["eps"], m["w_depth"], m["w_trans"],
+                          m["delta"], bool(m.get("indexed")), self._source_key(m))
+
+    def _args(self, slot_i, R, stride, N, flags, phases, cap, betas, eps, w_depth, w_trans, delta, indexed=False, src=None):
         f = self.field
         ps, ms, vs, _ = self._moments()
         buf = self.inbuf[slot_i]
         ws = self._workspace(R, N, cap)
-        ck = (slot_i, R, stride, N, flags, phases, cap, betas, eps, w_depth, w_trans, delta, ws.data_ptr(), buf.data_ptr(), ps[0].data_ptr())
+        if src is not None:
+            flags |= _lib.FLAG_GATHER_BATCH
+        ck = (slot_i, R, stride, N, flags, phases, cap, betas, eps, w_depth, w_trans, delta, ws.data_ptr(), buf.data_ptr(), ps[0].data_ptr(),
+              indexed, src)
         hit = self._arg_cache.get(ck)
         if hit is not None:
             hit[0].host_batch, hit[0].host_batch_bytes = None, 0
@@ -239,13 +278,13 @@ class FusedStep:
         if len(self._arg_cache) > 64:
             self._arg_cache.clear()
         a = _lib.TrainStepArgs()
-        o = 0
+        o = self._layout(R, stride, indexed)
         base = buf.data_ptr()
-        a.rays = base; o += R * stride
-        a.jitter = base + 4 * o; o += R
-        a.rgb_target = base + 4 * o; o += 3 * R
-        a.depth_target = base + 4 * o; o += R
-        a.hyper = base + 4 * o
+        a.rays = base + 4 * o["rays"]
+        a.jitter = base + 4 * o["jitter"]
+        a.rgb_target = base + 4 * o["rgb"]
+        a.depth_target = base + 4 * o["depth"]
+        a.hyper = base + 4 * o["hyper"]
         a.n_rays, a.ray_stride, a.n_samples, a.flags, a.phases = R, stride, N, flags, phases
         a.w_depth, a.w_trans, a.delta = w_depth, w_trans, delta
         a.beta1, a.beta2, a.eps = betas[0], betas[1], eps
@@ -259,7 +298,7 @@ class FusedStep:
         a.losses = self.losses.data_ptr()
         a.host_batch, a.host_batch_bytes, a.batch_buffer = None, 0, buf.data_ptr()
         key = (R, stride, N, flags, phases, cap, betas, eps, w_depth, w_trans, delta, ws.data_ptr(), buf.data_ptr(),
-               tuple(p.data_ptr() for p in ps), tuple(t.data_ptr() for t in ms), tuple(t.data_ptr() for t in vs))
+               tuple(p.data_ptr() for p in ps), tuple(t.data_ptr() for t in ms), tuple(t.data_ptr() for t in vs), indexed, src)
         self._arg_cache[ck] = (a, key)
         return a, key
 
@@ -277,8 +316,8 @@ class FusedStep:
                     self._drop_graphs()
                     for j in range(_RING):
                         self._ensure_inbuf(j, self.inbuf[slot_i].numel())
-                        aj, kj = self._args(j, m["R"], m["stride"], m["N"], m["flags"], 3, int(a.rows_capacity), m["betas"], m["eps"],
-                                            m["w_depth"], m["w_trans"], m["delta"])
+                        aj, kj = self._args_of(j, m, 3, int(a.rows_capacity))
+                        self._set_source(j, m)          # (frozen into the graph with every other pointer: its key carries them)
                         h = C.c_void_p()
                         _lib.check(lib.t2n_train_graph_capture(f._handle, C.byref(aj), st, C.byref(h)), "t2n_train_graph_capture")
                         self.graphs[(j, kj)] = h
@@ -294,6 +333,8 @@ class FusedStep:
                     if self.pipe_ok and self.pipe_ws and int(a.phases) == 3:
                         a.flags = int(a.flags) | _lib.FLAG_PIPELINE
                         self.pipelined_launches += 1
+                if int(a.phases) & 1:
+                    self._set_source(slot_i, m)
                 _lib.check(lib.t2n_train_step(f._handle, C.byref(a), st), "t2n_train_step")
                 self.eager_launches += 1
 
@@ -321,6 +362,8 @@ class FusedStep:
         """Submit the withheld batches again (eagerly), each with room for the rows its record said it needs."""
         while self.queue:
             data, m, need = self.queue.pop(0)
+            if m.get("source") is not None:     # (the withheld step's gather filled the buffer this replays: ids, jitter and rows as they were)
+                m = dict(m, source=None, keep=None)
             self.rows_cap = max(self.rows_cap, _ladder(need + 32))
             i = self._free_slot()
             self._ensure_inbuf(i, data.numel())
@@ -358,16 +401,16 @@ class FusedStep:
         if self.cap_once:                   # (tests: ONE submission with this capacity, whatever the records say)
             cap, self.cap_once = int(self.cap_once) // 32 * 32, 0
         if all_reduce is None:
-            a, key = self._args(i, m["R"], m["stride"], m["N"], m["flags"], 3, cap, m["betas"], m["eps"], m["w_depth"], m["w_trans"], m["delta"])
+            a, key = self._args_of(i, m, 3, cap)
             self._launch(i, a, key, graph, m)
         else:
-            a, key = self._args(i, m["R"], m["stride"], m["N"], m["flags"], 1, cap, m["betas"], m["eps"], m["w_depth"], m["w_trans"], m["delta"])
+            a, key = self._args_of(i, m, 1, cap)
             # parallel.ShardedExchange: the sharded optimiser — phase 1 seeds the TV gradient for the blocks this rank owns, the exchange
             # averages (reduce-scatter of the plane bodies + one small all-reduce), phase 2 steps the owned and the replicated blocks,
             # the exchange all-gathers the channel-last parameter bodies, phase 4 writes the gathered blocks to the caller's tensors
             sharded = hasattr(all_reduce, "gather") and int(getattr(all_reduce, "world", 1)) > 1
             a.shard_world, a.shard_rank = (int(all_reduce.world), int(all_reduce.rank)) if sharded else (0, 0)
-            self._launch(i, a, key, False)
+            self._launch(i, a, key, False, m)
             f._gbuf_dirty, f._gbuf_stale, f._gbuf_reduced = True, False, False
             f._deferred_grad_key = f._uploaded_key
             self._install_head_grads()
@@ -386,7 +429,9 @@ class FusedStep:
         self.issued += 1
         self._after_update()
 
-    def step(self, rays, rgb_t, dep_t, N, flags, w_depth, w_trans, delta, tv, graph, all_reduce=None):
+    def _begin(self, R):
+        """What every step starts with: the native field current, the records consumed, withheld batches replayed, a free input buffer.
+        Returns (input buffer index, nobody touched the field since this driver's last step)."""
         f = self.field
         lib = _lib.load()
         untouched = self._key_after is not None and f._uploaded_key == self._key_after and \
@@ -408,7 +453,6 @@ class FusedStep:
         f.factor_grad_buffer(_raw=True)          # the field's gradient buffer exists and is the caller-owned one
         f._drop_preseed()
         self._poll()
-        R, stride = int(rays.shape[0]), int(rays.shape[1])
         if not self.rows_cap:
             # nothing known yet: room for 12 appearance samples per ray (the first records correct it; a step that needs more is replayed)
             self.rows_cap = _ladder(12 * R)
@@ -417,6 +461,24 @@ class FusedStep:
             if not self.queue:
                 break
             self._drain_queue()
+        return i, untouched
+
+    def _end(self, i):
+        f = self.field
+        self.host_batch = None
+        self._key_after = f._uploaded_key
+        f.device_rows_steps = getattr(f, "device_rows_steps", 0) + 1
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self.events.append(ev)
+        self.slot_done[i] = ev
+        if len(self.events) > _RUN_AHEAD:
+            self.events.pop(0).synchronize()
+        return self.losses
+
+    def step(self, rays, rgb_t, dep_t, N, flags, w_depth, w_trans, delta, tv, graph, all_reduce=None):
+        R, stride = int(rays.shape[0]), int(rays.shape[1])
+        i, untouched = self._begin(R)
         hyper, betas, eps = self._hyper(tv)
         n_in = R * stride + R + 3 * R + R + _lib.TRAIN_HYPER_FLOATS
         for j in range(_RING):          # (all four slots at once: a pinned allocation inside somebody's timed loop costs a millisecond)
@@ -451,16 +513,43 @@ class FusedStep:
             self.host_batch = None
         meta = dict(R=R, stride=stride, N=N, flags=flags, betas=betas, eps=eps, w_depth=float(w_depth), w_trans=float(w_trans), delta=float(delta))
         self._submit(i, meta, graph, all_reduce)
-        self.host_batch = None
-        self._key_after = f._uploaded_key
-        f.device_rows_steps = getattr(f, "device_rows_steps", 0) + 1
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.dev))
-        self.events.append(ev)
-        self.slot_done[i] = ev
-        if len(self.events) > _RUN_AHEAD:
-            self.events.pop(0).synchronize()
-        return self.losses
+        return self._end(i)
+
+    def step_indexed(self, source, ids, N, flags, w_depth, w_trans, delta, tv, graph, all_reduce=None):
+        """`step` on rows `ids` (validated: dataset.check_ids) of a dataset.DeviceTrainSet on this device: the host stages
+        ids (int32) | jitter | hyper — 2 R + 32 words instead of 11 R + 32 — and the C call gathers the rows into the slot's buffer as
+        its first device work (T2N_FLAG_GATHER_BATCH). The jitter is drawn where `step` draws it; everything behind the gather is `step`."""
+        if source.rays.device != self.dev:
+            raise T2NError(f"fused train step: the training set is on {source.rays.device}, the field on {self.dev}")
+        R, stride = int(ids.numel()), 6
+        i, untouched = self._begin(R)
+        hyper, betas, eps = self._hyper(tv)
+        lay = self._layout(R, stride, True)
+        n_in, n_host = lay["n"], lay["host"]
+        for j in range(_RING):
+            self._ensure_inbuf(j, n_in)
+        buf, pin = self.inbuf[i], self.pinned[i]
+        jitter = torch.rand(R, 1)      # CPU default generator, one draw per ray: models/tensorBase.py:313-317
+        if self._pin_np[i] is None or self._pin_np[i].shape[0] != n_in:
+            self._pin_np[i] = pin.numpy()
+        self._pin_np[i][lay["hyper"]:lay["hyper"] + _lib.TRAIN_HYPER_FLOATS] = hyper
+        pin[lay["jitter"]:lay["jitter"] + R].copy_(jitter.reshape(-1))
+        on_host = ids.device.type == "cpu"
+        if on_host:
+            pin[:R].view(torch.int32).copy_(ids)
+        else:
+            # device ids: the unpipelined route, as device batch tensors take it in `step`
+            buf[lay["jitter"]:n_host].copy_(pin[lay["jitter"]:n_host], non_blocking=True)
+            buf[:R].view(torch.int32).copy_(ids, non_blocking=True)
+        self.host_batch = (C.c_void_p(pin.data_ptr()), n_host * 4) if on_host else None
+        self.pipe_ok = bool(on_host and self.pipeline and untouched and not graph and all_reduce is None)
+        if on_host and (graph or all_reduce is not None or not self.pipeline):
+            buf[:n_host].copy_(pin[:n_host], non_blocking=True)
+            self.host_batch = None
+        meta = dict(R=R, stride=stride, N=N, flags=flags, betas=betas, eps=eps, w_depth=float(w_depth), w_trans=float(w_trans), delta=float(delta),
+                    indexed=True, source=source, keep=source.storage())     # (keep: the storage outlives the slot's step)
+        self._submit(i, meta, graph, all_reduce)
+        return self._end(i)
 
     def owns_head_grads(self, params):
         """True when `params` are exactly the 7 head tensors and their .grad are the views of this step's flat buffer."""
