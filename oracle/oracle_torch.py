@@ -247,13 +247,19 @@ def positional_encoding(x, freqs):
     return torch.cat([torch.sin(p), torch.cos(p)], -1)
 
 
-def mlp_fea_noview(params, feat, fea_pe):
+def _mlp_layers(params, x, pre=None):
+    """Linear-ReLU-Linear-ReLU-Linear-sigmoid; ``pre`` (a list) collects the two hidden layers' pre-activations (the ReLU inputs)."""
+    p0 = x @ params["renderModule.mlp.0.weight"].T + params["renderModule.mlp.0.bias"]
+    p1 = torch.relu(p0) @ params["renderModule.mlp.2.weight"].T + params["renderModule.mlp.2.bias"]
+    if pre is not None:
+        pre += [p0.detach(), p1.detach()]
+    return torch.sigmoid(torch.relu(p1) @ params["renderModule.mlp.4.weight"].T + params["renderModule.mlp.4.bias"])
+
+
+def mlp_fea_noview(params, feat, fea_pe, pre=None):
     """models/tensorBase.py:88-109."""
     x = torch.cat([feat, positional_encoding(feat, fea_pe)], -1) if fea_pe > 0 else feat
-    h = torch.relu(x @ params["renderModule.mlp.0.weight"].T + params["renderModule.mlp.0.bias"])
-    h = torch.relu(h @ params["renderModule.mlp.2.weight"].T + params["renderModule.mlp.2.bias"])
-    o = h @ params["renderModule.mlp.4.weight"].T + params["renderModule.mlp.4.bias"]
-    return torch.sigmoid(o)
+    return _mlp_layers(params, x, pre)
 
 
 def sh_bases_deg2(d):
@@ -265,13 +271,16 @@ def sh_bases_deg2(d):
                         SH_C2[3] * xz, SH_C2[4] * (xx - yy)], -1)
 
 
-def sh_render(viewdirs, feat):
+def sh_render(viewdirs, feat, pre=None):
     """models/tensorBase.py:29-33."""
     b = sh_bases_deg2(viewdirs)[:, None]
-    return torch.relu((b * feat.view(-1, 3, b.shape[-1])).sum(-1) + 0.5)
+    x = (b * feat.view(-1, 3, b.shape[-1])).sum(-1) + 0.5
+    if pre is not None:
+        pre.append(x.detach())
+    return torch.relu(x)
 
 
-def mlp_view_head(cfg: FieldConfig, params, pts, viewdirs, feat):
+def mlp_view_head(cfg: FieldConfig, params, pts, viewdirs, feat, pre=None):
     """The view-dependent heads, models/tensorBase.py:62-86 (MLP_Fea), :111-135 (MLP_PE), :137-159 (MLP): the reference's
     torch.cat column order, three Linear layers with ReLU, sigmoid."""
     cols = [feat, viewdirs]
@@ -281,19 +290,17 @@ def mlp_view_head(cfg: FieldConfig, params, pts, viewdirs, feat):
         cols.append(positional_encoding(pts, cfg.pos_pe))
     if cfg.view_pe > 0:
         cols.append(positional_encoding(viewdirs, cfg.view_pe))
-    x = torch.cat(cols, -1)
-    h = torch.relu(x @ params["renderModule.mlp.0.weight"].T + params["renderModule.mlp.0.bias"])
-    h = torch.relu(h @ params["renderModule.mlp.2.weight"].T + params["renderModule.mlp.2.bias"])
-    return torch.sigmoid(h @ params["renderModule.mlp.4.weight"].T + params["renderModule.mlp.4.bias"])
+    return _mlp_layers(params, torch.cat(cols, -1), pre)
 
 
-def shade(cfg: FieldConfig, params, viewdirs, feat, pts=None):
+def shade(cfg: FieldConfig, params, viewdirs, feat, pts=None, pre=None):
+    """``pre``: an optional list that receives the heads' ReLU inputs (hidden pre-activations of the MLP heads, SH's pre-ReLU colours)."""
     if cfg.shading_mode == "MLP_Fea_noview":
-        return mlp_fea_noview(params, feat, cfg.fea_pe)
+        return mlp_fea_noview(params, feat, cfg.fea_pe, pre)
     if cfg.shading_mode in ("MLP_Fea", "MLP_PE", "MLP"):
-        return mlp_view_head(cfg, params, pts, viewdirs, feat)
+        return mlp_view_head(cfg, params, pts, viewdirs, feat, pre)
     if cfg.shading_mode == "SH":
-        return sh_render(viewdirs, feat)
+        return sh_render(viewdirs, feat, pre)
     if cfg.shading_mode == "RGB":
         return feat
     raise NotImplementedError(cfg.shading_mode)
@@ -360,6 +367,7 @@ def forward(cfg: FieldConfig, params, rays, white_bg=True, is_train=False, n_sam
     fdt = pts.dtype if geom_dtype is None else next(iter(params.values())).dtype
     sigma = torch.zeros(pts.shape[:-1], dtype=fdt)
     rgb = torch.zeros(pts.shape[:2] + (3,), dtype=fdt)
+    relu_pre = [] if return_aux else None
     xn = normalize_coord(cfg, pts)
     if valid.any():
         s = feature2density(cfg, density_feature(params, xn[valid]))
@@ -369,7 +377,7 @@ def forward(cfg: FieldConfig, params, rays, white_bg=True, is_train=False, n_sam
     if app_mask.any():
         vd = rd[:, None, :].expand(pts.shape)
         f = app_feature(params, xn[app_mask])
-        c = shade(cfg, params, vd[app_mask], f, pts=xn[app_mask])
+        c = shade(cfg, params, vd[app_mask], f, pts=xn[app_mask], pre=relu_pre)
         rgb = _scatter(rgb, app_mask, c)
     acc = weight.sum(-1)
     rgb_map = (weight[..., None] * rgb).sum(-2)
@@ -379,7 +387,8 @@ def forward(cfg: FieldConfig, params, rays, white_bg=True, is_train=False, n_sam
     rgb_map = rgb_map.clamp(0, 1)
     depth = (weight * z).sum(-1) + (1.0 - acc) * rays[..., -1]
     if return_aux:
-        return rgb_map, depth, z, weight, dict(sigma=sigma, valid=valid, app_mask=app_mask, acc=acc, alpha=alpha, rgb_pre_clamp=rgb_raw)
+        return rgb_map, depth, z, weight, dict(sigma=sigma, valid=valid, app_mask=app_mask, acc=acc, alpha=alpha, rgb_pre_clamp=rgb_raw,
+                                                  relu_pre=relu_pre)
     return rgb_map, depth, z, weight
 
 

@@ -578,6 +578,7 @@ __device__ __forceinline__ float gen_input_col(const GenArgs& a, const float* __
     return cs ? cosf(tt) : sinf(tt);
 }
 constexpr int kGenUnitsPerWave = kGenHidMax / 4;   // 64
+constexpr int kGenPeRestart = 6;                   // octaves built by angle doubling from one sincosf in the ROWS form (<= 5 doublings)
 // wave-uniform weight reads through the CONSTANT address space: the backend then issues scalar loads (s_load_dwordx16 into SGPRs, the FMAs
 // take them as scalar operands); through a plain global pointer every weight was a 64-lane vector load of one address — 2 216 of them in
 // the head kernel, which made it load-issue-bound
@@ -710,8 +711,8 @@ __device__ __forceinline__ void gen_head_body(const GenArgs& a, const GenFast& f
         if constexpr (ROWS) {
             // ---- the input rows of this tile to memory. Columns are built in rounds of `hbc` of them in Hb (free once the feature partials
             // are reduced): the plain columns one by one; the features' encodings per FEATURE — one sincosf, then angle doubling per octave
-            // (sin 2x = 2 s c, cos 2x = c^2 - s^2: <= 5 steps, error ~3e-6) instead of a sinf or cosf per column, which was most of this
-            // kernel's time — then 16 columns at a time to memory: thread -> (row tid / 4, four columns), 64-byte runs per row
+            // (sin 2x = 2 s c, cos 2x = c^2 - s^2: <= 5 steps from a fresh sincosf, error ~3e-6) instead of a sinf or cosf per column, which
+            // was most of this kernel's time — then 16 columns at a time to memory: thread -> (row tid / 4, four columns), 64-byte runs per row
             const int fpe = a.shading == T2N_SHADE_MLP ? 0 : a.fea_pe;
             const int pe0 = D + (a.shading != T2N_SHADE_MLP_FEA_NOVIEW ? 3 : 0), pe1 = pe0 + 2 * fpe * D;
             const int hbc = fa.hbc;
@@ -725,13 +726,15 @@ __device__ __forceinline__ void gen_head_body(const GenArgs& a, const GenFast& f
                 for (int f = g; f < D; f += 4) {
                     const int js = pe0 + f * fpe, jc = js + fpe * D;
                     if ((js >= c1 || js + fpe <= c0) && (jc >= c1 || jc + fpe <= c0)) continue;
-                    float sv, cv;
-                    sincosf(feat[f * 64 + s], &sv, &cv);
+                    const float fv = feat[f * 64 + s];
+                    float sv = 0.f, cv = 1.f;
                     for (int o = 0; o < fpe; ++o) {
+                        // every doubling doubles the angle's rounding error: a fresh sincosf every kGenPeRestart octaves (fea_pe goes
+                        // up to 16 here; fifteen doublings put ~3e-3 on the top octave)
+                        if (o % kGenPeRestart == 0) sincosf(fv * (float)(1 << o), &sv, &cv);
+                        else { const float s2 = 2.f * sv * cv, c2 = cv * cv - sv * sv; sv = s2; cv = c2; }
                         if (js + o >= c0 && js + o < c1) Hb[(js + o - c0) * 64 + s] = sv;
                         if (jc + o >= c0 && jc + o < c1) Hb[(jc + o - c0) * 64 + s] = cv;
-                        const float s2 = 2.f * sv * cv, c2 = cv * cv - sv * sv;
-                        sv = s2; cv = c2;
                     }
                 }
                 __syncthreads();
