@@ -386,6 +386,46 @@ int t2n_format_views(const float* images, const float* depths, const void* masks
                      float* all_rgbs, float* all_depths, int64_t capacity_rows, int64_t* record, void* workspace,
                      size_t workspace_bytes, t2n_stream stream);
 
+/* ---- the inpaint-view builder: everything render_warping_inapinting does before the inpainter (text2nerf_main.py:99-184) without a
+ * host hop. The renders are t2n_render_forward and the hole filling t2n_dibr_filter_mask2; the three calls below are the rest.
+ * t2n_sparse_bilateral_filtering_views = the per-view filter call of the render loop (text2nerf_main.py:115-119) for a STACK of V
+ * views with one schedule: depth [V,H,W], image [V,H,W,3] -> photo_out [V,H,W,3] (vis_photos[-1]) and depth_out [V,H,W]
+ * (vis_depths[-1], the depth before the last pass). The view is a grid axis of the kernels of t2n_sparse_bilateral_filtering: a pass
+ * is one launch set for all views, and every view is bit-equal to a single-image call. Workspace:
+ * t2n_image_filter_views_workspace_bytes(H, W, V) (0 = bad argument). Limits of the stack call, which the single-image call does
+ * not have: V <= 4096 (four channels per view on one grid axis) and H * W <= 2^26 pixels per view; beyond either the call returns
+ * T2N_ERR_INVALID. */
+size_t t2n_image_filter_views_workspace_bytes(int H, int W, int V);
+int t2n_sparse_bilateral_filtering_views(const float* depth, const float* image, int V, int H, int W, const int* filter_sizes_host,
+                                         int num_iter, float depth_threshold, float* photo_out, float* depth_out, void* workspace,
+                                         size_t workspace_bytes, t2n_stream stream);
+/* t2n_warp_sources = bilinear_splat_warping_multiview (utils.py:83-119 over Warper.forward_warp, scripts/Warper.py:21-186): V source
+ * views forward-warped into ONE target, the earliest source that lands on a pixel wins, then white where nothing landed and / 255 —
+ * the work of V t2n_warp_view calls and t2n_warp_finish as one launch set (memset, log-depth maxima, splat, resolve) per chunk of up
+ * to 8 sources, each source on its own planar canvas (the arithmetic of t2n_warp_views per source). Device inputs: rgb [V,H,W,3] fp32
+ * in [0,1] (truncated to uint8 levels like the reference), depth [V,H,W] fp32, mask1 [V,H,W] u8 or NULL (0 / non-zero: scales the
+ * weights of its source). Host inputs (row-major doubles): Ki9 = inv(K), T12 [V][12] = first three rows of inv(pose_tar)
+ * inv(inv(pose[v])), K9 = K. Device outputs: image_out [H,W,3] fp32, mask_out [H,W] int64, depth_out [H,W] fp64 (0 where nothing
+ * landed). Masks are exact; image and depth sum fp64 atomics in arrival order, as t2n_warp_view does. Workspace:
+ * t2n_warp_sources_workspace_bytes(H, W, V), which grows with V up to the 8-source chunk and not beyond (0 = bad argument).
+ * T2N_ERR_INVALID: NULL / non-positive argument; T2N_ERR_WORKSPACE: workspace too small. */
+size_t t2n_warp_sources_workspace_bytes(int H, int W, int V);
+int t2n_warp_sources(const float* rgb, const float* depth, const uint8_t* mask1, int H, int W, int V, const double* Ki9_host,
+                     const double* T12_host, const double* K9_host, float* image_out, int64_t* mask_out, double* depth_out,
+                     void* workspace, size_t workspace_bytes, t2n_stream stream);
+/* t2n_inpaint_pack = the arrays the driver builds around the inpainter (text2nerf_main.py:138-184, update_known_views=False) in one
+ * elementwise launch, from the (hole-filled) warp warp_image [H,W,3] fp32, its known map `known` [H,W] int32 (0 / non-zero), the
+ * target render rgb_render [H,W,3] fp32 (clamped to [0,1] here) and depth_render [H,W] fp32:
+ *   warp_u8 [H,W,3]        uint8(warp_image * 255) * mask  (:138,156-157; a float32 product, truncated)
+ *   map_filt [H,W] int64   the mask as 0 / 1;  mask_image, mask_inv [H,W] u8 = mask * 255, (1 - mask) * 255  (:158-159)
+ *   mask_ex [H,W,3] int64  the mask on three channels  (:154)
+ *   rgb_u8 [H,W,3]         uint8(clamp(rgb_render, 0, 1) * 255)  (:169-170);  rgb_masked_u8 = rgb_u8 * mask + 255 (1 - mask)  (:174-177)
+ *   depth_masked [H,W] fp64 = depth_render * mask  (:171)
+ * Exact. T2N_ERR_INVALID: NULL / non-positive argument. */
+int t2n_inpaint_pack(const float* warp_image, const int32_t* known, const float* rgb_render, const float* depth_render, int H, int W,
+                     uint8_t* warp_u8, int64_t* map_filt, uint8_t* mask_image, uint8_t* mask_inv, int64_t* mask_ex, uint8_t* rgb_u8,
+                     uint8_t* rgb_masked_u8, double* depth_masked, t2n_stream stream);
+
 /* ---- a-15: backward of the render call w.r.t. all field parameters (what autograd derives in the reference,
  * text2nerf_main.py:589; coordinates are detached there, models/tensoRF.py:208-210,226-228, so no ray gradients exist).
  * Protocol: (1) forward with T2N_FLAG_KEEP_CTX as ONE launch (workspace >= t2n_render_workspace_bytes_ctx), weights and

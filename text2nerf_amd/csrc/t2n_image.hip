@@ -5,22 +5,32 @@
 //                                reference (seconds per view)
 //   forward warp + merge         scripts/Warper.py:21-186 (compute_transformed_points, bilinear_splatting: numpy add.at in
 //                                fp64), utils.py:83-119 (bilinear_splat_warping_multiview)
+//   hole filling                 utils.py:393-409 (dibr_filter_mask2), :345-392 (dibr_filter_mask)
+//   the inpainter's inputs       text2nerf_main.py:138-184: uint8 image / mask arithmetic as one elementwise kernel
 #include "t2n_internal.h"
 
 namespace t2n {
 
 // ---- depth-aware median filter ------------------------------------------------------------------------------------------------
-// planar state [4][H][W]: channel 0 = depth, 1..3 = r, g, b
+// planar state [V][4][H][W]: channel 0 = depth, 1..3 = r, g, b. The view is a grid axis (blockIdx.y; one view for the single-image
+// entry point), so a pass over a stack of views is one launch set
 __global__ __launch_bounds__(256) void k_img_pack(const float* __restrict__ depth, const float* __restrict__ image, int n, float* st) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
+    const size_t v = blockIdx.y;
+    depth += v * n; image += v * 3 * n; st += v * 4 * n;
     st[t] = depth[t];
     st[n + t] = image[t * 3]; st[2 * n + t] = image[t * 3 + 1]; st[3 * n + t] = image[t * 3 + 2];
 }
-__global__ __launch_bounds__(256) void k_img_unpack(const float* __restrict__ st, int n, float* image) {
+// prev / depth_keep (both or neither): the state one pass earlier and where its depth channel goes (save_depths[-1])
+__global__ __launch_bounds__(256) void k_img_unpack(const float* __restrict__ st, const float* __restrict__ prev, int n, float* image,
+                                                    float* depth_keep) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= n) return;
+    const size_t v = blockIdx.y;
+    st += v * 4 * n; image += v * 3 * n;
     image[t * 3] = st[n + t]; image[t * 3 + 1] = st[2 * n + t]; image[t * 3 + 2] = st[3 * n + t];
+    if (depth_keep) depth_keep[v * n + t] = prev[v * 4 * n + t];
 }
 
 // bilateral_filtering.py:17-20,78-97,115-118: |1/d - 1/d_neighbour| > thr for any 4-neighbour (interior pixels only), or
@@ -29,6 +39,8 @@ __global__ __launch_bounds__(256) void k_img_disc(const float* __restrict__ vis,
                                                   unsigned char* disc) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= H * W) return;
+    const size_t view = blockIdx.y;                        // vis is the depth channel of the view's planar state
+    vis += view * 4 * H * W; orig += view * H * W; disc += view * H * W;
     const int y = t / W, x = t - y * W;
     bool d = false;
     if (y >= 1 && y <= H - 2 && x >= 1 && x <= W - 2) {
@@ -40,7 +52,7 @@ __global__ __launch_bounds__(256) void k_img_disc(const float* __restrict__ vis,
     disc[t] = d ? 1 : 0;
 }
 
-// One pass of the filter on all four channels (blockIdx.z). 16x16 pixels per workgroup, window <= 7: the (16+6)^2 halo tile
+// One pass of the filter on all four channels of every view (blockIdx.z = 4 view + channel). 16x16 pixels per workgroup, window <= 7: the (16+6)^2 halo tile
 // of values and flags is staged in LDS. The border ring of the image is replaced by its inner neighbours before the
 // edge padding (:149-154), i.e. every read is at (clamp(y,1,H-2), clamp(x,1,W-2)). Pixels whose window holds no
 // discontinuity keep the (ring-replaced) value; the others take the t-th smallest of the n non-discontinuity values,
@@ -51,6 +63,7 @@ __global__ __launch_bounds__(256) void k_img_median(const float* __restrict__ in
     __shared__ float sv[kMedS * kMedS];
     __shared__ unsigned char sd[kMedS * kMedS];
     const size_t plane = (size_t)blockIdx.z * H * W;
+    disc += (size_t)(blockIdx.z >> 2) * H * W;
     const int bx = blockIdx.x * kMedT, by = blockIdx.y * kMedT;
     for (int i = threadIdx.x; i < kMedS * kMedS; i += 256) {
         const int ly = i / kMedS, lx = i - ly * kMedS;
@@ -305,11 +318,50 @@ __global__ __launch_bounds__(1024) void k_fill_mask1_tail(float* image, int* kno
 using namespace t2n;
 
 static size_t al256i(size_t x) { return (x + 255) / 256 * 256; }
+constexpr int kFilterMaxViews = 4096;     // 4 channels per view on grid axis z (< 65536)
 
 extern "C" size_t t2n_image_filter_workspace_bytes(int H, int W) {
     if (H < 3 || W < 3) return 0;
     const size_t n = (size_t)H * W;
     return al256i(n * 16) * 2 + al256i(n);
+}
+
+extern "C" size_t t2n_image_filter_views_workspace_bytes(int H, int W, int V) {
+    if (H < 3 || W < 3 || V < 1 || V > kFilterMaxViews || (long long)H * W > (1ll << 26)) return 0;
+    const size_t n = (size_t)H * W * V;
+    return al256i(n * 16) * 2 + al256i(n);
+}
+
+// The passes over V views (the single-image entry point: V = 1). The two planar states and the discontinuity maps of all views are
+// contiguous in the workspace; per pass one k_img_disc and one k_img_median launch cover every view.
+// states_out [num_iter][H][W] (single image: save_depths) or keep_out [V][H][W] (stack: save_depths[-1]), the other NULL.
+static int filter_views(const char* who, const float* depth, const float* image, int V, int H, int W, const int* filter_sizes_host,
+                        int num_iter, float depth_threshold, float* photo_out, float* states_out, float* keep_out, void* workspace,
+                        hipStream_t s) {
+    for (int i = 0; i < num_iter; ++i)
+        if (filter_sizes_host[i] < 1 || filter_sizes_host[i] > 2 * kMedHalo + 1 || !(filter_sizes_host[i] & 1)) {
+            set_error("%s: window %d not in {1,3,5,7}", who, filter_sizes_host[i]);
+            return T2N_ERR_UNSUPPORTED;
+        }
+    const int n = H * W;
+    const size_t nv = (size_t)n * V;
+    float* A = (float*)workspace;
+    float* B = (float*)((char*)workspace + al256i(nv * 16));
+    unsigned char* disc = (unsigned char*)workspace + 2 * al256i(nv * 16);
+    const dim3 g1((unsigned)((n + 255) / 256), (unsigned)V);
+    hipLaunchKernelGGL(k_img_pack, g1, dim3(256), 0, s, depth, image, n, A);
+    for (int i = 0; i < num_iter; ++i) {
+        // save_depths[i] = the depth BEFORE pass i (the image list aliases ONE array, filtered in place: only its final state exists)
+        if (states_out) T2N_HIP(hipMemcpyAsync(states_out + (size_t)i * n, A, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_img_disc, g1, dim3(256), 0, s, (const float*)A, depth, H, W, depth_threshold, disc);
+        hipLaunchKernelGGL(k_img_median, dim3((unsigned)((W + kMedT - 1) / kMedT), (unsigned)((H + kMedT - 1) / kMedT), 4u * (unsigned)V),
+                           dim3(256), 0, s, (const float*)A, (const unsigned char*)disc, H, W, filter_sizes_host[i], B);
+        float* tmp = A; A = B; B = tmp;
+    }
+    // B is the state before the last pass: its depth channel is save_depths[-1]
+    hipLaunchKernelGGL(k_img_unpack, g1, dim3(256), 0, s, (const float*)A, (const float*)B, n, photo_out, keep_out);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
 }
 
 extern "C" int t2n_sparse_bilateral_filtering(const float* depth, const float* image, int H, int W, const int* filter_sizes_host, int num_iter,
@@ -319,30 +371,25 @@ extern "C" int t2n_sparse_bilateral_filtering(const float* depth, const float* i
         set_error("t2n_sparse_bilateral_filtering: bad argument");
         return T2N_ERR_INVALID;
     }
-    for (int i = 0; i < num_iter; ++i)
-        if (filter_sizes_host[i] < 1 || filter_sizes_host[i] > 2 * kMedHalo + 1 || !(filter_sizes_host[i] & 1)) {
-            set_error("t2n_sparse_bilateral_filtering: window %d not in {1,3,5,7}", filter_sizes_host[i]);
-            return T2N_ERR_UNSUPPORTED;
-        }
     if (workspace_bytes < t2n_image_filter_workspace_bytes(H, W)) { set_error("t2n_sparse_bilateral_filtering: workspace too small"); return T2N_ERR_WORKSPACE; }
-    hipStream_t s = (hipStream_t)stream;
-    const int n = H * W;
-    float* A = (float*)workspace;
-    float* B = (float*)((char*)workspace + al256i((size_t)n * 16));
-    unsigned char* disc = (unsigned char*)workspace + 2 * al256i((size_t)n * 16);
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_img_pack, dim3(nb), dim3(256), 0, s, depth, image, n, A);
-    for (int i = 0; i < num_iter; ++i) {
-        // save_depths[i] = the depth BEFORE pass i (the image list aliases ONE array, filtered in place: only its final state exists)
-        T2N_HIP(hipMemcpyAsync(depth_out + (size_t)i * n, A, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
-        hipLaunchKernelGGL(k_img_disc, dim3(nb), dim3(256), 0, s, (const float*)A, depth, H, W, depth_threshold, disc);
-        hipLaunchKernelGGL(k_img_median, dim3((unsigned)((W + kMedT - 1) / kMedT), (unsigned)((H + kMedT - 1) / kMedT), 4), dim3(256), 0, s,
-                           (const float*)A, (const unsigned char*)disc, H, W, filter_sizes_host[i], B);
-        float* tmp = A; A = B; B = tmp;
+    return filter_views("t2n_sparse_bilateral_filtering", depth, image, 1, H, W, filter_sizes_host, num_iter, depth_threshold, photo_out,
+                        depth_out, nullptr, workspace, (hipStream_t)stream);
+}
+
+extern "C" int t2n_sparse_bilateral_filtering_views(const float* depth, const float* image, int V, int H, int W, const int* filter_sizes_host,
+                                                    int num_iter, float depth_threshold, float* photo_out, float* depth_out, void* workspace,
+                                                    size_t workspace_bytes, t2n_stream stream) {
+    if (!depth || !image || !filter_sizes_host || !photo_out || !depth_out || !workspace || H < 3 || W < 3 || num_iter < 1 || V < 1 ||
+        V > kFilterMaxViews || (long long)H * W > (1ll << 26)) {
+        set_error("t2n_sparse_bilateral_filtering_views: bad argument");
+        return T2N_ERR_INVALID;
     }
-    hipLaunchKernelGGL(k_img_unpack, dim3(nb), dim3(256), 0, s, (const float*)A, n, photo_out);
-    T2N_HIP(hipGetLastError());
-    return T2N_OK;
+    if (workspace_bytes < t2n_image_filter_views_workspace_bytes(H, W, V)) {
+        set_error("t2n_sparse_bilateral_filtering_views: workspace too small");
+        return T2N_ERR_WORKSPACE;
+    }
+    return filter_views("t2n_sparse_bilateral_filtering_views", depth, image, V, H, W, filter_sizes_host, num_iter, depth_threshold,
+                        photo_out, nullptr, depth_out, workspace, (hipStream_t)stream);
 }
 
 extern "C" size_t t2n_warp_workspace_bytes(int H, int W) {
@@ -399,6 +446,51 @@ extern "C" int t2n_dibr_filter_mask(float* image, int32_t* known, int H, int W, 
     const int rc = t2n_dibr_filter_mask2(image, known, nullptr, H, W, 0.6f, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_fill_mask1_tail, dim3(1), dim3(1024), 0, (hipStream_t)stream, image, known, H, W);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
+// ---- the inpainter's inputs (text2nerf_main.py:138-184, the update_known_views=False branch) ---------------------------------------
+// One thread per pixel: numpy's float32 multiply by 255 followed by the truncating cast (the library is built without contraction),
+// the uint8 products with the 0 / 1 mask, and the float32 x int64 -> float64 product of the rendered depth.
+namespace t2n {
+__device__ __forceinline__ unsigned char u8_trunc(float x01) { return (unsigned char)(int)(x01 * 255.f); }
+__global__ __launch_bounds__(256) void k_inpaint_pack(const float* __restrict__ warp, const int* __restrict__ known,
+                                                      const float* __restrict__ rgb, const float* __restrict__ depth, int n,
+                                                      unsigned char* warp_u8, long long* map_filt, unsigned char* mask_image,
+                                                      unsigned char* mask_inv, long long* mask_ex, unsigned char* rgb_u8,
+                                                      unsigned char* rgb_masked_u8, double* depth_masked) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int m = known[t] != 0 ? 1 : 0;
+    map_filt[t] = m;
+    mask_image[t] = (unsigned char)(m * 255);
+    mask_inv[t] = (unsigned char)((1 - m) * 255);
+    depth_masked[t] = (double)depth[t] * (double)m;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const size_t o = (size_t)t * 3 + k;
+        warp_u8[o] = (unsigned char)(u8_trunc(warp[o]) * m);
+        mask_ex[o] = m;
+        const unsigned char r = u8_trunc(fminf(fmaxf(rgb[o], 0.f), 1.f));
+        rgb_u8[o] = r;
+        rgb_masked_u8[o] = m ? r : (unsigned char)255;
+    }
+}
+}  // namespace t2n
+
+extern "C" int t2n_inpaint_pack(const float* warp_image, const int32_t* known, const float* rgb_render, const float* depth_render, int H,
+                                int W, uint8_t* warp_u8, int64_t* map_filt, uint8_t* mask_image, uint8_t* mask_inv, int64_t* mask_ex,
+                                uint8_t* rgb_u8, uint8_t* rgb_masked_u8, double* depth_masked, t2n_stream stream) {
+    if (!warp_image || !known || !rgb_render || !depth_render || !warp_u8 || !map_filt || !mask_image || !mask_inv || !mask_ex || !rgb_u8 ||
+        !rgb_masked_u8 || !depth_masked || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) {
+        set_error("t2n_inpaint_pack: bad argument");
+        return T2N_ERR_INVALID;
+    }
+    const int n = H * W;
+    hipLaunchKernelGGL(k_inpaint_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, warp_image, known, rgb_render,
+                       depth_render, n, warp_u8, (long long*)map_filt, mask_image, mask_inv, (long long*)mask_ex, rgb_u8, rgb_masked_u8,
+                       depth_masked);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
 }

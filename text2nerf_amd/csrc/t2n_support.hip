@@ -5,6 +5,9 @@
 //                                is that of k_warp_points / k_warp_splat / k_warp_resolve (t2n_image.hip) in fp64; here the view
 //                                index is a grid axis, the V transforms travel by value, the projection is recomputed by the splat
 //                                instead of stored, and resolve + white background + / 255 are one kernel.
+//   many-to-one forward warp     utils.py:83-119 (bilinear_splat_warping_multiview), for the inpaint-view builder (text2nerf_main.py:129):
+//                                V source frames splatted by the same two kernels, the SOURCE on the grid axis and each on its own
+//                                canvas, then one resolve per target pixel in which the earliest source wins.
 //   formatter                    dataLoader/scene_gen.py:31-98 (produce_formatted_data): rays of N poses and the `mask > 0.5` row
 //                                selection in the reference's order (view-major, raster order inside a view): count -> exclusive
 //                                scan -> scatter.
@@ -31,13 +34,16 @@ __device__ __forceinline__ void sv_project(const double* Ki, const double* T, co
     u = p[0] / p[2]; v = p[1] / p[2]; z = p[2];
 }
 
-// Warper.py:141-143: max over the frame of log(1 + clip(z, 0, 1000)), one value PER TARGET VIEW (blockIdx.y). Few workgroups per
+// Both warps below put the view on blockIdx.y with its transform in M.T[view]: one source to V targets (src_stride = 0: every view
+// reads the same frame) and V sources to one target (src_stride = H W: view v reads frame v of the stacks; no mask_aux).
+// Warper.py:141-143: max over the frame of log(1 + clip(z, 0, 1000)), one value PER VIEW (blockIdx.y). Few workgroups per
 // view, each striding over the frame and posting ONE atomic: thousands of atomics on one word serialise (~90 per microsecond).
 constexpr int kSvLogmaxBlocks = 128;
-__global__ __launch_bounds__(256) void k_sv_logmax(const float* __restrict__ depth, int H, int W, const SvMats M,
+__global__ __launch_bounds__(256) void k_sv_logmax(const float* __restrict__ depth, size_t src_stride, int H, int W, const SvMats M,
                                                    unsigned long long* logmax_bits) {
     __shared__ double sm[4];
     const int view = blockIdx.y, n = H * W;
+    depth += (size_t)view * src_stride;
     double lg = 0.0;
     for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256) {
         const int yi = t / W, xi = t - yi * W;
@@ -63,10 +69,12 @@ __global__ __launch_bounds__(256) void k_sv_logmax(const float* __restrict__ dep
 // mask1 = mask_aux, so that `aux weight > 0` is the coverage of a second, masked warp decided as the reference decides it.
 __global__ __launch_bounds__(256) void k_sv_splat(const float* __restrict__ rgb, const float* __restrict__ depth,
                                                   const unsigned char* __restrict__ mask1, const unsigned char* __restrict__ mask_aux,
-                                                  int H, int W, const SvMats M, const unsigned long long* __restrict__ logmax_bits,
-                                                  double* canvas, size_t canvas_stride) {
+                                                  size_t src_stride, int H, int W, const SvMats M,
+                                                  const unsigned long long* __restrict__ logmax_bits, double* canvas, size_t canvas_stride) {
     const int t = blockIdx.x * 256 + threadIdx.x, view = blockIdx.y;
     if (t >= H * W) return;
+    rgb += (size_t)view * src_stride * 3; depth += (size_t)view * src_stride;
+    if (mask1) mask1 += (size_t)view * src_stride;
     const int yi = t / W, xi = t - yi * W;
     double u, v, z;
     sv_project(M.Ki, M.T[view], M.K2, xi, yi, (double)depth[t], u, v, z);
@@ -132,6 +140,52 @@ __global__ __launch_bounds__(256) void k_sv_resolve(const double* __restrict__ c
     if (depth) depth[o] = d;
     if (depth32) depth32[o] = (float)d;
     if (aux) aux[o] = (nch > 5 && c[5 * plane] > 0.0) ? 1 : 0;
+}
+
+// ---- many-to-one forward warp: utils.py:83-119 (bilinear_splat_warping_multiview) -----------------------------------------------------
+// Every source of the chunk has been splatted into its own planar canvas (k_sv_logmax / k_sv_splat with src_stride = H W). Per
+// target pixel: the first source, in ascending order, whose weight is > 0 wins (utils.py:106-113); pixels an earlier chunk filled
+// are left alone. `filled` / `image_u8` carry the state between chunks (untouched when one chunk holds every source), `depth` is
+// the output itself. The last chunk writes the white background, / 255 -> fp32 and the int64 mask (utils.py:115-118).
+__global__ __launch_bounds__(256) void k_ms_resolve(const double* __restrict__ canvas, size_t canvas_stride, int nv, int H, int W,
+                                                    int first, int last, unsigned char* filled, unsigned char* image_u8,
+                                                    float* __restrict__ image, long long* __restrict__ mask, double* __restrict__ depth) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= H * W) return;
+    const int y = t / W, x = t - y * W;
+    const size_t plane = (size_t)(H + 2) * (W + 2);
+    const double* c0 = canvas + (size_t)(y + 1) * (W + 2) + (x + 1);
+    bool known = first ? false : filled[t] != 0;
+    bool fresh = false;
+    int level[3] = {255, 255, 255};
+    if (known && last) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) level[k] = image_u8[(size_t)t * 3 + k];
+    }
+    if (!known) {
+        for (int v = 0; v < nv; ++v) {
+            const double* c = c0 + (size_t)v * canvas_stride;
+            const double w = c[4 * plane];
+            if (!(w > 0.0)) continue;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) level[k] = (int)(unsigned char)(int)rint(fmin(fmax(c[k * plane] / w, 0.0), 255.0));
+            depth[t] = c[3 * plane] / w;
+            known = fresh = true;
+            break;
+        }
+    }
+    if (first && !known) depth[t] = 0.0;
+    if (!last) {
+        if (first || fresh) {
+            filled[t] = known ? 1 : 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) image_u8[(size_t)t * 3 + k] = (unsigned char)level[k];
+        }
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) image[(size_t)t * 3 + k] = (float)((double)level[k] / 255.0);
+    mask[t] = known ? 1 : 0;
 }
 
 // ---- formatter --------------------------------------------------------------------------------------------------------------------
@@ -271,12 +325,56 @@ extern "C" int t2n_warp_views(const float* rgb, const float* depth, const uint8_
         unsigned long long* logmax = (unsigned long long*)((char*)workspace + cbytes * nv);
         T2N_HIP(hipMemsetAsync(workspace, 0, cbytes * nv + 256, s));
         const size_t o = (size_t)v0 * n;
-        hipLaunchKernelGGL(k_sv_logmax, dim3(nb < (unsigned)kSvLogmaxBlocks ? nb : (unsigned)kSvLogmaxBlocks, (unsigned)nv), dim3(256), 0, s, depth, H, W, M, logmax);
-        hipLaunchKernelGGL(k_sv_splat, dim3(nb, (unsigned)nv), dim3(256), 0, s, rgb, depth, mask1, mask_aux, H, W, M,
+        hipLaunchKernelGGL(k_sv_logmax, dim3(nb < (unsigned)kSvLogmaxBlocks ? nb : (unsigned)kSvLogmaxBlocks, (unsigned)nv), dim3(256), 0, s, depth, (size_t)0, H, W, M, logmax);
+        hipLaunchKernelGGL(k_sv_splat, dim3(nb, (unsigned)nv), dim3(256), 0, s, rgb, depth, mask1, mask_aux, (size_t)0, H, W, M,
                            (const unsigned long long*)logmax, canvas, cstride);
         hipLaunchKernelGGL(k_sv_resolve, dim3(nb, (unsigned)nv), dim3(256), 0, s, (const double*)canvas, cstride, nch, H, W,
                            image_out + o * 3, (long long*)(mask_out ? mask_out + o : nullptr), depth_out ? depth_out + o : nullptr,
                            depth32_out ? depth32_out + o : nullptr, (long long*)(aux_out ? aux_out + o : nullptr));
+    }
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
+static size_t ms_canvas_bytes(int H, int W) { return al256s((size_t)(H + 2) * (W + 2) * 5 * sizeof(double)); }
+
+extern "C" size_t t2n_warp_sources_workspace_bytes(int H, int W, int V) {
+    if (H < 1 || W < 1 || V < 1 || (long long)H * W > (1ll << 30)) return 0;
+    const size_t n = (size_t)H * W;      // canvases of one chunk | per-source log-depth maxima | filled | image_u8
+    return ms_canvas_bytes(H, W) * (size_t)(V < kSvViews ? V : kSvViews) + 256 + al256s(n) + al256s(n * 3);
+}
+
+extern "C" int t2n_warp_sources(const float* rgb, const float* depth, const uint8_t* mask1, int H, int W, int V, const double* Ki9_host,
+                                const double* T12_host, const double* K9_host, float* image_out, int64_t* mask_out, double* depth_out,
+                                void* workspace, size_t workspace_bytes, t2n_stream stream) {
+    if (!rgb || !depth || !Ki9_host || !T12_host || !K9_host || !image_out || !mask_out || !depth_out || !workspace || H < 1 || W < 1 ||
+        V < 1 || (long long)H * W > (1ll << 30)) {
+        set_error("t2n_warp_sources: bad argument");
+        return T2N_ERR_INVALID;
+    }
+    if (workspace_bytes < t2n_warp_sources_workspace_bytes(H, W, V)) { set_error("t2n_warp_sources: workspace too small"); return T2N_ERR_WORKSPACE; }
+    hipStream_t s = (hipStream_t)stream;
+    const int n = H * W, chunk = V < kSvViews ? V : kSvViews;
+    const size_t cbytes = ms_canvas_bytes(H, W), cstride = cbytes / sizeof(double);
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    double* canvas = (double*)workspace;
+    unsigned long long* logmax = (unsigned long long*)((char*)workspace + cbytes * chunk);
+    unsigned char* filled = (unsigned char*)workspace + cbytes * chunk + 256;
+    unsigned char* image_u8 = filled + al256s((size_t)n);
+    SvMats M;
+    memcpy(M.Ki, Ki9_host, sizeof(M.Ki)); memcpy(M.K2, K9_host, sizeof(M.K2));
+    for (int v0 = 0; v0 < V; v0 += kSvViews) {
+        const int nv = V - v0 < kSvViews ? V - v0 : kSvViews;
+        memset(M.T, 0, sizeof(M.T));
+        memcpy(M.T, T12_host + (size_t)v0 * 12, (size_t)nv * 12 * sizeof(double));
+        T2N_HIP(hipMemsetAsync(workspace, 0, cbytes * chunk + 256, s));      // canvases and maxima (contiguous)
+        const size_t o = (size_t)v0 * n;
+        hipLaunchKernelGGL(k_sv_logmax, dim3(nb < (unsigned)kSvLogmaxBlocks ? nb : (unsigned)kSvLogmaxBlocks, (unsigned)nv), dim3(256), 0, s,
+                           depth + o, (size_t)n, H, W, M, logmax);
+        hipLaunchKernelGGL(k_sv_splat, dim3(nb, (unsigned)nv), dim3(256), 0, s, rgb + o * 3, depth + o, mask1 ? mask1 + o : nullptr,
+                           (const unsigned char*)nullptr, (size_t)n, H, W, M, (const unsigned long long*)logmax, canvas, cstride);
+        hipLaunchKernelGGL(k_ms_resolve, dim3(nb), dim3(256), 0, s, (const double*)canvas, cstride, nv, H, W, v0 == 0 ? 1 : 0,
+                           v0 + nv == V ? 1 : 0, filled, image_u8, image_out, (long long*)mask_out, depth_out);
     }
     T2N_HIP(hipGetLastError());
     return T2N_OK;

@@ -12,11 +12,18 @@ and the steps after inpainting that turn one inpainted RGB-D view into training 
 * ``produce_formatted_data`` — dataLoader/scene_gen.py:31-98: rays per pose and the ``mask > 0.5`` row selection
 * ``build_support_set`` — text2nerf_main.py:380-392 / scene_gen.py:305-316 as one device-resident call
 
+and everything before inpainting as one device-resident call (csrc/t2n_image.hip, csrc/t2n_support.hip):
+
+* ``build_inpaint_view`` — text2nerf_main.py:99-184: known views rendered, filtered as a stack
+  (``sparse_bilateral_filtering_views``), warped into the new pose in one launch set per 8 sources (``warp_sources``), hole-filled,
+  the new pose rendered, and the inpainter's uint8 image and masks packed (``pack_inpaint_inputs``)
+
 Inputs may be numpy arrays (as in the driver) or torch tensors; numpy in -> numpy out. No CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import Any, NamedTuple
 
 import numpy as np
 import torch
@@ -387,3 +394,262 @@ def build_support_set(img_new, depth_new, mask_inpainted, poses_support, intrins
                     None if maux is None else masks[1:])
     rays_split, rows, rgbs, deps, _ = _format_views(lib, dev, images, depths, masks, c2w, N, H, W, intrinsic, True)
     return rows, rgbs, deps, rays_split, images, depths, torch.from_numpy(p44).to(dev)
+
+
+# ---- before inpainting: known views -> the warped, filled and packed new view ------------------------------------------------------------
+def _filter_schedule(filter_size, num_iter):
+    sizes = [int(filter_size[i]) if isinstance(filter_size, (list, tuple)) else int(filter_size) for i in range(num_iter)]
+    return (C.c_int * num_iter)(*sizes)
+
+
+def _is_cuda(x):
+    if isinstance(x, (list, tuple)):
+        return any(_is_cuda(a) for a in x)
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _first_device(*xs):
+    for x in xs:
+        for a in (x if isinstance(x, (list, tuple)) else (x,)):
+            if isinstance(a, torch.Tensor) and a.is_cuda:
+                return a.device
+    return None
+
+
+def _view_stack(x, dev, dtype, what, shape):
+    """A list of frames or a stacked array as one contiguous device tensor of `shape`."""
+    t = _to(_stack(x), dev, dtype)
+    if tuple(t.shape) != tuple(shape):
+        raise T2NError(f"{what}: shape {tuple(t.shape)} does not match {tuple(shape)}")
+    return t
+
+
+def _filter_views(lib, dev, d, im, filter_size, depth_threshold, num_iter):
+    """t2n_sparse_bilateral_filtering_views on the current stream of `dev`: device stacks in, (photo, depth kept) out."""
+    V, H, W = d.shape
+    photo, keep = torch.empty_like(im), torch.empty_like(d)
+    ws = torch.empty(int(lib.t2n_image_filter_views_workspace_bytes(H, W, V)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_sparse_bilateral_filtering_views(_lib.ptr(d), _lib.ptr(im), V, H, W, _filter_schedule(filter_size, num_iter),
+                                                            num_iter, float(depth_threshold), _lib.ptr(photo), _lib.ptr(keep), _lib.ptr(ws),
+                                                            ws.numel(), _lib.current_stream_ptr(dev)),
+                   "t2n_sparse_bilateral_filtering_views")
+    return photo, keep
+
+
+def sparse_bilateral_filtering_views(depths, images, filter_size=[7, 7, 5, 5, 5], depth_threshold=0.04, num_iter=5, device=None):
+    """``sparse_bilateral_filtering`` for a stack of views with one schedule, one launch set per pass for all of them: ``depths``
+    [V,H,W], ``images`` [V,H,W,3] (stacked arrays or lists of frames) -> ``(photos [V,H,W,3], depths [V,H,W])``, per view what the
+    driver keeps of the single-image call (text2nerf_main.py:118-119): ``vis_photos[-1]`` and ``vis_depths[-1]``, bit-equal to it."""
+    lib = _lib.load()
+    as_numpy = not _is_cuda(depths)
+    dev = _dev(device if device is not None else _first_device(depths))
+    d = _to(_stack(depths), dev, torch.float32)
+    if d.dim() != 3:
+        raise T2NError(f"sparse_bilateral_filtering_views: depths must be [V,H,W], got {tuple(d.shape)}")
+    im = _view_stack(images, dev, torch.float32, "sparse_bilateral_filtering_views: images", tuple(d.shape) + (3,))
+    photo, keep = _filter_views(lib, dev, d, im, filter_size, depth_threshold, num_iter)
+    return (photo.cpu().numpy(), keep.cpu().numpy()) if as_numpy else (photo, keep)
+
+
+def _source_mats(poses, pose_tar, intrinsic):
+    """The host matrices of bilinear_splat_warping_multiview (utils.py:88-100) and Warper.compute_transformed_points (Warper.py:75,84),
+    in numpy and the inputs' dtype like the reference: inv(K), the first three rows of inv(pose_tar) @ inv(inv(poses[v])) per source, K."""
+    T2 = np.linalg.inv(_host(pose_tar))
+    K = np.eye(3).astype(np.float32)
+    K[0, 0], K[1, 1], K[0, 2], K[1, 2] = intrinsic[0], intrinsic[1], intrinsic[2], intrinsic[3]
+    T = [np.matmul(T2, np.linalg.inv(np.linalg.inv(_host(p)))) for p in poses]
+    T12 = np.stack([np.asarray(t, np.float64)[:3, :4] for t in T]).reshape(-1)
+    d9 = lambda m: (C.c_double * 9)(*np.asarray(m, np.float64).reshape(-1)[:9])       # noqa: E731
+    return d9(np.linalg.inv(K)), (C.c_double * T12.size)(*T12), d9(K)
+
+
+def _warp_sources(lib, dev, rgb, depth, m1, mats):
+    """t2n_warp_sources on the current stream of `dev`: device stacks in, (mask int64, image fp32, depth fp64) out."""
+    V, H, W = depth.shape
+    Ki, T12, K = mats
+    image = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    mask = torch.empty(H, W, dtype=torch.int64, device=dev)
+    dep = torch.empty(H, W, dtype=torch.float64, device=dev)
+    ws = torch.empty(int(lib.t2n_warp_sources_workspace_bytes(H, W, V)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_warp_sources(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(m1), H, W, V, Ki, T12, K, _lib.ptr(image), _lib.ptr(mask),
+                                        _lib.ptr(dep), _lib.ptr(ws), ws.numel(), _lib.current_stream_ptr(dev)), "t2n_warp_sources")
+    return mask, image, dep
+
+
+def warp_sources(rgbs, depths, poses, pose_tar, H, W, intrinsic, masks=None, device=None):
+    """``bilinear_splat_warping_multiview`` (utils.py:83, same arguments and return) with all sources in one launch set per chunk of 8
+    instead of four launches per source: ``rgbs`` [V,H,W,3] / ``depths`` [V,H,W] (stacked or lists), ``poses[:V]`` their
+    camera-to-world matrices, ``masks`` [V,H,W] boolean or 0/1 -> ``(mask_final [H,W] int64, output_image [H,W,3] fp32, output_depth
+    [H,W] fp64)``; earlier sources win."""
+    lib = _lib.load()
+    as_numpy = not _is_cuda(rgbs)
+    dev = _dev(device if device is not None else _first_device(rgbs))
+    V = len(rgbs)
+    if V < 1:
+        raise T2NError("warp_sources: needs at least one source view")
+    rgb = _view_stack(rgbs, dev, torch.float32, "warp_sources: rgbs", (V, H, W, 3))
+    d = _view_stack(depths, dev, torch.float32, "warp_sources: depths", (V, H, W))
+    m1 = None
+    if masks is not None:
+        m1 = _stack(masks)
+        m1 = _view_stack(_mask_u8(m1, dev) if isinstance(m1, np.ndarray) else (m1 != 0), dev, torch.uint8, "warp_sources: masks", (V, H, W))
+    out = _warp_sources(lib, dev, rgb, d, m1, _source_mats([poses[v] for v in range(V)], pose_tar, intrinsic))
+    return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+
+def _pack(lib, dev, warp, known32, rgb, depth):
+    """t2n_inpaint_pack on the current stream of `dev`; returns the eight arrays in the C call's order."""
+    H, W = known32.shape
+    u8 = lambda *sh: torch.empty(*sh, dtype=torch.uint8, device=dev)                    # noqa: E731
+    out = (u8(H, W, 3), torch.empty(H, W, dtype=torch.int64, device=dev), u8(H, W), u8(H, W),
+           torch.empty(H, W, 3, dtype=torch.int64, device=dev), u8(H, W, 3), u8(H, W, 3), torch.empty(H, W, dtype=torch.float64, device=dev))
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_inpaint_pack(_lib.ptr(warp), _lib.ptr(known32), _lib.ptr(rgb), _lib.ptr(depth), H, W, *[_lib.ptr(t) for t in out],
+                                        _lib.current_stream_ptr(dev)), "t2n_inpaint_pack")
+    return out
+
+
+def pack_inpaint_inputs(output_image_warp, myMap_filt, rgb_render, depth_render, device=None):
+    """The arrays the driver builds around the inpainter (text2nerf_main.py:138-184, ``update_known_views=False``) in one launch, from
+    the filled warp [H,W,3] fp32, its 0/1 map [H,W], and the target render ``rgb_render`` [H,W,3] (clamped here) / ``depth_render``
+    [H,W] fp32. Returns ``(output_image_warp u8 [H,W,3], myMap_filt int64 [H,W], mask_image u8, mask_inv u8, mask_ex int64 [H,W,3],
+    rgb_render u8 [H,W,3], rgb_render_ u8 [H,W,3], depth_rendered fp64 [H,W])``."""
+    lib = _lib.load()
+    as_numpy = not _is_cuda(output_image_warp)
+    dev = _dev(device if device is not None else _first_device(output_image_warp))
+    known = _to(myMap_filt, dev, torch.int32)
+    if known.dim() != 2:
+        raise T2NError(f"pack_inpaint_inputs: myMap_filt must be [H,W], got {tuple(known.shape)}")
+    H, W = known.shape
+    warp = _view_stack(output_image_warp, dev, torch.float32, "pack_inpaint_inputs: output_image_warp", (H, W, 3))
+    rgb = _to(rgb_render, dev, torch.float32).reshape(-1)
+    dep = _to(depth_render, dev, torch.float32).reshape(-1)
+    if rgb.numel() != H * W * 3 or dep.numel() != H * W:
+        raise T2NError(f"pack_inpaint_inputs: the render does not match (H, W) = {(H, W)}")
+    out = _pack(lib, dev, warp, known, rgb, dep)
+    return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
+
+class InpaintView(NamedTuple):
+    """What ``render_warping_inapinting`` holds when it reaches the inpainter, named after its variables (text2nerf_main.py:99-184).
+    numpy arrays or device tensors, as ``build_inpaint_view`` was called.
+
+    ======================  ===========  =======  ===========================================================================
+    rgbs_pre                [V,H,W,3]    float32  the frames that were warped: the filtered renders of the known views (:119),
+    depths_pre              [V,H,W]      float32  or ``known_rgbs`` / ``known_depths`` as given
+    warp_image              [H,W,3]      float32  the merged warp before hole filling, in [0,1], white where nothing landed
+    myMap                   [H,W]        int64    1 where a known view landed (:129)
+    warp_depth              [H,W]        float64  its depth, 0 where nothing landed
+    output_image_warp       [H,W,3]      float32  the warp after ``dibr_filter_mask2`` (:134; = warp_image without the fill stage)
+    myMap_filt              [H,W]        int64    its map (= myMap without the fill stage)
+    output_depth            [H,W]        float64  its depth
+    output_image_warp_u8    [H,W,3]      uint8    what the driver rebinds ``output_image_warp`` to: ``* 255`` truncated, zero outside
+                                                  the mask (:138,156-157)
+    mask_image, mask_inv    [H,W]        uint8    ``myMap_filt * 255``, ``(1 - myMap_filt) * 255`` (:158-159)
+    mask_ex                 [H,W,3]      int64    ``myMap_filt`` on three channels (:154)
+    rgb_render              [H,W,3]      uint8    the new pose rendered, clamped, truncated (:169-170)
+    rgb_render_             [H,W,3]      uint8    ``rgb_render`` inside the mask, white outside (:174-177)
+    depth_rendered          [H,W]        float64  the rendered depth times the mask (:171)
+    output_image            [H,W,3]      uint8    the inpainter's init image: the same array as ``rgb_render`` (:184)
+    ======================  ===========  =======  ===========================================================================
+    """
+    myMap: Any
+    myMap_filt: Any
+    output_image_warp: Any
+    output_depth: Any
+    mask_image: Any
+    mask_inv: Any
+    mask_ex: Any
+    rgb_render: Any
+    rgb_render_: Any
+    depth_rendered: Any
+    output_image: Any
+    rgbs_pre: Any
+    depths_pre: Any
+    warp_image: Any
+    warp_depth: Any
+    output_image_warp_u8: Any
+
+
+def _render_frames(tensorf, poses, rays, intrinsic, H, W, N_samples, white_bg, ndc_ray):
+    """rgb [V,H,W,3] clamped to [0,1] and depth [V,H,W] of whole frames: from `rays` [V,H*W,6] as the driver's renderer call does
+    (text2nerf_main.py:110-112), else from rays generated on the device per pose (``render_views``)."""
+    from .renderer import OctreeRender_trilinear_fast, _no_materialised_weights, render_views
+    if rays is None:
+        if ndc_ray:
+            raise T2NError("build_inpaint_view: ndc_ray=True needs the caller's NDC rays (rays=)")
+        return render_views(tensorf, poses, intrinsic, H, W, N_samples=N_samples, white_bg=white_bg)
+    rgbs, depths = [], []
+    with torch.no_grad(), _no_materialised_weights(tensorf):
+        for v in range(rays.shape[0]):
+            rgb, _, depth, _, _ = OctreeRender_trilinear_fast(rays[v], tensorf, N_samples=N_samples, ndc_ray=ndc_ray, white_bg=white_bg,
+                                                              is_train=False, device=rays.device)
+            rgbs.append(rgb.clamp(0.0, 1.0).reshape(H, W, 3))
+            depths.append(depth.reshape(H, W))
+    return torch.stack(rgbs), torch.stack(depths)
+
+
+def build_inpaint_view(tensorf, poses, N_iter, H, W, intrinsic, N_samples=-1, white_bg=False, ndc_ray=False, rays=None, known_rgbs=None,
+                       known_depths=None, use_filter_filling=True, device=None):
+    """The half of ``render_warping_inapinting`` that runs before the inpainter (text2nerf_main.py:99-184, the
+    ``update_known_views=False`` branch the driver selects) as one device-resident call; returns an ``InpaintView``.
+
+    ``poses`` [>= N_iter + 1, 4, 4] camera-to-world (host array or tensor; inverted on the host): ``poses[:N_iter]`` are the known
+    views, ``poses[N_iter]`` the new one. Stages, queued in order with nothing read back in between (the known views render on
+    ``render_views``' two alternating streams, which hand over to the current stream; everything else is on the current stream):
+    render the known views; filter the stack (``[7,5,5,3,3]``, 0.02, 5 passes, :115-117); warp all of them into the new pose, earlier views win
+    (``warp_sources``); ``dibr_filter_mask2`` unless ``use_filter_filling=False``; render the new pose; pack.
+
+    Rays are generated on the device from ``(pose, intrinsic)`` as ``render_views`` does; ``rays`` [N_iter + 1, H*W, 6] (the driver's
+    ``all_rays_gen_split``) are used instead when given, and are required with ``ndc_ray``. ``known_rgbs`` [N_iter,H,W,3] /
+    ``known_depths`` [N_iter,H,W] is the ``use_rendered_img_to_warp=False`` form: these frames are warped, and the known views are
+    neither rendered nor filtered. numpy / CPU inputs -> numpy out; a device tensor among ``poses`` / ``rays`` / ``known_*`` (or
+    ``device=``) -> device tensors out. Not here: the ``update_known_views=True`` mask expansion and the PNG writes. No CPU fallback."""
+    V = int(N_iter)
+    if V < 1:
+        raise T2NError(f"build_inpaint_view: N_iter must be >= 1 (the known views to warp), got {N_iter}")
+    if (known_rgbs is None) != (known_depths is None):
+        raise T2NError("build_inpaint_view: known_rgbs and known_depths go together")
+    if len(poses) < V + 1:
+        raise T2NError(f"build_inpaint_view: {len(poses)} poses for N_iter = {V}: poses[N_iter] is the new view")
+    inputs = (poses, rays, known_rgbs, known_depths)
+    to_host = device is None and not any(_is_cuda(x) for x in inputs if x is not None)
+    dev = _dev(device if device is not None else (_first_device(*[x for x in inputs if x is not None]) or
+                                                  getattr(getattr(getattr(tensorf, "basis_mat", None), "weight", None), "device", None)))
+    lib = _lib.load()
+    poses_h = np.stack([_host(poses[v]) for v in range(V + 1)])
+    if poses_h.shape[1:] != (4, 4):
+        raise T2NError(f"build_inpaint_view: poses must be [N,4,4] camera-to-world matrices, got {poses_h.shape}")
+    if rays is not None:
+        rays = _to(rays if not isinstance(rays, (list, tuple)) else _stack(rays), dev, torch.float32)
+        if rays.dim() != 3 or rays.shape[0] < V + 1 or tuple(rays.shape[1:]) != (H * W, 6):
+            raise T2NError(f"build_inpaint_view: rays {tuple(rays.shape)} must be [>= {V + 1}, {H * W}, 6]")
+    with torch.cuda.device(dev):
+        if known_rgbs is not None:
+            rgbs_pre = _view_stack(known_rgbs, dev, torch.float32, "build_inpaint_view: known_rgbs", (V, H, W, 3))
+            depths_pre = _view_stack(known_depths, dev, torch.float32, "build_inpaint_view: known_depths", (V, H, W))
+        else:
+            rgb_k, depth_k = _render_frames(tensorf, poses_h[:V], None if rays is None else rays[:V], intrinsic, H, W, N_samples, white_bg,
+                                            ndc_ray)
+            rgbs_pre, depths_pre = _filter_views(lib, dev, depth_k.contiguous(), rgb_k.contiguous(), [7, 5, 5, 3, 3], 0.02, 5)
+        myMap, warp_image, warp_depth = _warp_sources(lib, dev, rgbs_pre, depths_pre, None, _source_mats(poses_h[:V], poses_h[V], intrinsic))
+        known = myMap.to(torch.int32)
+        filled_image, output_depth = warp_image, warp_depth
+        if use_filter_filling:
+            filled_image, output_depth = warp_image.clone(), warp_depth.clone()
+            _lib.check(lib.t2n_dibr_filter_mask2(_lib.ptr(filled_image), _lib.ptr(known), _lib.ptr(output_depth), H, W, 0.65,
+                                                 _lib.current_stream_ptr(dev)), "t2n_dibr_filter_mask2")
+        rgb_t, depth_t = _render_frames(tensorf, poses_h[V:V + 1], None if rays is None else rays[V:V + 1], intrinsic, H, W, N_samples,
+                                        white_bg, ndc_ray)
+        warp_u8, myMap_filt, mask_image, mask_inv, mask_ex, rgb_u8, rgb_masked, depth_rendered = _pack(
+            lib, dev, filled_image, known, rgb_t.contiguous(), depth_t.contiguous())
+    out = InpaintView(myMap=myMap, myMap_filt=myMap_filt, output_image_warp=filled_image, output_depth=output_depth, mask_image=mask_image,
+                      mask_inv=mask_inv, mask_ex=mask_ex, rgb_render=rgb_u8, rgb_render_=rgb_masked, depth_rendered=depth_rendered,
+                      output_image=rgb_u8, rgbs_pre=rgbs_pre, depths_pre=depths_pre, warp_image=warp_image, warp_depth=warp_depth,
+                      output_image_warp_u8=warp_u8)
+    if not to_host:
+        return out
+    host = {id(t): t.cpu().numpy() for t in set(out)}          # aliases (output_image is rgb_render) stay aliases
+    return InpaintView(*[host[id(t)] for t in out])
