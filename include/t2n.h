@@ -315,6 +315,27 @@ int t2n_frame_postprocess(const float* rgb /*[n,3]*/, const float* depth /*[n]*/
                           int shift_clamp, float mi, float ma, uint8_t* rgb8, uint8_t* depth8, const float* gt_rgb, double* sq_err_sum,
                           t2n_stream stream);
 
+/* t2n_ssim_views = rgb_ssim (utils.py:436-482; called per view by `evaluation`, renderer.py:103-109, and by the offline scorer
+ * extra/compute_metrics.py:34-80,151-162) for a STACK of V image pairs in one tile kernel plus one short reduction, instead of 30
+ * scipy.signal.convolve2d calls per view on the host: per channel the five "valid" Gaussian-windowed moments (mu0, mu1, E[a a],
+ * E[b b], E[a b]), the clamped variances / covariance, the SSIM map and its mean. Device inputs: img0, img1 [V,H,W,3] of `dtype`
+ * (0: float32, 1: float64). The products a*a, b*b, a*b are formed in the input dtype (as `img0**2` is in the reference) and every
+ * window sum and all later arithmetic is float64 (scipy widens the image to the float64 filter's dtype), so the map agrees with the
+ * reference to ~1e-13 (summation order only). Host input: filter_host [filter_size] = the normalised 1-D taps, copied into the
+ * launch by value; 1 <= filter_size <= 33 (compile-time cap of the kernel's LDS stage). c1 = (k1 max_val)^2, c2 = (k2 max_val)^2.
+ * clamp01_img0 != 0: img0 is clamped to [0,1] as it is loaded (renderer.py:92), so a raw render can be scored. Device outputs:
+ * ssim [V] = mean of each view's map; ssim_map [V,H-fs+1,W-fs+1,3] or NULL; sq_err [V] or NULL = sum((img0 - img1)^2) per view,
+ * difference and square in the input dtype, summed in float64 (PSNR = -10 log10(sq_err / (3 H W)), renderer.py:98). No atomics:
+ * results are bit-repeatable and a view of a stack is bit-equal to the same view alone. Nothing is allocated or synchronised.
+ * Workspace: t2n_ssim_views_workspace_bytes(V, H, W, filter_size) bytes of device memory (0 = bad argument). T2N_ERR_INVALID,
+ * before anything is launched: NULL img0 / img1 / filter_host / ssim / workspace, dtype not 0 / 1, filter_size outside 1..33,
+ * H or W < filter_size (scipy raises there too), V < 1 (or > 65535), H or W > 32768, workspace too small. */
+size_t t2n_ssim_views_workspace_bytes(int V, int H, int W, int filter_size);
+int t2n_ssim_views(const void* img0, const void* img1, int dtype /*0: float32, 1: float64*/, int V, int H, int W,
+                   const double* filter_host /*[filter_size], host*/, int filter_size, double c1, double c2, int clamp01_img0,
+                   double* ssim /*[V]*/, double* ssim_map /*[V,H-fs+1,W-fs+1,3] or NULL*/, double* sq_err /*[V] or NULL*/,
+                   void* workspace, size_t workspace_bytes, t2n_stream stream);
+
 /* ---- f-3: the image-space steps either side of the renderer in render_warping_inapinting (text2nerf_main.py:102-141).
  * t2n_sparse_bilateral_filtering = dataLoader/bilateral_filtering.py:5-35 with mask=None, HR=False: per pass the depth
  * discontinuity map (:64-136; 4-neighbour disparity jumps > depth_threshold, or original depth == 0) and the median of the
