@@ -576,6 +576,51 @@ int t2n_filter_rays_alpha(const t2n_field* f, const float* rays, int64_t n_rays,
  * samples kept}. Double precision, deterministic. */
 int t2n_depth_align_global(const float* depth_rendered, const float* depth_est, int H, int W, const int32_t* pixel_sample_yx,
                            int n_samples, double push_depth, float* depth_shift, double* scale_shift, t2n_stream stream);
+/* The same over an EMPTY sample list, which t2n_depth_align_global rejects (n_samples < 1): no pixel of the warped view is filled,
+ * :233-240 give pixel_sample = [], and the reference falls through to scale = thresh (:251-252) and shift = max scaled - max
+ * rendered (:265-266). Same outputs; pairs kept = samples kept = 0. */
+int t2n_depth_align_fallback(const float* depth_rendered, const float* depth_est, int H, int W, double push_depth, float* depth_shift,
+                             double* scale_shift, t2n_stream stream);
+
+/* ---- The depth stage of a new view: what text2nerf_main.py does between the inpainter and the support set (:230-299) and the
+ * update_known_views=True mask expansion (:147-162), apart from the networks. All exact and deterministic (no atomics); H * W < 2^31.
+ *
+ * Filled pixels, :233-239: `pixel_filled` lists the pixels with myMap_filt > 0 column by column (column ascending, inside a column row
+ * ascending; the reference's loop bounds assume H == W, the order is defined here for any H, W) as (row, col), and
+ * random.sample(pixel_filled, k) is [pixel_filled[r] for r in random.sample(range(n), k)] with the generator left in the same state.
+ * So the draw stays on the host and the image on the device:
+ *   t2n_filled_pixels_count   per-column counts of known > 0 (known [H,W] int32), their exclusive scan into the workspace (W + 1 int32
+ *                             offsets; t2n_filled_pixels_workspace_bytes(H, W), 0 = bad argument), n to count_out (device int64)
+ *   t2n_filled_pixels_select  ranks [K] int32 (device; each in [0, n)) -> pixel_yx [K][2] int32 (row, col), the layout
+ *                             t2n_depth_align_global reads; the workspace as the count call left it for the same map. K = 0 is a
+ *                             no-op; a rank outside [0, n) gives (-1, -1).
+ * T2N_ERR_INVALID: NULL / non-positive argument. */
+size_t t2n_filled_pixels_workspace_bytes(int H, int W);
+int t2n_filled_pixels_count(const int32_t* known, int H, int W, void* workspace, int64_t* count_out, t2n_stream stream);
+int t2n_filled_pixels_select(const int32_t* known, int H, int W, const void* workspace, const int32_t* ranks, int K, int32_t* pixel_yx,
+                             t2n_stream stream);
+/* t2n_depth_merge_inputs = the merge network's inputs, :275-276, in one elementwise launch, from depth_rendered [H,W] fp64 (the
+ * rendered depth times the mask, t2n_inpaint_pack's depth_masked), the map `known` [H,W] int32 (0 / non-zero) and depth_shift [H,W]
+ * fp32 (t2n_depth_align_global's output), with numpy's dtype rules for these inputs:
+ *   depth_ref [H,W] fp32 = float32(((depth_rendered - push) * 12000 / 32768. - 1.) * mask)   fp64 arithmetic, rounded once  (:275)
+ *   depth_src [H,W] fp32 = (depth_shift - push) * 12000 / 32768. - 1.                        fp32 operation by operation    (:276)
+ *   mask [H,W] fp32      = the map as 0 / 1: run_finetune_numpy's mask_ref                                                  (:277)
+ * T2N_ERR_INVALID: NULL / non-positive argument. */
+int t2n_depth_merge_inputs(const double* depth_rendered, const int32_t* known, const float* depth_shift, int H, int W, double push_depth,
+                           float* depth_ref, float* depth_src, float* mask, t2n_stream stream);
+/* t2n_view_finish = the arrays rebuilt after the merge network, in one elementwise launch, from depth_merged [H,W] fp32 (the
+ * network's output in [-1,1]), the chosen inpainted image img_u8 [H,W,3] uint8 and the map `known` [H,W] int32:
+ *   depth_new [H,W] fp32            = ((depth_merged + 1.) * 32768.) / 12000 + push   fp32 operation by operation  (:278, :282)
+ *   img_new [H,W,3] fp32            = float32(double(img_u8) / 255.)                                               (:285)
+ *   mask_inpainted [H,W] int64      = 1 - mask                                                                     (:296)
+ * T2N_ERR_INVALID: NULL / non-positive argument. */
+int t2n_view_finish(const float* depth_merged, const uint8_t* img_u8, const int32_t* known, int H, int W, double push_depth,
+                    float* depth_new, float* img_new, int64_t* mask_inpainted, t2n_stream stream);
+/* t2n_mask_expand = the update_known_views=True mask expansion, :147-152: (cv2.blur(myMap_filt as float32, (5,5)) > 0.99) * 1 with
+ * OpenCV's default border (BORDER_REFLECT_101). 25 set taps average to >= 0.9999 and 24 to 0.96 in float32 whatever the summation
+ * order, so the test is the AND of the 25 taps. known [H,W] int32 (0 / non-zero) -> eroded [H,W] int32 (0 / 1; not in place) and
+ * mask_ex [H,W,3] int64 = the removed ring (mask - eroded) on three channels (:150-151). T2N_ERR_INVALID: NULL argument, H or W < 3. */
+int t2n_mask_expand(const int32_t* known, int H, int W, int32_t* eroded, int64_t* mask_ex, t2n_stream stream);
 
 /* ---- One optimisation step of the reference's loop (text2nerf_main.py:547-601) as ONE submission: TV gradient -> train-mode render
  * (KEEP_CTX) -> t2n_train_loss -> t2n_render_backward (device-side row plan, as T2N_FLAG_DEVICE_ROWS) -> Adam on all 19 tensors ->

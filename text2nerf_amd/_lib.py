@@ -123,6 +123,15 @@ SIGNATURES = {
     "t2n_render_workspace_bytes_ctx": (C.c_size_t, [C.c_int64, C.c_int]),
     "t2n_depth_align_global": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "t2n_depth_align_fallback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2n_filled_pixels_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "t2n_filled_pixels_count": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2n_filled_pixels_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "t2n_depth_merge_inputs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "t2n_view_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
+    "t2n_mask_expand": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2n_field_grad_buffer_bytes": (C.c_size_t, [C.c_void_p]),
     "t2n_field_set_grad_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "t2n_field_grad_buffer_density_bytes": (C.c_size_t, [C.c_void_p]),

@@ -572,3 +572,20 @@ extern "C" int t2n_depth_align_global(const float* depth_rendered, const float* 
     T2N_HIP(hipGetLastError());
     return T2N_OK;
 }
+
+// The same two kernels over an empty sample list (no pixel of the warped view is filled, :233-240 give pixel_sample = []): both sample
+// loops run zero times, which leaves the reference's fallbacks, scale = thresh (:251-252) and shift = thresh2 (:265-266).
+extern "C" int t2n_depth_align_fallback(const float* depth_rendered, const float* depth_est, int H, int W, double push_depth,
+                                        float* depth_shift, double* scale_shift, t2n_stream stream) {
+    if (!depth_rendered || !depth_est || !depth_shift || !scale_shift || H < 1 || W < 1) {
+        set_error("t2n_depth_align_fallback: bad argument");
+        return T2N_ERR_INVALID;
+    }
+    AlignArgs a;
+    a.dr = depth_rendered; a.de = depth_est; a.H = H; a.W = W; a.ps = nullptr; a.K = 0; a.push = push_depth;
+    a.out = depth_shift; a.ss = scale_shift;
+    hipLaunchKernelGGL(k_align_stats, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(k_align_apply, dim3((unsigned)(((long long)H * W + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}

@@ -16,13 +16,22 @@ and everything before inpainting as one device-resident call (csrc/t2n_image.hip
 
 * ``build_inpaint_view`` — text2nerf_main.py:99-184: known views rendered, filtered as a stack
   (``sparse_bilateral_filtering_views``), warped into the new pose in one launch set per 8 sources (``warp_sources``), hole-filled,
-  the new pose rendered, and the inpainter's uint8 image and masks packed (``pack_inpaint_inputs``)
+  the new pose rendered, and the inpainter's uint8 image and masks packed (``pack_inpaint_inputs``), with the
+  ``update_known_views=True`` mask expansion (:147-162) as a keyword
+
+and the depth stage between the inpainter and the support set (csrc/t2n_view.hip):
+
+* ``sample_filled_pixels`` — text2nerf_main.py:233-239: the filled-pixel list addressed by rank, the draw on the caller's ``random``
+* ``prepare_depth_merge`` — :230-276: sampling, the global alignment and the merge network's inputs in one call
+* ``finish_view`` — :278-299 and :380-392: the merged depth to ``depth_new`` / ``img_new`` / the inpainted mask, the filter, the support
+  set and the training set's new rows in one call
 
 Inputs may be numpy arrays (as in the driver) or torch tensors; numpy in -> numpy out. No CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+import random
 from typing import Any, NamedTuple
 
 import numpy as np
@@ -155,12 +164,20 @@ def align_depth_global(depth_rendered, depth_est, pixel_sample, push_depth=2.0, 
     """The global stage of the depth alignment in ``render_warping_inapinting`` (text2nerf_main.py:241-270) on the device: scale and
     shift of the monocular estimate against the rendered depth over the caller's sampled pixel list (``random.sample`` of the filled
     pixels, :234-240 — host-side and the caller's, like the reference's). Returns ``(scale, shift, depth_shift)`` with ``depth_shift``
-    a float32 [H,W] device tensor (= depth_est * scale - shift) and scale / shift Python floats (one 32-byte read-back)."""
+    a float32 [H,W] device tensor (= depth_est * scale - shift) and scale / shift Python floats (one 32-byte read-back).
+    ``pixel_sample`` may also be a device int32 [K,2] tensor of (row, col) — what ``sample_filled_pixels`` returns for a device mask —
+    which is read in place, with no host hop."""
     lib = _lib.load()
     dev = _dev(device)
     dr = _to(depth_rendered, dev, torch.float32)
     de = _to(depth_est, dev, torch.float32)
-    ps = torch.as_tensor(np.asarray(pixel_sample, dtype=np.int32).reshape(-1, 2)).to(dev).contiguous()
+    if isinstance(pixel_sample, torch.Tensor) and pixel_sample.is_cuda:
+        if pixel_sample.dtype != torch.int32 or pixel_sample.dim() != 2 or pixel_sample.shape[1] != 2:
+            raise T2NError(f"align_depth_global: a device pixel_sample must be int32 [K,2], got {pixel_sample.dtype} "
+                           f"{tuple(pixel_sample.shape)}")
+        ps = pixel_sample.to(dev).contiguous()
+    else:
+        ps = torch.as_tensor(np.asarray(pixel_sample, dtype=np.int32).reshape(-1, 2)).to(dev).contiguous()
     H, W = dr.shape
     out = torch.empty(H, W, device=dev, dtype=torch.float32)
     ss = torch.empty(4, device=dev, dtype=torch.float64)
@@ -169,6 +186,120 @@ def align_depth_global(depth_rendered, depth_est, pixel_sample, push_depth=2.0, 
                                               _lib.ptr(out), _lib.ptr(ss), _lib.current_stream_ptr(dev)), "t2n_depth_align_global")
     s = ss.cpu().tolist()
     return s[0], s[1], out
+
+
+# ---- between the inpainter and the support set: sampling, alignment, the merge network's inputs ----------------------------------------
+def _known32(m, dev):
+    """A validity map (int64 ``myMap_filt``, int32 ``known``, boolean or a float 0/1 map) as device int32; int32 on `dev` is used in
+    place."""
+    t = torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m
+    if t.dim() != 2:
+        raise T2NError(f"the validity map must be [H,W], got {tuple(t.shape)}")
+    if t.is_floating_point() or t.dtype == torch.bool:
+        t = t.to(dev) > 0
+    return t.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _filled_pixels(lib, dev, known, max_samples, rng):
+    """Count, draw on the host, select: device int32 [K,2] (row, col). The one host read is the 8-byte count."""
+    H, W = known.shape
+    ws = torch.empty(int(lib.t2n_filled_pixels_workspace_bytes(H, W)), dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        st = _lib.current_stream_ptr(dev)
+        _lib.check(lib.t2n_filled_pixels_count(_lib.ptr(known), H, W, _lib.ptr(ws), _lib.ptr(count), st), "t2n_filled_pixels_count")
+        n = int(count.item())
+        ranks = rng.sample(range(n), min(n, int(max_samples)))      # random.sample(pixel_filled, num_max) draws exactly these indices
+        out = torch.empty(len(ranks), 2, dtype=torch.int32, device=dev)
+        if ranks:
+            r = torch.tensor(ranks, dtype=torch.int32).to(dev)
+            _lib.check(lib.t2n_filled_pixels_select(_lib.ptr(known), H, W, _lib.ptr(ws), _lib.ptr(r), len(ranks), _lib.ptr(out), st),
+                       "t2n_filled_pixels_select")
+    return out
+
+
+def sample_filled_pixels(myMap_filt, max_samples=10000, rng=random, device=None):
+    """``pixel_sample`` of text2nerf_main.py:233-239 without the image leaving the device: int32 [K,2] of (row, col), K = min(number of
+    pixels with ``myMap_filt > 0``, ``max_samples``), bit-compatible with the reference's ``random.sample(pixel_filled, num_max)`` for
+    the same generator state, and leaving the generator in the same state.
+
+    The reference lists the filled pixels with ``for i in range(H): for j in range(W): if myMap_filt[j, i] > 0``, whose index ranges
+    only make sense for H == W. The order is defined here as COLUMN-MAJOR over the whole image for any H, W: column ascending, and
+    inside a column row ascending. ``random.sample(list, k)`` picks ``[list[r] for r in random.sample(range(len(list)), k)]``, so the
+    device counts (per-column counts, one scan; the total is the one 8-byte read), ``rng`` draws the ranks on the host (``rng``: the
+    ``random`` module or a ``random.Random``; one upload of at most ``max_samples`` int32), and a kernel maps each rank to its pixel.
+    ``myMap_filt``: the int64 map of ``InpaintView``, the int32 ``known`` form, boolean or a float 0/1 map. A device mask in -> a device
+    tensor out, which ``align_depth_global`` reads in place; a numpy mask in -> a numpy array out. No CPU fallback."""
+    lib = _lib.load()
+    as_numpy = not _is_cuda(myMap_filt)
+    dev = _dev(device if device is not None else _first_device(myMap_filt))
+    out = _filled_pixels(lib, dev, _known32(myMap_filt, dev), max_samples, rng)
+    return out.cpu().numpy() if as_numpy and device is None else out
+
+
+class DepthMerge(NamedTuple):
+    """What ``render_warping_inapinting`` holds when it reaches the merge network (text2nerf_main.py:230-277).
+
+    ============  =======  =======  ===================================================================================
+    scale, shift           float    the global alignment (:254, :268)
+    pixel_sample  [K,2]    int32    the sampled filled pixels, (row, col) (:239)
+    depth_shift   [H,W]    float32  ``depth_est * scale - shift`` (:270)
+    depth_ref     [H,W]    float32  ``((depth_rendered - push) * 12000 / 32768. - 1.) * myMap_filt``, rounded once (:275, :277)
+    depth_src     [H,W]    float32  ``(depth_shift - push) * 12000 / 32768. - 1.`` (:276)
+    mask          [H,W]    float32  ``myMap_filt``: what ``run_finetune_numpy`` receives as ``mask_ref`` (:277)
+    ============  =======  =======  ===================================================================================
+    """
+    scale: float
+    shift: float
+    pixel_sample: Any
+    depth_shift: Any
+    depth_ref: Any
+    depth_src: Any
+    mask: Any
+
+
+def prepare_depth_merge(depth_rendered, myMap_filt, depth_est, push_depth, rng=random, max_samples=10000, device=None):
+    """From "the depth estimate is here" to "the merge network's inputs are on the device" (text2nerf_main.py:230-276) in one call:
+    ``sample_filled_pixels`` -> the global alignment (``align_depth_global``'s kernels) -> one elementwise launch for ``depth_ref`` /
+    ``depth_src`` / the float32 mask; returns a ``DepthMerge``.
+
+    ``depth_rendered`` [H,W] is ``InpaintView.depth_rendered`` (float64: the rendered depth times the map; the alignment reads it as
+    float32, which is exact for that product), ``myMap_filt`` its map, ``depth_est`` [H,W] the monocular estimate after
+    ``/ 12000 + push_depth`` (:230; read as float32, as ``align_depth_global`` does). The arithmetic follows numpy's dtype rules for
+    these inputs: ``depth_ref`` in float64, rounded to float32 once; ``depth_src`` in float32 operation by operation. An empty map
+    gives the reference's fallbacks (no samples: ``scale = thresh``, ``shift = max scaled - max rendered``). Host reads: the 8-byte
+    count and the 32-byte scale / shift record. numpy / CPU inputs -> numpy arrays out; a device tensor among the inputs (or
+    ``device=``) -> device tensors out. No CPU fallback."""
+    lib = _lib.load()
+    inputs = (depth_rendered, myMap_filt, depth_est)
+    to_host = device is None and not any(_is_cuda(x) for x in inputs)
+    dev = _dev(device if device is not None else _first_device(*inputs))
+    known = _known32(myMap_filt, dev)
+    H, W = known.shape
+    dr64 = _to(depth_rendered, dev, torch.float64)
+    de = _to(depth_est, dev, torch.float32)
+    if tuple(dr64.shape) != (H, W) or tuple(de.shape) != (H, W):
+        raise T2NError(f"prepare_depth_merge: depth_rendered {tuple(dr64.shape)} / depth_est {tuple(de.shape)} do not match the map {(H, W)}")
+    dr32 = dr64.to(torch.float32)
+    ps = _filled_pixels(lib, dev, known, max_samples, rng)
+    f32 = lambda: torch.empty(H, W, device=dev, dtype=torch.float32)                       # noqa: E731
+    depth_shift, depth_ref, depth_src, mask = f32(), f32(), f32(), f32()
+    ss = torch.empty(4, device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        st = _lib.current_stream_ptr(dev)
+        if ps.shape[0] >= 1:
+            _lib.check(lib.t2n_depth_align_global(_lib.ptr(dr32), _lib.ptr(de), H, W, _lib.ptr(ps), int(ps.shape[0]), float(push_depth),
+                                                  _lib.ptr(depth_shift), _lib.ptr(ss), st), "t2n_depth_align_global")
+        else:
+            _lib.check(lib.t2n_depth_align_fallback(_lib.ptr(dr32), _lib.ptr(de), H, W, float(push_depth), _lib.ptr(depth_shift),
+                                                    _lib.ptr(ss), st), "t2n_depth_align_fallback")
+        _lib.check(lib.t2n_depth_merge_inputs(_lib.ptr(dr64), _lib.ptr(known), _lib.ptr(depth_shift), H, W, float(push_depth),
+                                              _lib.ptr(depth_ref), _lib.ptr(depth_src), _lib.ptr(mask), st), "t2n_depth_merge_inputs")
+    s = ss.cpu().tolist()
+    arrays = (ps, depth_shift, depth_ref, depth_src, mask)
+    if to_host:
+        arrays = tuple(t.cpu().numpy() for t in arrays)
+    return DepthMerge(s[0], s[1], *arrays)
 
 
 # ---- after inpainting: one RGB-D view -> support views -> training rays -------------------------------------------------------------
@@ -396,6 +527,71 @@ def build_support_set(img_new, depth_new, mask_inpainted, poses_support, intrins
     return rows, rgbs, deps, rays_split, images, depths, torch.from_numpy(p44).to(dev)
 
 
+# ---- after the merge network: the finished view, its support set, its rows in the training set ------------------------------------------
+def _view_finish(lib, dev, depth_merged, img_u8, known, push_depth):
+    """t2n_view_finish on the current stream of `dev`: (depth_new fp32 [H,W], img_new fp32 [H,W,3], mask_inpainted int64 [H,W]),
+    before the filter."""
+    H, W = known.shape
+    depth_new = torch.empty(H, W, dtype=torch.float32, device=dev)
+    img_new = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    mask_inpainted = torch.empty(H, W, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_view_finish(_lib.ptr(depth_merged), _lib.ptr(img_u8), _lib.ptr(known), H, W, float(push_depth),
+                                       _lib.ptr(depth_new), _lib.ptr(img_new), _lib.ptr(mask_inpainted), _lib.current_stream_ptr(dev)),
+                   "t2n_view_finish")
+    return depth_new, img_new, mask_inpainted
+
+
+class FinishedView(NamedTuple):
+    """``finish_view``'s return, named after the driver's variables (text2nerf_main.py:278-299, :380-392). Device tensors.
+
+    ==============  =========  =======  =============================================================================
+    img_new         [H,W,3]    float32  the inpainted image ``/ 255.`` after the filter (:285, :291)
+    depth_new       [H,W]      float32  the merged depth in scene units after the filter (:278, :282, :290)
+    mask_inpainted  [H,W]      int64    ``current_mask_inpainted = 1 - myMap_filt`` (:296)
+    support                             ``build_support_set``'s 7-tuple for the view (:380-392)
+    lo, hi                     int      the row range the view's rays took in ``train_set`` (``None`` without a set)
+    ==============  =========  =======  =============================================================================
+    """
+    img_new: Any
+    depth_new: Any
+    mask_inpainted: Any
+    support: Any
+    lo: Any
+    hi: Any
+
+
+def finish_view(depth_merged, img_u8, myMap_filt, push_depth, poses_support, intrinsic, H, W, train_set=None, device=None):
+    """From "the merged depth is here" to "the rows are in the training set" (text2nerf_main.py:278-299 and :380-392) in one call:
+    one elementwise launch for ``depth_new = ((depth_merged + 1.) * 32768.) / 12000 + push_depth`` (float32 operation by operation, as
+    :278 and :282 on the network's float32 output), ``img_new = float32(img_u8 / 255.)`` (:285) and ``1 - myMap_filt`` (:296); the
+    depth-aware filter with ``[5, 5, 3, 3]``, 0.02, 4 passes (:287-291); ``build_support_set`` on the filtered pair; and, when
+    ``train_set`` (a ``DeviceTrainSet``) is given, ``train_set.append`` of the rows. Returns a ``FinishedView`` of device tensors.
+
+    ``depth_merged``: the merge network's output, H*W float32 values in [-1,1] in any leading shape; ``img_u8`` [H,W,3] uint8, the
+    chosen inpainted image; ``myMap_filt`` [H,W] the map the view was built with; ``poses_support`` [N,4,4] as ``build_support_set``
+    takes them (host array; ``poses_support[0]`` is the view's own pose). Nothing between the stages is read on the host except
+    ``build_support_set``'s row-count record. The PNG previews of :279-293 are not written. No CPU fallback."""
+    lib = _lib.load()
+    dev = _dev(device if device is not None else _first_device(depth_merged, img_u8, myMap_filt))
+    known = _known32(myMap_filt, dev)
+    if tuple(known.shape) != (H, W):
+        raise T2NError(f"finish_view: myMap_filt {tuple(known.shape)} does not match (H, W) = {(H, W)}")
+    dm = _to(depth_merged, dev, torch.float32)
+    u8 = _to(img_u8, dev, torch.uint8)
+    if dm.numel() != H * W or tuple(u8.shape) != (H, W, 3):
+        raise T2NError(f"finish_view: depth_merged {tuple(dm.shape)} / img_u8 {tuple(u8.shape)} do not match (H, W) = {(H, W)}")
+    depth0, img0, mask_inpainted = _view_finish(lib, dev, dm.reshape(H, W), u8, known, push_depth)
+    photo, keep = _filter_views(lib, dev, depth0[None], img0[None], [5, 5, 3, 3], 0.02, 4)
+    img_new, depth_new = photo[0], keep[0]
+    with torch.cuda.device(dev):
+        support = build_support_set(img_new, depth_new, mask_inpainted, poses_support, intrinsic, H, W, device=dev)
+        lo = hi = None
+        if train_set is not None:
+            lo, hi = train_set.append(support[0], support[1], support[2])
+    return FinishedView(img_new, depth_new, mask_inpainted, support, lo, hi)
+
+
 # ---- before inpainting: known views -> the warped, filled and packed new view ------------------------------------------------------------
 def _filter_schedule(filter_size, num_iter):
     sizes = [int(filter_size[i]) if isinstance(filter_size, (list, tuple)) else int(filter_size) for i in range(num_iter)]
@@ -511,11 +707,25 @@ def _pack(lib, dev, warp, known32, rgb, depth):
     return out
 
 
-def pack_inpaint_inputs(output_image_warp, myMap_filt, rgb_render, depth_render, device=None):
-    """The arrays the driver builds around the inpainter (text2nerf_main.py:138-184, ``update_known_views=False``) in one launch, from
+def _expand_mask(lib, dev, known32):
+    """t2n_mask_expand on the current stream of `dev`: (eroded map int32 [H,W], the removed ring int64 [H,W,3])."""
+    H, W = known32.shape
+    eroded = torch.empty_like(known32)
+    ring = torch.empty(H, W, 3, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_mask_expand(_lib.ptr(known32), H, W, _lib.ptr(eroded), _lib.ptr(ring), _lib.current_stream_ptr(dev)),
+                   "t2n_mask_expand")
+    return eroded, ring
+
+
+def pack_inpaint_inputs(output_image_warp, myMap_filt, rgb_render, depth_render, device=None, update_known_views=False):
+    """The arrays the driver builds around the inpainter (text2nerf_main.py:138-184) in one launch, from
     the filled warp [H,W,3] fp32, its 0/1 map [H,W], and the target render ``rgb_render`` [H,W,3] (clamped here) / ``depth_render``
     [H,W] fp32. Returns ``(output_image_warp u8 [H,W,3], myMap_filt int64 [H,W], mask_image u8, mask_inv u8, mask_ex int64 [H,W,3],
-    rgb_render u8 [H,W,3], rgb_render_ u8 [H,W,3], depth_rendered fp64 [H,W])``."""
+    rgb_render u8 [H,W,3], rgb_render_ u8 [H,W,3], depth_rendered fp64 [H,W])``. ``update_known_views=True`` is the mask expansion of
+    :147-152, one stencil launch in front: the map is eroded (a pixel stays 1 only when its whole 5x5 window, reflected at the border
+    as OpenCV's default ``BORDER_REFLECT_101`` does, is 1), the eroded map takes ``myMap_filt``'s place in every output, and
+    ``mask_ex`` is the removed ring (the map minus the eroded map) on three channels."""
     lib = _lib.load()
     as_numpy = not _is_cuda(output_image_warp)
     dev = _dev(device if device is not None else _first_device(output_image_warp))
@@ -528,7 +738,12 @@ def pack_inpaint_inputs(output_image_warp, myMap_filt, rgb_render, depth_render,
     dep = _to(depth_render, dev, torch.float32).reshape(-1)
     if rgb.numel() != H * W * 3 or dep.numel() != H * W:
         raise T2NError(f"pack_inpaint_inputs: the render does not match (H, W) = {(H, W)}")
+    ring = None
+    if update_known_views:
+        known, ring = _expand_mask(lib, dev, known)
     out = _pack(lib, dev, warp, known, rgb, dep)
+    if ring is not None:
+        out = out[:4] + (ring,) + out[5:]
     return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
 
@@ -543,12 +758,14 @@ class InpaintView(NamedTuple):
     myMap                   [H,W]        int64    1 where a known view landed (:129)
     warp_depth              [H,W]        float64  its depth, 0 where nothing landed
     output_image_warp       [H,W,3]      float32  the warp after ``dibr_filter_mask2`` (:134; = warp_image without the fill stage)
-    myMap_filt              [H,W]        int64    its map (= myMap without the fill stage)
+    myMap_filt              [H,W]        int64    its map (= myMap without the fill stage); with ``update_known_views=True`` that map
+                                                  eroded (:148-152), which every row below then uses
     output_depth            [H,W]        float64  its depth
     output_image_warp_u8    [H,W,3]      uint8    what the driver rebinds ``output_image_warp`` to: ``* 255`` truncated, zero outside
                                                   the mask (:138,156-157)
     mask_image, mask_inv    [H,W]        uint8    ``myMap_filt * 255``, ``(1 - myMap_filt) * 255`` (:158-159)
-    mask_ex                 [H,W,3]      int64    ``myMap_filt`` on three channels (:154)
+    mask_ex                 [H,W,3]      int64    ``myMap_filt`` on three channels (:154); with ``update_known_views=True`` the ring the
+                                                  erosion removed (:150-151)
     rgb_render              [H,W,3]      uint8    the new pose rendered, clamped, truncated (:169-170)
     rgb_render_             [H,W,3]      uint8    ``rgb_render`` inside the mask, white outside (:174-177)
     depth_rendered          [H,W]        float64  the rendered depth times the mask (:171)
@@ -592,9 +809,10 @@ def _render_frames(tensorf, poses, rays, intrinsic, H, W, N_samples, white_bg, n
 
 
 def build_inpaint_view(tensorf, poses, N_iter, H, W, intrinsic, N_samples=-1, white_bg=False, ndc_ray=False, rays=None, known_rgbs=None,
-                       known_depths=None, use_filter_filling=True, device=None):
-    """The half of ``render_warping_inapinting`` that runs before the inpainter (text2nerf_main.py:99-184, the
-    ``update_known_views=False`` branch the driver selects) as one device-resident call; returns an ``InpaintView``.
+                       known_depths=None, use_filter_filling=True, device=None, update_known_views=False):
+    """The half of ``render_warping_inapinting`` that runs before the inpainter (text2nerf_main.py:99-184) as one device-resident
+    call; returns an ``InpaintView``. ``update_known_views=False`` is the branch the driver selects; ``True`` adds the mask expansion
+    of :147-152 (see ``pack_inpaint_inputs``) between the fill stage and the pack.
 
     ``poses`` [>= N_iter + 1, 4, 4] camera-to-world (host array or tensor; inverted on the host): ``poses[:N_iter]`` are the known
     views, ``poses[N_iter]`` the new one. Stages, queued in order with nothing read back in between (the known views render on
@@ -606,7 +824,7 @@ def build_inpaint_view(tensorf, poses, N_iter, H, W, intrinsic, N_samples=-1, wh
     ``all_rays_gen_split``) are used instead when given, and are required with ``ndc_ray``. ``known_rgbs`` [N_iter,H,W,3] /
     ``known_depths`` [N_iter,H,W] is the ``use_rendered_img_to_warp=False`` form: these frames are warped, and the known views are
     neither rendered nor filtered. numpy / CPU inputs -> numpy out; a device tensor among ``poses`` / ``rays`` / ``known_*`` (or
-    ``device=``) -> device tensors out. Not here: the ``update_known_views=True`` mask expansion and the PNG writes. No CPU fallback."""
+    ``device=``) -> device tensors out. Not here: the PNG writes. No CPU fallback."""
     V = int(N_iter)
     if V < 1:
         raise T2NError(f"build_inpaint_view: N_iter must be >= 1 (the known views to warp), got {N_iter}")
@@ -643,8 +861,13 @@ def build_inpaint_view(tensorf, poses, N_iter, H, W, intrinsic, N_samples=-1, wh
                                                  _lib.current_stream_ptr(dev)), "t2n_dibr_filter_mask2")
         rgb_t, depth_t = _render_frames(tensorf, poses_h[V:V + 1], None if rays is None else rays[V:V + 1], intrinsic, H, W, N_samples,
                                         white_bg, ndc_ray)
+        ring = None
+        if update_known_views:
+            known, ring = _expand_mask(lib, dev, known)
         warp_u8, myMap_filt, mask_image, mask_inv, mask_ex, rgb_u8, rgb_masked, depth_rendered = _pack(
             lib, dev, filled_image, known, rgb_t.contiguous(), depth_t.contiguous())
+        if ring is not None:
+            mask_ex = ring
     out = InpaintView(myMap=myMap, myMap_filt=myMap_filt, output_image_warp=filled_image, output_depth=output_depth, mask_image=mask_image,
                       mask_inv=mask_inv, mask_ex=mask_ex, rgb_render=rgb_u8, rgb_render_=rgb_masked, depth_rendered=depth_rendered,
                       output_image=rgb_u8, rgbs_pre=rgbs_pre, depths_pre=depths_pre, warp_image=warp_image, warp_depth=warp_depth,
