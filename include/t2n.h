@@ -622,6 +622,30 @@ int t2n_view_finish(const float* depth_merged, const uint8_t* img_u8, const int3
  * mask_ex [H,W,3] int64 = the removed ring (mask - eroded) on three channels (:150-151). T2N_ERR_INVALID: NULL argument, H or W < 3. */
 int t2n_mask_expand(const int32_t* known, int H, int W, int32_t* eroded, int64_t* mask_ex, t2n_stream stream);
 
+/* ---- Mesh export: marching cubes over a dense volume on the device, in the place of skimage.measure.marching_cubes on a host copy
+ * in convert_sdf_samples_to_ply (utils.py:512-572; upstream's export_mesh hands it getDenseAlpha's volume). volume [n0][n1][n2] fp32,
+ * contiguous, last index fastest. A node is inside iff v > level (strict: NaN is outside). A crossed grid edge carries one vertex,
+ * owned by the edge's lower node; cases and triangles come from a generated table (csrc/t2n_mc_table.h, tools/gen_mc_table.py) whose
+ * meshes are closed oriented 2-manifolds with right-hand normals towards LOWER values. No atomics: vertices come in node-linear order
+ * (inside a node axis 0, 1, 2), triangles in cell-linear order (inside a cell table order), both functions of the input alone.
+ *   t2n_mc_count   classifies every node and cell, scans the counts into the workspace (t2n_mc_workspace_bytes(n0, n1, n2) bytes of
+ *                  device memory, 0 = bad argument) and writes the totals to counts_out (device int64 [2]: vertices, triangles).
+ *                  Totals of 2^31 and more are the caller's to refuse (the workspace then holds wrapped offsets).
+ *   t2n_mc_emit    takes the workspace as the count call left it for the same volume and level (it fills in the per-node vertex bases,
+ *                  the one region the count call leaves unwritten) and writes verts [V][3] fp32, normals [V][3] fp32 (or NULL: not
+ *                  computed) and faces [T][3] int32; flip != 0 swaps the last two indices of every triple. With zero vertices nothing
+ *                  is written.
+ * Vertex on the edge from node v0 along axis a to v1, fp32, one IEEE operation per step: t = (level - v0) / (v1 - v0), clamped to [0,1]
+ * (fmaxf, then fminf: a NaN becomes 0, so +-inf and NaN neighbours give finite vertices), p_a = (float)index_a + t, world = origin + p *
+ * spacing per component (origin3, spacing3: host float [3]). Normal: node gradients by central differences / (2 spacing), one-sided /
+ * spacing at a border; g = g0 + t * (g1 - g0); -g / |g|, zero where |g| is zero or not finite.
+ * T2N_ERR_INVALID (before any HIP call): NULL pointer, a dimension < 2, n0 * n1 * n2 >= 2^31, a spacing that is not finite and
+ * positive. */
+size_t t2n_mc_workspace_bytes(int n0, int n1, int n2);
+int t2n_mc_count(const float* volume, int n0, int n1, int n2, float level, void* workspace, int64_t* counts_out, t2n_stream stream);
+int t2n_mc_emit(const float* volume, int n0, int n1, int n2, float level, const void* workspace, const float* origin3,
+                const float* spacing3, int flip, float* verts, float* normals_or_null, int32_t* faces, t2n_stream stream);
+
 /* ---- One optimisation step of the reference's loop (text2nerf_main.py:547-601) as ONE submission: TV gradient -> train-mode render
  * (KEEP_CTX) -> t2n_train_loss -> t2n_render_backward (device-side row plan, as T2N_FLAG_DEVICE_ROWS) -> Adam on all 19 tensors ->
  * re-packed head operands, on the caller's stream and three library-owned side streams (forked from / joined into `stream` by events, so

@@ -11,3 +11,4 @@ from .ray_utils import (get_ray_directions, get_ray_directions_blender, get_rays
                         ndc_rays_blender, ndc_rays, sample_pdf, depth2dist, ndc2dist)
 from .sh import eval_sh_bases  # noqa: F401
 from .dataset import DeviceTrainSet  # noqa: F401
+from .mesh import Mesh, marching_cubes, convert_sdf_samples_to_ply, write_ply  # noqa: F401

@@ -1085,6 +1085,41 @@ class TensorBase(nn.Module):
         print(f"bbox: {lo, hi} alpha rest %%%f" % (float(vol.sum()) / total * 100))
         return new_aabb
 
+    @torch.no_grad()
+    def export_mesh(self, path=None, level=0.005, gridSize=None, colors=True, normals=True):
+        """Upstream's `export_mesh` (getDenseAlpha -> convert_sdf_samples_to_ply(alpha.cpu(), path, bbox=aabb.cpu(), level=0.005)) on the
+        device: getDenseAlpha(gridSize), marching cubes at `level`, and with `colors` the field's colour at the vertices. Returns a
+        `text2nerf_amd.mesh.Mesh` of device tensors (verts [V,3] world space, faces [F,3] int32, normals [V,3] or None, colors [V,3]
+        uint8 or None) and writes a binary PLY when `path` is given.
+
+        Spacing: getDenseAlpha's nodes come from linspace(0, 1, g) and span the box, so the node spacing is (aabb[1] - aabb[0]) /
+        (g - 1) and the origin aabb[0]; the mesh lies where the field is. Upstream's convert_sdf_samples_to_ply divides by g instead
+        (its mesh is (g - 1) / g of the scene); `mesh.convert_sdf_samples_to_ply` keeps that arithmetic for callers who want it.
+
+        Colours: shade(normalize_coord(verts), viewdirs=-normals)[1], clamped to [0,1] and rounded to uint8 on the device. The driver's
+        fields use MLP_Fea_noview, whose colour does not depend on the direction. A general-shape field has no `shade`: there
+        colors=True raises T2NError and colors=False works. Faces and normals point towards lower alpha: out of the dense region."""
+        from . import mesh as M
+        if colors and self._is_general():
+            raise T2NError("export_mesh(colors=True) needs the tuned-shape field's shade stage; a general-shape field exports with "
+                           "colors=False")
+        g = [int(x) for x in (self.gridSize if gridSize is None else gridSize)]
+        alpha, _ = self.getDenseAlpha(g)
+        a = self.aabb.detach().float().cpu()
+        spacing = (a[1] - a[0]) / (torch.tensor(g, dtype=torch.float32) - 1)
+        verts, faces, nrm = M.marching_cubes(alpha, level, spacing=spacing.tolist(), origin=a[0].tolist(), normals=bool(normals or colors))
+        rgb8 = None
+        if colors:
+            if verts.shape[0]:
+                rgb = self.shade(self.normalize_coord(verts), viewdirs=-nrm)[1]
+                rgb8 = (rgb.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8)
+            else:
+                rgb8 = torch.empty(0, 3, dtype=torch.uint8, device=verts.device)
+        out = M.Mesh(verts, faces, nrm if normals else None, rgb8)
+        if path is not None:
+            M.write_ply(path, out.verts, out.faces, out.normals, out.colors)
+        return out
+
     # ---- the render call ----------------------------------------------------------------------------------------------------
     def forward(self, rays_chunk, white_bg=True, is_train=False, ndc_ray=False, N_samples=-1, frame_width=None):
         """models/tensorBase.py:436-507: returns (rgb_map [R,3], depth_map [R], z_vals [R,N], weight [R,N]). `frame_width` (not in
