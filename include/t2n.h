@@ -172,6 +172,14 @@ int t2n_alpha_at(const t2n_field* f, const float* xyz_world, int64_t n, float* a
  * handle) = off = the reference's arithmetic sample for sample. Train launches, launches with weights / z_vals outputs and
  * T2N_FLAG_KEEP_CTX launches ignore it. */
 int t2n_field_set_early_termination(t2n_field* f, float eps);
+/* Feature stage of the default render path (k_app_features_p, fp32 factor storage): on = 1 (default of a new handle): per 32-entry
+ * tile and plane / line pair the wave copies the bounding box of the entries' taps into LDS and reads the taps there, where the box
+ * fits (texels of the plane box + taps of the line span <= 64 slots); a pair that does not fit is gathered tap by tap. on = 0:
+ * every pair is gathered; bf16 factor storage is always gathered. The feature rows are the same bit for bit either way.
+ * t2n_field_feature_staging_counts: the (tile, pair) units that ran staged (out[0]) and gathered (out[1]) since the field was
+ * created. A diagnostic: it waits for the whole device (hipDeviceSynchronize), so it must not be called inside a stream capture. */
+int t2n_field_set_feature_staging(t2n_field* f, int on);
+int t2n_field_feature_staging_counts(const t2n_field* f, uint64_t out[2]);
 /* Image width of the row-major frames passed with T2N_FLAG_COHERENT (0 = unknown: the flag is ignored). */
 int t2n_field_set_frame_width(t2n_field* f, int width);
 

@@ -435,6 +435,7 @@ extern "C" int t2n_field_destroy(t2n_field* f) {
     }
     if (f->gbuf_all && !f->gbuf_external) (void)hipFree(f->gbuf_all);
     if (f->buf_mlp) (void)hipFree(f->buf_mlp);
+    if (f->staging_counts) (void)hipFree(f->staging_counts);
     if (f->buf_mlp_h) (void)hipFree(f->buf_mlp_h);
     if (f->buf_ss) (void)hipFree(f->buf_ss);
     if (f->ss_event) (void)hipEventDestroy((hipEvent_t)f->ss_event);
@@ -472,6 +473,10 @@ extern "C" int t2n_field_upload(t2n_field* f, const t2n_field_params* p, t2n_str
         return T2N_ERR_INVALID;
     }
     hipStream_t s = (hipStream_t)stream;
+    if (!f->staging_counts) {
+        T2N_HIP(hipMalloc((void**)&f->staging_counts, 2 * sizeof(unsigned long long)));
+        T2N_HIP(hipMemsetAsync(f->staging_counts, 0, 2 * sizeof(unsigned long long), s));
+    }
     timing_begin(f, T2N_K_UPLOAD, s);
     int rc = launch_relayout(f, p, s);
     if (!rc) rc = launch_pack_mlp(f, p, s);
@@ -906,6 +911,23 @@ extern "C" int t2n_field_set_early_termination(t2n_field* f, float eps) {
 extern "C" int t2n_field_set_mlp_precision(t2n_field* f, int exact_fp32) {
     if (!f) { set_error("t2n_field_set_mlp_precision: NULL field"); return T2N_ERR_INVALID; }
     f->mlp_split = exact_fp32 ? 0 : 1;
+    return T2N_OK;
+}
+
+extern "C" int t2n_field_set_feature_staging(t2n_field* f, int on) {
+    if (!f) { set_error("t2n_field_set_feature_staging: NULL field"); return T2N_ERR_INVALID; }
+    f->feature_staging = on ? 1 : 0;
+    return T2N_OK;
+}
+
+extern "C" int t2n_field_feature_staging_counts(const t2n_field* f, uint64_t out[2]) {
+    if (!f || !out) { set_error("t2n_field_feature_staging_counts: NULL argument"); return T2N_ERR_INVALID; }
+    out[0] = out[1] = 0;
+    if (!f->staging_counts) return T2N_OK;   // nothing uploaded, nothing rendered
+    T2N_HIP(hipDeviceSynchronize());          // the renders that count may sit on any stream
+    unsigned long long h[2];
+    T2N_HIP(hipMemcpy(h, f->staging_counts, sizeof(h), hipMemcpyDeviceToHost));
+    out[0] = h[0]; out[1] = h[1];
     return T2N_OK;
 }
 

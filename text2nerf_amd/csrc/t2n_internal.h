@@ -107,6 +107,8 @@ struct t2n_field {
     unsigned* ss_ok_host = nullptr; void* ss_ok_event = nullptr; int ss_variant = -2;   // head instantiation the packed weights allow: -1 copy in flight, -2 unknown (both launched), 0 untracked, 1 tracked
     float* buf_alpha = nullptr; // alpha-mask volume copy
     int mlp_split = 1;         // 1: f16 two-way split products (default), 0: exact fp32 MFMA
+    int feature_staging = 1;   // feature stage of the default render path: taps from a per-tile texel box in LDS (t2n_field_set_feature_staging)
+    unsigned long long* staging_counts = nullptr;   // device: (tile, pair) units staged / gathered since creation (allocated by the first upload)
     // channel-last gradient accumulators (backward), allocated on first use
     float* gbuf_den_plane[3] = {nullptr, nullptr, nullptr};
     float* gbuf_den_line[3] = {nullptr, nullptr, nullptr};

@@ -300,6 +300,8 @@ struct ShadeArgs {
     const unsigned* split_unsafe;     // device word set at upload when a weight x 2^8 (the one-kernel split path's fixed pre-scale) leaves
                                       // the f16 range: split launches then do nothing (and raise range_flag) and the exact launch behind them runs
     unsigned long long* stats;        // redo launches count themselves in stats[T2N_STAT_F16_REDO]
+    int feature_staging;              // k_app_features_p: read the taps from a per-tile texel box in LDS where it fits
+    unsigned long long* staging_counts;   // k_app_features_p: (tile, pair) units staged / gathered, added per wave
 };
 
 // Gather: 384 (sample, channel-quad) items over 64 lanes, 6 per lane; an item computes its sample's three axis taps once
@@ -977,6 +979,16 @@ __device__ __forceinline__ void gather_pair(const FactorSet& S, float* __restric
 // basis chunks 3K .. 3K+2 (16 K-values each) of f16_stream's operand layout, from X[48][kXld]; the A operands (basis_mat as hi / lo f16
 // halves, 18 KB) sit in the workgroup's LDS: streamed from L1 they were 18 of a tile's 137 load instructions, on a kernel that is bound
 // by the L1's 64 B/clk
+// one chunk: the lane's 8 K-values x[] (rows 16c + 8h .. + 7 of the pair's X) against the chunk's three split products
+__device__ __forceinline__ void basis_chunk(f32x16& acc, const uint4* __restrict__ ap, int c, const float (&x)[8], float& amax) {
+    h8 bhi, blo;
+    split8(x, bhi, blo, amax);
+    const h8 ahi = __builtin_bit_cast(h8, ap[(c * 2) * 64]), alo = __builtin_bit_cast(h8, ap[(c * 2 + 1) * 64]);
+    acc = mfma16(ahi, bhi, acc);
+    acc = mfma16(ahi, blo, acc);
+    acc = mfma16(alo, bhi, acc);
+    asm volatile("" : "+v"(amax));   // the range tracking of this chunk is due here (deferred to the loop's end, its 8 values are spilled)
+}
 template <int K>
 __device__ __forceinline__ void pair_basis(f32x16& acc, const uint4* __restrict__ Wl, const float* __restrict__ Xs, int h, int lane, float& amax) {
     const uint4* __restrict__ ap = Wl + lane + (3 * K) * 2 * 64;
@@ -986,13 +998,183 @@ __device__ __forceinline__ void pair_basis(f32x16& acc, const uint4* __restrict_
         const float* p = Xs + (size_t)(16 * c + 8 * h) * kXld;
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] = p[e * kXld];
-        h8 bhi, blo;
-        split8(x, bhi, blo, amax);
-        const h8 ahi = __builtin_bit_cast(h8, ap[(c * 2) * 64]), alo = __builtin_bit_cast(h8, ap[(c * 2 + 1) * 64]);
-        acc = mfma16(ahi, bhi, acc);
-        acc = mfma16(ahi, blo, acc);
-        acc = mfma16(alo, bhi, acc);
-        asm volatile("" : "+v"(amax));   // the range tracking of this chunk is due here (deferred to the loop's end, its 8 values are spilled)
+        basis_chunk(acc, ap, c, x, amax);
+    }
+}
+
+// ---- staged taps: a tile's 32 entries are ~5 neighbouring rays x ~7 consecutive steps, so the 32 x 6 taps of a plane / line pair fall
+// into a few dozen distinct texels. Per pair the wave copies the bounding box of its live entries' taps (plane box + line span) into
+// LDS, one 16-channel chunk at a time, and every lane reads its taps there: ~2 wave-wide 16-B loads per chunk instead of 12. The box
+// lives where the gather path keeps X (the staged path needs no X: lane (s, h) of the basis product owns rows 16c + 8h .. + 7 of
+// sample s, which are quads 4c + 2h and 4c + 2h + 1 - it computes exactly those from the box and feeds them to the product). Same
+// texel values, same multiply / fma chain per channel, same chunk order: the feature rows are bit-identical to the gather's.
+// A pair whose box does not fit (a tile that straddles two marcher regions, rays more than a voxel apart, stale slots of an
+// overflowed list) runs gather_pair + pair_basis as before.
+constexpr int kBoxSlots = 64;    // box slots per wave: the plane box and the line span of a pair share them
+constexpr int kBoxSlot = 80;     // bytes per box slot: 4 quads + 16 B of padding - a 20-bank stride, so the 16 lanes of a
+                                 // ds_read_b128 group hit 16 consecutive slots without a conflict
+constexpr int kBoxLoads = kBoxSlots * 4 / 64;   // wave-wide 16-B loads per chunk at most
+static_assert(kBoxSlots * kBoxSlot <= kPairRows * kXld * 4, "the box aliases X");
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+struct TileBox { int lo[3], hi[3]; };   // per axis: min / max low-tap index over the tile's live entries (wave-uniform)
+
+template <int O>
+__device__ __forceinline__ void box_min_step(unsigned (&v)[3]) {
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const unsigned t = (unsigned)__builtin_amdgcn_ds_swizzle((int)v[k], (O << 10) | 0x1f);
+        v[k] = __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(u16x2, v[k]), __builtin_bit_cast(u16x2, t)));
+    }
+}
+// lanes 0..31 hold (ix, iy, iz) of their entry; `live` is false in dead entries and in the upper half-wave. One packed 16-bit
+// min per axis over (i, 0xffff - i): five exchange steps for all six bounds (tap indices are < 2^16).
+__device__ __forceinline__ TileBox tile_box(int ix, int iy, int iz, bool live) {
+    unsigned v[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
+    if (live) {
+        v[0] = (unsigned)ix | ((0xffffu - (unsigned)ix) << 16);
+        v[1] = (unsigned)iy | ((0xffffu - (unsigned)iy) << 16);
+        v[2] = (unsigned)iz | ((0xffffu - (unsigned)iz) << 16);
+    }
+    // (ds_swizzle, bit mode: lane ^ O within each half-wave - no address register to keep alive across the tile loop)
+    box_min_step<1>(v); box_min_step<2>(v); box_min_step<4>(v); box_min_step<8>(v); box_min_step<16>(v);
+    TileBox b;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const unsigned u = (unsigned)__builtin_amdgcn_readfirstlane((int)v[k]);
+        b.lo[k] = (int)(u & 0xffffu); b.hi[k] = (int)(0xffffu - (u >> 16));
+    }
+    return b;
+}
+
+// Census builds only (profiles/feature_staging_count_table.txt): 1 compiles the staged form alone, 2 the gathered form alone, so that
+// tools/featp_count_table.py counts the tile loop of ONE form. Such an object is for reading, never for running: form 1 has no fallback.
+#ifndef T2N_FEATP_FORM
+#define T2N_FEATP_FORM 0
+#endif
+// pair K of a tile: box origin, extents (high taps included: hi - lo + 2) and whether it fits the LDS box. All wave-uniform.
+struct PairBox { int a0, b0, l0, na, npl, nl; bool fits; };
+template <int K>
+__device__ __forceinline__ PairBox pair_box(const TileBox& t, unsigned nlive, bool on) {
+    PairBox p;
+    p.a0 = t.lo[mat0(K)]; p.b0 = t.lo[mat1(K)]; p.l0 = t.lo[vecm(K)];
+    p.na = t.hi[mat0(K)] - p.a0 + 2;
+    const int nb = t.hi[mat1(K)] - p.b0 + 2;
+    p.nl = t.hi[vecm(K)] - p.l0 + 2;
+    p.npl = p.na * nb;
+    if constexpr (T2N_FEATP_FORM == 1) p.fits = true;
+    else if constexpr (T2N_FEATP_FORM == 2) p.fits = false;
+    else p.fits = on && nlive > 0u && p.na >= 2 && nb >= 2 && p.nl >= 2 && p.na <= kBoxSlots && nb <= kBoxSlots && p.nl <= kBoxSlots &&
+             p.npl + p.nl <= kBoxSlots;
+    return p;
+}
+
+// Staging item i = 64 j + lane -> (box slot i >> 2, quad i & 3): slots [0, npl) are the plane box row by row, [npl, npl + nl) the
+// line span. Box column i holds texel min(a0 + i, W - 1) (rows and line taps alike): the clamp of parked_axes, so a high tap is
+// always the low tap's slot + 1, at the border too. gp[j]: the item's address in its plane or line (chunk 0).
+template <int K>
+__device__ __forceinline__ void stage_offsets(const FactorSet& S, const PairBox& p, int lane, const char* (&gp)[kBoxLoads]) {
+    asm volatile("" : "+v"(lane));   // (as in gather_pair: the per-lane item maps are not hoisted out of the tile loop and spilled)
+    const unsigned W = (unsigned)S.W[K];
+    const unsigned rcp = 65536u / (unsigned)p.na + 1u;   // slot / na for slot < 64 <= 65536 / na: exact
+    const char* __restrict__ Pb = reinterpret_cast<const char*>(S.plane[K]);
+    const char* __restrict__ Lb = reinterpret_cast<const char*>(S.line[K]);
+#pragma unroll
+    for (int j = 0; j < kBoxLoads; ++j) {
+        const unsigned i = (unsigned)(j * 64 + lane), t = i >> 2, qq = i & 3u;
+        const unsigned by = __umul24(t, rcp) >> 16, bx = t - __umul24(by, (unsigned)p.na);   // (t < 2^8, rcp < 2^16: 24-bit products)
+        const unsigned x = min((unsigned)p.a0 + bx, W - 1u), y = min((unsigned)p.b0 + by, (unsigned)S.H[K] - 1u);
+        const unsigned tap = min((unsigned)p.l0 + (t - (unsigned)p.npl), (unsigned)S.L[K] - 1u);
+        const bool ln = t >= (unsigned)p.npl;
+        const unsigned texel = ln ? tap : umad24(y, W, x);
+        gp[j] = (ln ? Lb : Pb) + umad24(texel, 12u * 16u, qq * 16u);   // chunk c of the item: + 64 c, an immediate of the load
+    }
+}
+template <int K>
+__device__ __forceinline__ void stage_load(const PairBox& p, int lane, int c, const char* const (&gp)[kBoxLoads], f32x4 (&r)[kBoxLoads]) {
+    asm volatile("" : "+v"(lane));
+    const int nitems = (p.npl + p.nl) * 4;
+#pragma unroll
+    for (int j = 0; j < kBoxLoads; ++j) {
+        if (j * 64 < nitems) {   // wave-uniform
+            if (j * 64 + lane < nitems) r[j] = *reinterpret_cast<const f32x4*>(gp[j] + c * 64);
+        }
+    }
+}
+// item i = 64 j + lane lands at slot (lane >> 2) + 16 j, quad lane & 3: one address per lane, the rest an immediate of the store
+__device__ __forceinline__ void stage_store(char* __restrict__ B, const PairBox& p, int lane, const f32x4 (&r)[kBoxLoads]) {
+    asm volatile("" : "+v"(lane));
+    const int nitems = (p.npl + p.nl) * 4;
+    char* __restrict__ d = B + __mul24(lane >> 2, kBoxSlot) + (lane & 3) * 16;
+#pragma unroll
+    for (int j = 0; j < kBoxLoads; ++j) {
+        if (j * 64 < nitems) {
+            if (j * 64 + lane < nitems) *reinterpret_cast<f32x4*>(d + j * 16 * kBoxSlot) = r[j];
+        }
+    }
+}
+
+// the first chunk of pair K on its way (nothing when the pair does not fit)
+template <int K>
+__device__ __forceinline__ void stage_first(const FactorSet& S, const PairBox& p, int lane, const char* (&gp)[kBoxLoads], f32x4 (&r)[kBoxLoads]) {
+    // (the loads below write the lanes that hold an item only, so the old contents of r stay alive up to here - across a whole
+    // gathered pair, which has no registers to spare: start from constants)
+#pragma unroll
+    for (int j = 0; j < kBoxLoads; ++j) { r[j] = f32x4{0.f, 0.f, 0.f, 0.f}; gp[j] = nullptr; }
+    if (p.fits) {   // wave-uniform
+        stage_offsets<K>(S, p, lane, gp);
+        stage_load<K>(p, lane, 0, gp, r);
+    }
+}
+
+// Pair K from the box. On entry chunk 0 of the pair is in flight in r (stage_first<K>); once the last chunk's texels are in LDS
+// and gp / r are free again, the next pair's first chunk is sent on its way (pn: its box).
+template <int K>
+__device__ __forceinline__ void staged_pair(const FactorSet& S, f32x16& acc, const uint4* __restrict__ Wl, char* __restrict__ B,
+                                            const float4* __restrict__ P, const PairBox& p, const PairBox& pn, const char* (&gp)[kBoxLoads],
+                                            f32x4 (&r)[kBoxLoads], int s, int h, int lane, unsigned nlive, float& amax) {
+    asm volatile("" : "+v"(lane), "+v"(s), "+v"(h));   // (the lane's LDS addresses are rebuilt per pair, not hoisted and spilled)
+    const uint4* __restrict__ ap = Wl + lane + (3 * K) * 2 * 64;
+    const bool live = (unsigned)s < nlive;
+    const float4 pi = P[2 * s], pw = P[2 * s + 1];
+    const int idx[3] = {__float_as_int(pi.x), __float_as_int(pi.y), __float_as_int(pi.z)};
+    const float w1[3] = {pw.x, pw.y, pw.z};
+    // dead entries sit at the volume centre, outside the box: they read slot 0 and store zeros
+    const int jx = live ? idx[mat0(K)] - p.a0 : 0, jy = live ? idx[mat1(K)] - p.b0 : 0, jl = live ? idx[vecm(K)] - p.l0 : 0;
+    const float ax1 = w1[mat0(K)], ay1 = w1[mat1(K)], al1 = w1[vecm(K)];
+    const float ax0 = 1.f - ax1, ay0 = 1.f - ay1, al0 = 1.f - al1;
+    QuadTaps t;
+    t.wnw = ay0 * ax0; t.wne = ay0 * ax1; t.wsw = ay1 * ax0; t.wse = ay1 * ax1;
+    t.wl0 = al0; t.wl1 = al1;
+    const char* __restrict__ r0 = B + __mul24(__mul24(jy, p.na) + jx, kBoxSlot) + h * 32;
+    const char* __restrict__ r1 = r0 + p.na * kBoxSlot;
+    const char* __restrict__ rl = B + __mul24(p.npl + jl, kBoxSlot) + h * 32;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        stage_store(B, p, lane, r);
+        wave_lds_sync();
+        if (c < 2) stage_load<K>(p, lane, c + 1, gp, r);
+        else if constexpr (K < 2) stage_first<K + 1>(S, pn, lane, gp, r);
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            t.nw = *reinterpret_cast<const float4*>(r0 + 16 * j); t.ne = *reinterpret_cast<const float4*>(r0 + kBoxSlot + 16 * j);
+            t.sw = *reinterpret_cast<const float4*>(r1 + 16 * j); t.se = *reinterpret_cast<const float4*>(r1 + kBoxSlot + 16 * j);
+            t.l0 = *reinterpret_cast<const float4*>(rl + 16 * j); t.l1 = *reinterpret_cast<const float4*>(rl + kBoxSlot + 16 * j);
+            float4 pv = taps_plane(t);
+            // (kept apart from the line's chain: left together, the vectoriser pairs the last plane fma with the line fma into
+            // v_pk_fma_f32 and pays for it in register moves)
+            asm("" : "+v"(pv.x), "+v"(pv.y), "+v"(pv.z), "+v"(pv.w));
+            const float4 l = taps_line(t);
+            float4 v = make_float4(pv.x * l.x, pv.y * l.y, pv.z * l.z, pv.w * l.w);
+            if (!live) v = make_float4(0.f, 0.f, 0.f, 0.f);
+            x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
+            // (fenced: unfenced, both quads' twelve taps are read up front - 48 registers - and the staging addresses are spilled)
+            if (j == 0) __builtin_amdgcn_sched_barrier(0);
+        }
+        basis_chunk(acc, ap, c, x, amax);
+        wave_lds_sync();   // the chunk's box reads are done before the next chunk (or the next pair's gather) overwrites it
     }
 }
 
@@ -1003,7 +1185,6 @@ template <bool HALF>
 __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_app_features_p(const ShadeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int s = lane & 31, h = lane >> 5;
     uint4* __restrict__ Wl = reinterpret_cast<uint4*>(smem);
     float* __restrict__ X = smem + kPairBasisVec * 4 + (size_t)wid * kPairFloats;
     float4* __restrict__ P = reinterpret_cast<float4*>(X + kPairRows * kXld);
@@ -1029,6 +1210,7 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
     }
     const unsigned wave_stride = gridDim.x * (unsigned)kPairWaves;
     float amax = 0.f;
+    unsigned n_staged = 0u, n_gathered = 0u;
     // tile -> (first entry, live entries) and the lane's position entry (lanes 0..31; dead entries sit at the volume centre and
     // store zeros); the next tile's positions are fetched while this tile is processed
     auto locate = [&](unsigned tile, unsigned& base, unsigned& nlive, float4& mine) {
@@ -1048,42 +1230,88 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
     locate(blockIdx.x * (unsigned)kPairWaves + wid, base, nlive, mine);
     for (unsigned tile = blockIdx.x * (unsigned)kPairWaves + wid; tile < ntiles; tile += wave_stride, base = nbase, nlive = nnlive, mine = nmine) {
         asm volatile("; FEATP_MARK tile_begin");   // (tools/featp_count_table.py: the tile loop's instructions by mnemonic)
-        if (lane < 32) {   // (dead entries sit at the volume centre: in the box like every list entry)
+        // the lane index behind an opaque copy, per tile: visible, the lane's LDS addresses and item maps are hoisted out of the tile
+        // loop and spilled (the staged and the gathered form together hold more of them than the register file has room for)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const int sl = ln & 31, hl = ln >> 5;
+        int ix = 0, iy = 0, iz = 0;
+        if (ln < 32) {   // (dead entries sit at the volume centre: in the box like every list entry)
             const Axes3 A = sample_axes_inbox(F.app, mine.x, mine.y, mine.z);
             // list slots that were reserved but never written (a budgeted launch that overflowed: this kernel is already queued when
             // the host learns of it) hold stale workspace bytes: whatever they decode to, the taps stay inside the planes
             // (parked_axes: high tap = min(low + 1, size - 1)); such rows belong to no ray's slice and are never composited
-            const int ix = min(max(A.a[0].i0, 0), F.app.W[0] - 1), iy = min(max(A.a[1].i0, 0), F.app.H[0] - 1),
-                      iz = min(max(A.a[2].i0, 0), F.app.H[1] - 1);
-            P[2 * lane] = make_float4(__int_as_float(ix), __int_as_float(iy), __int_as_float(iz), mine.w);
-            P[2 * lane + 1] = make_float4(A.a[0].w1, A.a[1].w1, A.a[2].w1, 0.f);
+            ix = min(max(A.a[0].i0, 0), F.app.W[0] - 1); iy = min(max(A.a[1].i0, 0), F.app.H[0] - 1);
+            iz = min(max(A.a[2].i0, 0), F.app.H[1] - 1);
+            P[2 * ln] = make_float4(__int_as_float(ix), __int_as_float(iy), __int_as_float(iz), mine.w);
+            P[2 * ln + 1] = make_float4(A.a[0].w1, A.a[1].w1, A.a[2].w1, 0.f);
         }
         locate(tile + wave_stride, nbase, nnlive, nmine);
         wave_lds_sync();
         f32x16 acc = {0};
-        gather_pair<0, HALF>(F.app, X, P, lane, nlive);
-        wave_lds_sync();
-        pair_basis<0>(acc, Wl, X + s, h, lane, amax);
-        wave_lds_sync();
-        gather_pair<1, HALF>(F.app, X, P, lane, nlive);
-        wave_lds_sync();
-        pair_basis<1>(acc, Wl, X + s, h, lane, amax);
-        wave_lds_sync();
-        gather_pair<2, HALF>(F.app, X, P, lane, nlive);
-        wave_lds_sync();
-        pair_basis<2>(acc, Wl, X + s, h, lane, amax);
+        if constexpr (HALF) {   // bf16 storage keeps the gather (8-B texels: half the bytes already)
+            gather_pair<0, HALF>(F.app, X, P, ln, nlive);
+            wave_lds_sync();
+            pair_basis<0>(acc, Wl, X + sl, hl, ln, amax);
+            wave_lds_sync();
+            gather_pair<1, HALF>(F.app, X, P, ln, nlive);
+            wave_lds_sync();
+            pair_basis<1>(acc, Wl, X + sl, hl, ln, amax);
+            wave_lds_sync();
+            gather_pair<2, HALF>(F.app, X, P, ln, nlive);
+            wave_lds_sync();
+            pair_basis<2>(acc, Wl, X + sl, hl, ln, amax);
+            n_gathered += 3u;
+        } else {
+            // staged where the pair's tap box fits the wave's LDS box, gathered where it does not (wave-uniform, per pair)
+            const TileBox tb = tile_box(ix, iy, iz, ln < 32 && (unsigned)ln < nlive);
+            const bool on = a.feature_staging != 0;
+            const PairBox b0 = pair_box<0>(tb, nlive, on), b1 = pair_box<1>(tb, nlive, on), b2 = pair_box<2>(tb, nlive, on);
+            char* __restrict__ B = reinterpret_cast<char*>(X);
+            const char* gp[kBoxLoads];
+            f32x4 r[kBoxLoads];
+            stage_first<0>(F.app, b0, ln, gp, r);
+            if (b0.fits) staged_pair<0>(F.app, acc, Wl, B, P, b0, b1, gp, r, sl, hl, ln, nlive, amax);
+            else {
+                gather_pair<0, HALF>(F.app, X, P, ln, nlive);
+                wave_lds_sync();
+                pair_basis<0>(acc, Wl, X + sl, hl, ln, amax);
+                wave_lds_sync();
+                stage_first<1>(F.app, b1, ln, gp, r);
+            }
+            if (b1.fits) staged_pair<1>(F.app, acc, Wl, B, P, b1, b2, gp, r, sl, hl, ln, nlive, amax);
+            else {
+                gather_pair<1, HALF>(F.app, X, P, ln, nlive);
+                wave_lds_sync();
+                pair_basis<1>(acc, Wl, X + sl, hl, ln, amax);
+                wave_lds_sync();
+                stage_first<2>(F.app, b2, ln, gp, r);
+            }
+            if (b2.fits) staged_pair<2>(F.app, acc, Wl, B, P, b2, b2, gp, r, sl, hl, ln, nlive, amax);
+            else {
+                gather_pair<2, HALF>(F.app, X, P, ln, nlive);
+                wave_lds_sync();
+                pair_basis<2>(acc, Wl, X + sl, hl, ln, amax);
+            }
+            const unsigned ns = (b0.fits ? 1u : 0u) + (b1.fits ? 1u : 0u) + (b2.fits ? 1u : 0u);
+            n_staged += ns; n_gathered += 3u - ns;
+        }
         const f32x16 accb = acc * kWUnscale;
         // lane (s, h) register v holds feature (v & 3) + 8 (v >> 2) + 4 h: four float4 stores per lane. Column 27 (a zero of the
         // padded basis) carries the entry's compositing weight to the head, which hands it on in app_rgb.w
-        float* __restrict__ row = a.ctx.feat32 + ((size_t)tile * 32 + s) * 32 + 4 * h;
-        const float wgt = (h == 0 && (unsigned)s < nlive) ? P[2 * s].w : 0.f;   // lane (s, 0) holds columns 24..27 in registers 12..15
+        float* __restrict__ row = a.ctx.feat32 + ((size_t)tile * 32 + sl) * 32 + 4 * hl;
+        const float wgt = (hl == 0 && (unsigned)sl < nlive) ? P[2 * sl].w : 0.f;   // lane (s, 0) holds columns 24..27 in registers 12..15
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<float4*>(row + 8 * g) = make_float4(accb[4 * g], accb[4 * g + 1], accb[4 * g + 2], (g == 3 && h == 0) ? wgt : accb[4 * g + 3]);
+            *reinterpret_cast<float4*>(row + 8 * g) = make_float4(accb[4 * g], accb[4 * g + 1], accb[4 * g + 2], (g == 3 && hl == 0) ? wgt : accb[4 * g + 3]);
         wave_lds_sync();   // X and P reads done before the next tile overwrites them
         asm volatile("; FEATP_MARK tile_end");
     }
     if (a.range_flag && __any(!(amax <= 60000.f)) && lane == 0) atomicOr(a.range_flag, 1u);
+    if (a.staging_counts && lane == 0) {   // (tile, pair) units of this wave: staged / gathered
+        if (n_staged) atomicAdd(a.staging_counts, (unsigned long long)n_staged);
+        if (n_gathered) atomicAdd(a.staging_counts + 1, (unsigned long long)n_gathered);
+    }
 }
 
 // ---- block-cooperative variant (default render path, split-f16 MLP head) ---------------------------------------------
@@ -1664,6 +1892,7 @@ int launch_shade_list(t2n_field* f, const float4* app_pos, const int* app_ray, c
         fa.ctx = ShadeCtx{nullptr, feat, nullptr, nullptr};
         fa.ctx_rows = ws_tiles * 32u; fa.tile_hi = ws_tiles;
         fa.range_flag = flag; fa.split_unsafe = f->split_unsafe;
+        fa.feature_staging = f->feature_staging; fa.staging_counts = f->staging_counts;
         timing_begin(f, T2N_K_APPFEAT, s);
         {
             const size_t lds_p = (size_t)kPairBasisVec * 16 + (size_t)kPairWaves * kPairFloats * sizeof(float);

@@ -364,6 +364,8 @@ class TensorBase(nn.Module):
         self.frame_width = 0              # set to the image width when eval rays are whole row-major frames: enables the
                                           # 8x8-tile marcher (shared dot-product tables); 0 = unknown -> per-ray marcher
         self.mlp_exact_fp32 = False       # False: f16 two-way-split MFMA products; True: exact fp32 MFMA (forward and backward)
+        self.feature_staging = True       # feature stage of eval frames: taps read from a per-tile texel box in LDS where it fits
+                                          # (same rows bit for bit; False = every tap gathered); see feature_staging_counts()
         # 'fp32' (default) or 'bf16' (BASELINE configs[4]): the forward gathers read bf16 copies of the 12 factor tensors;
         # the render equals the fp32 render of the bf16-rounded tensors bit for bit, the parameters stay fp32 masters
         self.factor_storage = "fp32"
@@ -799,6 +801,7 @@ class TensorBase(nn.Module):
             self._term_set = None
             self._storage_set = None
             self._frame_w_set = None
+            self._staging_set = None
             self._head_rows_set = 32
             self._alpha_key = "unset"
         queued = False     # device work queued by this call (mask / parameter uploads)
@@ -832,6 +835,10 @@ class TensorBase(nn.Module):
             _lib.check(lib.t2n_field_set_mlp_precision(self._handle, 1 if self.mlp_exact_fp32 else 0),
                        "t2n_field_set_mlp_precision")
             self._precision_set = bool(self.mlp_exact_fp32)
+        if getattr(self, "_staging_set", None) != bool(self.feature_staging):
+            _lib.check(lib.t2n_field_set_feature_staging(self._handle, 1 if self.feature_staging else 0),
+                       "t2n_field_set_feature_staging")
+            self._staging_set = bool(self.feature_staging)
         # (rayMarch_weight_thres = 0 — `weight > thres`, models/tensorBase.py:477 — is a legitimate setting: 0 then means off)
         et = max(0.0, min(float(self.early_termination or 0.0), float(self.rayMarch_weight_thres)))
         if getattr(self, "_term_set", None) != et:
@@ -1550,6 +1557,15 @@ class TensorBase(nn.Module):
             raise T2NError("appearance list overflow — workspace sizing bug")
         return {"evaluated": s[_lib.STAT_EVALUATED], "appearance": s[_lib.STAT_APPEARANCE], "f16_redo": s[_lib.STAT_F16_REDO],
                 "list_retry": s[_lib.STAT_LIST_RETRY]}
+
+    def feature_staging_counts(self):
+        """(staged, gathered): the (tile, plane / line pair) units of the feature stage that read their taps from the LDS box and
+        the units that gathered them, since the native field was created. Waits for the device."""
+        if self._handle is None:
+            return (0, 0)
+        out = (C.c_uint64 * 2)()
+        _lib.check(_lib.load().t2n_field_feature_staging_counts(self._handle, out), "t2n_field_feature_staging_counts")
+        return (int(out[0]), int(out[1]))
 
 
 class TensorVMSplit(TensorBase):
