@@ -654,6 +654,40 @@ int t2n_mc_count(const float* volume, int n0, int n1, int n2, float level, void*
 int t2n_mc_emit(const float* volume, int n0, int n1, int n2, float level, const void* workspace, const float* origin3,
                 const float* spacing3, int flip, float* verts, float* normals_or_null, int32_t* faces, t2n_stream stream);
 
+/* ---- Mesh export: connected components of a triangle list and removal of the unwanted ones ("floaters") on the device, the stage
+ * behind marching cubes that users of upstream's --export_mesh run on the host (MeshLab, trimesh). All integer: every output is a
+ * function of the input alone, two calls give bit-equal arrays. faces [F][3] int32 into n_verts vertices.
+ *   connectivity   two vertices are connected when a face contains both; a vertex that no face references is a component of its own
+ *                  with 0 faces. A face with an index outside [0, n_verts) violates the precondition (the Python layer checks it):
+ *                  every kernel skips such a face and never touches memory through it.
+ *   labels         dense, 0 .. K-1, numbered in the order of each component's SMALLEST vertex index (vertex 0 is in component 0).
+ *   t2n_mesh_components       fills labels [V] int32 and K (n_components_out: device int64 [1]). Lock-free union-find: parent[v] = v,
+ *                  one thread per face unites (f0,f1) and (f1,f2): find both roots, atomicMin(&parent[hi], lo); a returned value other
+ *                  than hi means hi was no longer a root and the thread goes on uniting (returned value, lo). parent[x] <= x only ever
+ *                  decreases, so a component's final root is its smallest vertex whatever order the threads ran in. Then flatten,
+ *                  exclusive scan of the root flags (per-256 sums, one workgroup with a running carry), labels = rank of the root.
+ *   t2n_mesh_component_sizes  vert_counts [K] and face_counts [K] int32 (a face counts for the component of its first vertex); integer
+ *                  atomics, equal labels combined inside a wave first.
+ *   t2n_mesh_filter_count     keep [K] uint8: per-vertex flags keep[labels[v]], per-face flags through the face's first vertex, two
+ *                  exclusive scans into the workspace, the totals to totals_out (device int64 [2]: vertices, faces).
+ *   t2n_mesh_filter_emit      takes the workspace as the count call left it for the same arguments and writes the kept vertex rows
+ *                  (verts [V'][3] fp32, normals [V'][3] fp32 or NULL, colors [V'][3] uint8 or NULL: in and out NULL together) and the
+ *                  kept faces re-indexed, both in their input order. No atomics. With zero kept vertices nothing is written.
+ * One workspace serves all four: t2n_mesh_components_workspace_bytes(n_verts, n_faces) bytes of device memory (0 = bad argument).
+ * T2N_ERR_INVALID (before any HIP call): NULL required pointer, a negative count, n_verts >= 2^31, 3 * n_faces >= 2^31, n_components
+ * outside [0, n_verts], workspace_bytes smaller than required. */
+size_t t2n_mesh_components_workspace_bytes(int64_t n_verts, int64_t n_faces);
+int t2n_mesh_components(const int32_t* faces, int64_t n_faces, int64_t n_verts, int32_t* labels, int64_t* n_components_out, void* workspace,
+                        size_t workspace_bytes, t2n_stream stream);
+int t2n_mesh_component_sizes(const int32_t* faces, int64_t n_faces, const int32_t* labels, int64_t n_verts, int64_t n_components,
+                             int32_t* vert_counts, int32_t* face_counts, t2n_stream stream);
+int t2n_mesh_filter_count(const int32_t* faces, int64_t n_faces, const int32_t* labels, int64_t n_verts, const uint8_t* keep,
+                          int64_t n_components, void* workspace, size_t workspace_bytes, int64_t* totals_out, t2n_stream stream);
+int t2n_mesh_filter_emit(const int32_t* faces, int64_t n_faces, const int32_t* labels, int64_t n_verts, const uint8_t* keep,
+                         int64_t n_components, const float* verts, const float* normals_or_null, const uint8_t* colors_or_null,
+                         void* workspace, size_t workspace_bytes, float* verts_out, float* normals_out_or_null,
+                         uint8_t* colors_out_or_null, int32_t* faces_out, t2n_stream stream);
+
 /* ---- One optimisation step of the reference's loop (text2nerf_main.py:547-601) as ONE submission: TV gradient -> train-mode render
  * (KEEP_CTX) -> t2n_train_loss -> t2n_render_backward (device-side row plan, as T2N_FLAG_DEVICE_ROWS) -> Adam on all 19 tensors ->
  * re-packed head operands, on the caller's stream and three library-owned side streams (forked from / joined into `stream` by events, so

@@ -12,3 +12,4 @@ from .ray_utils import (get_ray_directions, get_ray_directions_blender, get_rays
 from .sh import eval_sh_bases  # noqa: F401
 from .dataset import DeviceTrainSet  # noqa: F401
 from .mesh import Mesh, marching_cubes, convert_sdf_samples_to_ply, write_ply  # noqa: F401
+from .mesh import Components, mesh_components, filter_components  # noqa: F401

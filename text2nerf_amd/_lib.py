@@ -138,6 +138,13 @@ SIGNATURES = {
     "t2n_mc_count": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2n_mc_emit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2n_mesh_components_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "t2n_mesh_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_mesh_component_sizes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2n_mesh_filter_count": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_void_p]),
+    "t2n_mesh_filter_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2n_field_grad_buffer_bytes": (C.c_size_t, [C.c_void_p]),
     "t2n_field_set_grad_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "t2n_field_grad_buffer_density_bytes": (C.c_size_t, [C.c_void_p]),

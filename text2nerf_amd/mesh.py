@@ -6,10 +6,21 @@ writer, in the place of `skimage.measure.marching_cubes` on a host copy followed
     convert_sdf_samples_to_ply   the reference's function, signature and defaults (tests/golden/mesh_signatures.json)
     write_ply                    binary little-endian PLY by numpy `tofile`, property names as plyfile writes them
     Mesh                         what `TensorBase.export_mesh` returns: verts, faces, normals, colors
+    mesh_components              faces, n_verts -> Components(labels, n_components, vert_counts, face_counts)
+    filter_components            a Mesh without its unwanted components ("floaters"): min_faces and / or keep_largest
 
 The meshes are closed oriented 2-manifolds (the case table is generated from rules, tools/gen_mc_table.py); the right-hand normal of
 every triangle, and every vertex normal, points towards LOWER values: out of the dense region of an alpha volume. Vertex and face order
-are functions of the input alone (no atomics): two calls give bit-equal arrays. No CPU fallback."""
+are functions of the input alone (no atomics): two calls give bit-equal arrays. No CPU fallback.
+
+A Text2NeRF alpha volume at the export level holds the scene's surface plus detached blobs. The documented route to a usable mesh:
+
+    m = tensorf.export_mesh(None)                 # colours and normals as before
+    m = filter_components(m, keep_largest=1)      # or min_faces=...
+    write_ply("scene.ply", *m)
+
+Components are all-integer (lock-free union-find whose roots are each component's smallest vertex, integer counts, scans): labels,
+counts and the compacted arrays are functions of the face list alone as well."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,9 +40,16 @@ class Mesh(NamedTuple):
     colors: Optional[torch.Tensor]      # [V,3] uint8, or None
 
 
+class Components(NamedTuple):
+    labels: torch.Tensor                # [V] int32, 0 .. K-1 in the order of each component's smallest vertex index
+    n_components: int                   # K
+    vert_counts: torch.Tensor           # [K] int32
+    face_counts: torch.Tensor           # [K] int32
+
+
 def _device():
     if not torch.cuda.is_available():
-        raise _lib.T2NError("marching_cubes runs on the MI355X only (no CPU fallback)")
+        raise _lib.T2NError("the mesh stages run on the MI355X only (no CPU fallback)")
     return torch.device("cuda", torch.cuda.current_device())
 
 
@@ -85,6 +103,146 @@ def marching_cubes(volume, level, spacing=(1., 1., 1.), origin=(0., 0., 0.), nor
     if on_device:
         return verts, faces, norms
     return verts.cpu().numpy(), faces.cpu().numpy(), None if norms is None else norms.cpu().numpy()
+
+
+# ---- connected components and floater removal -----------------------------------------------------------------------------------------
+def _is_device(x):
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+def _faces_on_device(faces, n_verts, who):
+    """faces as a contiguous int32 device tensor [F,3], every index inside [0, n_verts): ValueError otherwise, before any launch of
+    ours (one device min / max, read once)."""
+    t = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(faces))
+    if t.dim() != 2 or t.shape[1] != 3 or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"{who}: faces of shape {tuple(t.shape)} and dtype {t.dtype}, need [F,3] integer")
+    V = int(n_verts)
+    if V < 0 or V >= 2**31 or 3 * t.shape[0] >= 2**31:
+        raise ValueError(f"{who}: {V} vertices and {t.shape[0]} faces (need 0 <= V < 2^31 and 3 F < 2^31)")
+    dev = t.device if t.is_cuda else _device()
+    t = t.detach().to(dev)
+    if t.shape[0]:
+        lo, hi = (int(x) for x in torch.stack(torch.aminmax(t)).cpu().tolist())
+        if lo < 0 or hi >= V:
+            raise ValueError(f"{who}: face indices span [{lo}, {hi}], outside [0, {V})")
+    return t.to(torch.int32).contiguous(), dev
+
+
+def _components(lib, f, V, dev):
+    """Components of checked device faces; device tensors."""
+    F = int(f.shape[0])
+    labels = torch.empty(V, dtype=torch.int32, device=dev)
+    if V == 0:                                                  # nothing is launched
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return Components(labels, 0, e, e.clone()), None
+    with torch.cuda.device(dev):
+        nbytes = int(lib.t2n_mesh_components_workspace_bytes(V, F))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        k = torch.empty(1, dtype=torch.int64, device=dev)
+        stream = _lib.current_stream_ptr(dev)
+        _lib.check(lib.t2n_mesh_components(_lib.ptr(f), F, V, _lib.ptr(labels), _lib.ptr(k), _lib.ptr(ws), nbytes, stream),
+                   "t2n_mesh_components")
+        K = int(k.cpu().item())                                 # the one 8-byte read
+        vc = torch.empty(K, dtype=torch.int32, device=dev)
+        fc = torch.empty(K, dtype=torch.int32, device=dev)
+        _lib.check(lib.t2n_mesh_component_sizes(_lib.ptr(f), F, _lib.ptr(labels), V, K, _lib.ptr(vc), _lib.ptr(fc), stream),
+                   "t2n_mesh_component_sizes")
+    return Components(labels, K, vc, fc), ws
+
+
+@torch.no_grad()
+def mesh_components(faces, n_verts):
+    """Connected components of a triangle list: Components(labels [V] int32, n_components K, vert_counts [K] int32, face_counts [K]
+    int32). faces [F,3] integer: a device tensor (device tensors come back) or a numpy array / CPU tensor (numpy arrays come back,
+    through the device). Two vertices are connected when a face contains both; a vertex that no face references is a component of its
+    own with 0 faces. Labels are dense and numbered in the order of each component's smallest vertex index, so `labels` is one fixed
+    array for a given face list; two calls give bit-equal arrays. Host reads: the index check's min / max and the 8 bytes of K.
+    ValueError: faces that are not [F,3] integer, an index outside [0, n_verts). T2NError without a GPU."""
+    lib = _lib.load()
+    f, dev = _faces_on_device(faces, n_verts, "mesh_components")
+    c, _ = _components(lib, f, int(n_verts), dev)
+    if _is_device(faces):
+        return c
+    return Components(c.labels.cpu().numpy(), c.n_components, c.vert_counts.cpu().numpy(), c.face_counts.cpu().numpy())
+
+
+def _rows(x, V, dtype, dev, what):
+    if x is None:
+        return None
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+    if tuple(t.shape) != (V, 3):
+        raise ValueError(f"filter_components: {what} of shape {tuple(t.shape)} for {V} vertices, need [V,3]")
+    return t.detach().to(device=dev, dtype=dtype).contiguous()
+
+
+@torch.no_grad()
+def filter_components(mesh, min_faces=0, keep_largest=None, components=None):
+    """`mesh` (a Mesh, or (verts, faces[, normals[, colors]])) without the components the caller does not want, as a Mesh. Component c
+    stays iff face_counts[c] >= min_faces and, with keep_largest = k, c is among the k components with the most faces (ties go to the
+    lower label). Kept vertices keep their relative order and their verts / normals / colors rows move together; kept faces keep
+    their relative order and are re-indexed: whole components leave, so a closed oriented 2-manifold stays one. `components`: an
+    earlier mesh_components(faces, V) result for the same mesh, to skip the labelling. Device tensors in, device tensors out; numpy
+    arrays / CPU tensors in, numpy arrays out. normals and colors that are None stay None. Host reads: the index check's min / max,
+    K when `components` is not given, and the 16 bytes of the new totals. ValueError: min_faces < 0, keep_largest < 1, faces that are
+    not [F,3] integer or hold an index outside [0, V), rows that do not match verts. T2NError without a GPU."""
+    lib = _lib.load()
+    parts = tuple(mesh)
+    if not 2 <= len(parts) <= 4:
+        raise ValueError(f"filter_components: a mesh of {len(parts)} parts, need (verts, faces[, normals[, colors]])")
+    verts, faces, normals, colors = parts + (None,) * (4 - len(parts))
+    if int(min_faces) < 0:
+        raise ValueError(f"filter_components: min_faces {min_faces} < 0")
+    if keep_largest is not None and int(keep_largest) < 1:
+        raise ValueError(f"filter_components: keep_largest {keep_largest} < 1")
+    if len(verts.shape) != 2 or verts.shape[1] != 3:
+        raise ValueError(f"filter_components: verts of shape {tuple(verts.shape)}, need [V,3]")
+    V = int(verts.shape[0])
+    f, dev = _faces_on_device(faces, V, "filter_components")
+    F = int(f.shape[0])
+    v = _rows(verts, V, torch.float32, dev, "verts")
+    n = _rows(normals, V, torch.float32, dev, "normals")
+    c = _rows(colors, V, torch.uint8, dev, "colors")
+    ws = None
+    if components is None:
+        comp, ws = _components(lib, f, V, dev)
+    else:
+        labels, K, _, fc = components
+        as_i32 = lambda x: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(
+            device=dev, dtype=torch.int32).contiguous()
+        comp = Components(as_i32(labels), int(K), None, as_i32(fc))
+        if tuple(comp.labels.shape) != (V,) or tuple(comp.face_counts.shape) != (comp.n_components,) or comp.n_components > V:
+            raise ValueError(f"filter_components: components of {tuple(comp.labels.shape)} labels and {comp.n_components} counts do not "
+                             f"belong to a mesh of {V} vertices")
+    K = comp.n_components
+    with torch.cuda.device(dev):
+        keep = comp.face_counts >= int(min_faces)
+        if keep_largest is not None and K > 0:
+            order = torch.sort(comp.face_counts, descending=True, stable=True).indices     # ties: the lower label first
+            top = torch.zeros(K, dtype=torch.bool, device=dev)
+            top[order[:int(keep_largest)]] = True
+            keep &= top
+        keep = keep.to(torch.uint8).contiguous()
+        Vk = Fk = 0
+        if V > 0:                                               # nothing is launched on an empty mesh
+            nbytes = int(lib.t2n_mesh_components_workspace_bytes(V, F))
+            if ws is None:
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            stream = _lib.current_stream_ptr(dev)
+            args = (_lib.ptr(f), F, _lib.ptr(comp.labels), V, _lib.ptr(keep), K)
+            _lib.check(lib.t2n_mesh_filter_count(*args, _lib.ptr(ws), nbytes, _lib.ptr(totals), stream), "t2n_mesh_filter_count")
+            Vk, Fk = (int(x) for x in totals.cpu().tolist())    # the one 16-byte read
+        out_v = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+        out_f = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
+        out_n = None if n is None else torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+        out_c = None if c is None else torch.empty(Vk, 3, dtype=torch.uint8, device=dev)
+        if Vk > 0:
+            _lib.check(lib.t2n_mesh_filter_emit(*args, _lib.ptr(v), _lib.ptr(n), _lib.ptr(c), _lib.ptr(ws), nbytes, _lib.ptr(out_v),
+                                                _lib.ptr(out_n), _lib.ptr(out_c), _lib.ptr(out_f), stream), "t2n_mesh_filter_emit")
+    if _is_device(verts):
+        return Mesh(out_v, out_f, out_n, out_c)
+    host = lambda x: None if x is None else x.cpu().numpy()
+    return Mesh(host(out_v), host(out_f), host(out_n), host(out_c))
 
 
 def _host(x, dtype):
