@@ -180,6 +180,11 @@ int t2n_field_set_early_termination(t2n_field* f, float eps);
  * created. A diagnostic: it waits for the whole device (hipDeviceSynchronize), so it must not be called inside a stream capture. */
 int t2n_field_set_feature_staging(t2n_field* f, int on);
 int t2n_field_feature_staging_counts(const t2n_field* f, uint64_t out[2]);
+/* DIAGNOSTIC, for tests of the feature stage's tile queue only (like the staging counters above, not part of the rendering API): the
+ * shape of the feature stage's launch. At most `workgroups` workgroups of eight waves (0 = the default, 512), and `defer_cap` tiles
+ * (1 .. 64; 0 = the default, 16) that a wave sets aside for its gathered loop before it drains them. Small values make one wave see
+ * many tiles and drain a full queue on a small frame. Neither value changes a feature row; no caller needs them to render. */
+int t2n_field_set_feature_stage_shape(t2n_field* f, int workgroups, int defer_cap);
 /* Image width of the row-major frames passed with T2N_FLAG_COHERENT (0 = unknown: the flag is ignored). */
 int t2n_field_set_frame_width(t2n_field* f, int width);
 

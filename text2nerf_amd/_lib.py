@@ -94,6 +94,7 @@ SIGNATURES = {
     "t2n_field_set_early_termination": (C.c_int, [C.c_void_p, C.c_float]),
     "t2n_field_set_feature_staging": (C.c_int, [C.c_void_p, C.c_int]),
     "t2n_field_feature_staging_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "t2n_field_set_feature_stage_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "t2n_sample_ray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "t2n_field_set_frame_width": (C.c_int, [C.c_void_p, C.c_int]),

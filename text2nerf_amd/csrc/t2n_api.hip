@@ -920,6 +920,14 @@ extern "C" int t2n_field_set_feature_staging(t2n_field* f, int on) {
     return T2N_OK;
 }
 
+extern "C" int t2n_field_set_feature_stage_shape(t2n_field* f, int workgroups, int defer_cap) {
+    if (!f) { set_error("t2n_field_set_feature_stage_shape: NULL field"); return T2N_ERR_INVALID; }
+    if (workgroups < 0 || defer_cap < 0 || defer_cap > 64) { set_error("t2n_field_set_feature_stage_shape: workgroups >= 0, defer_cap in [0, 64]"); return T2N_ERR_INVALID; }
+    f->feature_workgroups = workgroups;
+    f->feature_defer_cap = defer_cap ? defer_cap : 16;
+    return T2N_OK;
+}
+
 extern "C" int t2n_field_feature_staging_counts(const t2n_field* f, uint64_t out[2]) {
     if (!f || !out) { set_error("t2n_field_feature_staging_counts: NULL argument"); return T2N_ERR_INVALID; }
     out[0] = out[1] = 0;

@@ -109,6 +109,8 @@ struct t2n_field {
     int mlp_split = 1;         // 1: f16 two-way split products (default), 0: exact fp32 MFMA
     int feature_staging = 1;   // feature stage of the default render path: taps from a per-tile texel box in LDS (t2n_field_set_feature_staging)
     unsigned long long* staging_counts = nullptr;   // device: (tile, pair) units staged / gathered since creation (allocated by the first upload)
+    int feature_defer_cap = 16;    // feature stage: tiles a wave sets aside for its gathered loop before it drains them (1 .. 64)
+    int feature_workgroups = 0;    // feature stage: most workgroups of its grid (0 = 512); t2n_field_set_feature_stage_shape
     // channel-last gradient accumulators (backward), allocated on first use
     float* gbuf_den_plane[3] = {nullptr, nullptr, nullptr};
     float* gbuf_den_line[3] = {nullptr, nullptr, nullptr};

@@ -302,6 +302,7 @@ struct ShadeArgs {
     unsigned long long* stats;        // redo launches count themselves in stats[T2N_STAT_F16_REDO]
     int feature_staging;              // k_app_features_p: read the taps from a per-tile texel box in LDS where it fits
     unsigned long long* staging_counts;   // k_app_features_p: (tile, pair) units staged / gathered, added per wave
+    int defer_cap;                    // k_app_features_p: tiles a wave sets aside for its gathered loop before it drains them
 };
 
 // Gather: 384 (sample, channel-quad) items over 64 lanes, 6 per lane; an item computes its sample's three axis taps once
@@ -1008,8 +1009,9 @@ __device__ __forceinline__ void pair_basis(f32x16& acc, const uint4* __restrict_
 // lives where the gather path keeps X (the staged path needs no X: lane (s, h) of the basis product owns rows 16c + 8h .. + 7 of
 // sample s, which are quads 4c + 2h and 4c + 2h + 1 - it computes exactly those from the box and feeds them to the product). Same
 // texel values, same multiply / fma chain per channel, same chunk order: the feature rows are bit-identical to the gather's.
-// A pair whose box does not fit (a tile that straddles two marcher regions, rays more than a voxel apart, stale slots of an
-// overflowed list) runs gather_pair + pair_basis as before.
+// A tile with a pair whose box does not fit (a tile that straddles two marcher regions, rays more than a voxel apart, stale slots of
+// an overflowed list) is not staged at all: the wave sets it aside and its gathered loop runs gather_pair + pair_basis on all three
+// pairs later (k_app_features_p).
 constexpr int kBoxSlots = 64;    // box slots per wave: the plane box and the line span of a pair share them
 constexpr int kBoxSlot = 80;     // bytes per box slot: 4 quads + 16 B of padding - a 20-bank stride, so the 16 lanes of a
                                  // ds_read_b128 group hit 16 consecutive slots without a conflict
@@ -1048,114 +1050,114 @@ __device__ __forceinline__ TileBox tile_box(int ix, int iy, int iz, bool live) {
     return b;
 }
 
-// Census builds only (profiles/feature_staging_count_table.txt): 1 compiles the staged form alone, 2 the gathered form alone, so that
-// tools/featp_count_table.py counts the tile loop of ONE form. Such an object is for reading, never for running: form 1 has no fallback.
-#ifndef T2N_FEATP_FORM
-#define T2N_FEATP_FORM 0
-#endif
 // pair K of a tile: box origin, extents (high taps included: hi - lo + 2) and whether it fits the LDS box. All wave-uniform.
-struct PairBox { int a0, b0, l0, na, npl, nl; bool fits; };
+struct PairBox { int a0, b0, l0, na, npl, nl; unsigned rcp; bool fits; };
 template <int K>
-__device__ __forceinline__ PairBox pair_box(const TileBox& t, unsigned nlive, bool on) {
+__device__ __forceinline__ PairBox pair_box(const TileBox& t) {
     PairBox p;
     p.a0 = t.lo[mat0(K)]; p.b0 = t.lo[mat1(K)]; p.l0 = t.lo[vecm(K)];
     p.na = t.hi[mat0(K)] - p.a0 + 2;
     const int nb = t.hi[mat1(K)] - p.b0 + 2;
     p.nl = t.hi[vecm(K)] - p.l0 + 2;
     p.npl = p.na * nb;
-    if constexpr (T2N_FEATP_FORM == 1) p.fits = true;
-    else if constexpr (T2N_FEATP_FORM == 2) p.fits = false;
-    else p.fits = on && nlive > 0u && p.na >= 2 && nb >= 2 && p.nl >= 2 && p.na <= kBoxSlots && nb <= kBoxSlots && p.nl <= kBoxSlots &&
-             p.npl + p.nl <= kBoxSlots;
+    p.rcp = 65536u / (unsigned)p.na + 1u;   // slot / na = (slot * rcp) >> 16 for slot < 64 <= 65536 / na: exact
+    p.fits = p.na >= 2 && nb >= 2 && p.nl >= 2 && p.na <= kBoxSlots && nb <= kBoxSlots && p.nl <= kBoxSlots && p.npl + p.nl <= kBoxSlots;
     return p;
 }
 
 // Staging item i = 64 j + lane -> (box slot i >> 2, quad i & 3): slots [0, npl) are the plane box row by row, [npl, npl + nl) the
 // line span. Box column i holds texel min(a0 + i, W - 1) (rows and line taps alike): the clamp of parked_axes, so a high tap is
-// always the low tap's slot + 1, at the border too. gp[j]: the item's address in its plane or line (chunk 0).
-template <int K>
-__device__ __forceinline__ void stage_offsets(const FactorSet& S, const PairBox& p, int lane, const char* (&gp)[kBoxLoads]) {
-    asm volatile("" : "+v"(lane));   // (as in gather_pair: the per-lane item maps are not hoisted out of the tile loop and spilled)
-    const unsigned W = (unsigned)S.W[K];
-    const unsigned rcp = 65536u / (unsigned)p.na + 1u;   // slot / na for slot < 64 <= 65536 / na: exact
-    const char* __restrict__ Pb = reinterpret_cast<const char*>(S.plane[K]);
-    const char* __restrict__ Lb = reinterpret_cast<const char*>(S.line[K]);
-#pragma unroll
-    for (int j = 0; j < kBoxLoads; ++j) {
-        const unsigned i = (unsigned)(j * 64 + lane), t = i >> 2, qq = i & 3u;
-        const unsigned by = __umul24(t, rcp) >> 16, bx = t - __umul24(by, (unsigned)p.na);   // (t < 2^8, rcp < 2^16: 24-bit products)
+// always the low tap's slot + 1, at the border too. The lane's part of the split (slot lane >> 2 of 16 per load, quad lane & 3) does
+// not depend on the tile: the staged loop keeps it in registers. A load runs when ANY of its 64 items exists (wave-uniform), then in
+// every lane: a lane past the last item fetches the last slot's texel again and stores it to its own slot, which no tap reads (the
+// 64 slots take 5 120 B of the 6 336 B the box may use). gp[j]: the item's address in its plane or line (chunk 0).
+// (the four slots' registers as members, not arrays: an array of four float4 is promoted to ONE 16-float vector, and every load
+// under a wave-uniform branch then copies all of it)
+struct StageRegs {
+    f32x4 r0, r1, r2, r3;
+    const char *g0, *g1, *g2, *g3;
+    template <int J> __device__ __forceinline__ f32x4& r() { if constexpr (J == 0) return r0; else if constexpr (J == 1) return r1; else if constexpr (J == 2) return r2; else return r3; }
+    template <int J> __device__ __forceinline__ const char*& g() { if constexpr (J == 0) return g0; else if constexpr (J == 1) return g1; else if constexpr (J == 2) return g2; else return g3; }
+};
+static_assert(kBoxLoads == 4, "StageRegs holds four slots");
+
+// a * b + c on the 24-bit multiplier, b wave-uniform (umad24 wants b in a vector register; left to the compiler, these products
+// become full 32-bit multiplies at a quarter of the rate)
+__device__ __forceinline__ unsigned umad24_su(unsigned a, unsigned b, unsigned c) {
+    unsigned d;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b), "v"(c));
+    return d;
+}
+template <int K, int J>
+__device__ __forceinline__ void stage_offset(const FactorSet& S, const PairBox& p, int lane, StageRegs& R) {
+    const unsigned last = (unsigned)(p.npl + p.nl - 1);
+    if (J * 16 <= (int)last) {   // wave-uniform
+        const unsigned W = (unsigned)S.W[K];
+        const char* __restrict__ Pb = reinterpret_cast<const char*>(S.plane[K]);
+        const char* __restrict__ Lb = reinterpret_cast<const char*>(S.line[K]);
+        const unsigned t = min(((unsigned)lane >> 2) + 16u * J, last), qoff = ((unsigned)lane & 3u) * 16u;
+        const unsigned by = umad24_su(t, p.rcp, 0u) >> 16, bx = t - __umul24(by, (unsigned)p.na);   // (t < 2^8, rcp < 2^16: 24-bit products)
         const unsigned x = min((unsigned)p.a0 + bx, W - 1u), y = min((unsigned)p.b0 + by, (unsigned)S.H[K] - 1u);
         const unsigned tap = min((unsigned)p.l0 + (t - (unsigned)p.npl), (unsigned)S.L[K] - 1u);
         const bool ln = t >= (unsigned)p.npl;
-        const unsigned texel = ln ? tap : umad24(y, W, x);
-        gp[j] = (ln ? Lb : Pb) + umad24(texel, 12u * 16u, qq * 16u);   // chunk c of the item: + 64 c, an immediate of the load
+        const unsigned texel = ln ? tap : umad24_su(y, W, x);
+        R.g<J>() = (ln ? Lb : Pb) + (__umul24(texel, 12u * 16u) + qoff);   // chunk c of the item: + 64 c, an immediate of the load
     }
 }
+template <int K, int J>
+__device__ __forceinline__ void stage_load1(const FactorSet& S, const PairBox& p, int lane, int c, StageRegs& R) {
+    if (J * 16 <= p.npl + p.nl - 1) R.r<J>() = *reinterpret_cast<const f32x4*>(R.g<J>() + c * 64);   // wave-uniform
+}
 template <int K>
-__device__ __forceinline__ void stage_load(const PairBox& p, int lane, int c, const char* const (&gp)[kBoxLoads], f32x4 (&r)[kBoxLoads]) {
-    asm volatile("" : "+v"(lane));
-    const int nitems = (p.npl + p.nl) * 4;
-#pragma unroll
-    for (int j = 0; j < kBoxLoads; ++j) {
-        if (j * 64 < nitems) {   // wave-uniform
-            if (j * 64 + lane < nitems) r[j] = *reinterpret_cast<const f32x4*>(gp[j] + c * 64);
-        }
-    }
+__device__ __forceinline__ void stage_load(const FactorSet& S, const PairBox& p, int lane, int c, StageRegs& R) {
+    stage_load1<K, 0>(S, p, lane, c, R); stage_load1<K, 1>(S, p, lane, c, R); stage_load1<K, 2>(S, p, lane, c, R); stage_load1<K, 3>(S, p, lane, c, R);
 }
 // item i = 64 j + lane lands at slot (lane >> 2) + 16 j, quad lane & 3: one address per lane, the rest an immediate of the store
-__device__ __forceinline__ void stage_store(char* __restrict__ B, const PairBox& p, int lane, const f32x4 (&r)[kBoxLoads]) {
-    asm volatile("" : "+v"(lane));
-    const int nitems = (p.npl + p.nl) * 4;
+template <int J>
+__device__ __forceinline__ void stage_store1(char* __restrict__ d, const PairBox& p, StageRegs& R) {
+    if (J * 16 <= p.npl + p.nl - 1) *reinterpret_cast<f32x4*>(d + J * 16 * kBoxSlot) = R.r<J>();
+}
+__device__ __forceinline__ void stage_store(char* __restrict__ B, const PairBox& p, int lane, StageRegs& R) {
     char* __restrict__ d = B + __mul24(lane >> 2, kBoxSlot) + (lane & 3) * 16;
-#pragma unroll
-    for (int j = 0; j < kBoxLoads; ++j) {
-        if (j * 64 < nitems) {
-            if (j * 64 + lane < nitems) *reinterpret_cast<f32x4*>(d + j * 16 * kBoxSlot) = r[j];
-        }
-    }
+    stage_store1<0>(d, p, R); stage_store1<1>(d, p, R); stage_store1<2>(d, p, R); stage_store1<3>(d, p, R);
 }
 
-// the first chunk of pair K on its way (nothing when the pair does not fit)
+// the first chunk of pair K on its way
 template <int K>
-__device__ __forceinline__ void stage_first(const FactorSet& S, const PairBox& p, int lane, const char* (&gp)[kBoxLoads], f32x4 (&r)[kBoxLoads]) {
-    // (the loads below write the lanes that hold an item only, so the old contents of r stay alive up to here - across a whole
-    // gathered pair, which has no registers to spare: start from constants)
-#pragma unroll
-    for (int j = 0; j < kBoxLoads; ++j) { r[j] = f32x4{0.f, 0.f, 0.f, 0.f}; gp[j] = nullptr; }
-    if (p.fits) {   // wave-uniform
-        stage_offsets<K>(S, p, lane, gp);
-        stage_load<K>(p, lane, 0, gp, r);
-    }
+__device__ __forceinline__ void stage_first(const FactorSet& S, const PairBox& p, int lane, StageRegs& R) {
+    stage_offset<K, 0>(S, p, lane, R); stage_offset<K, 1>(S, p, lane, R); stage_offset<K, 2>(S, p, lane, R); stage_offset<K, 3>(S, p, lane, R);
+    stage_load<K>(S, p, lane, 0, R);
 }
 
 // Pair K from the box. On entry chunk 0 of the pair is in flight in r (stage_first<K>); once the last chunk's texels are in LDS
 // and gp / r are free again, the next pair's first chunk is sent on its way (pn: its box).
 template <int K>
 __device__ __forceinline__ void staged_pair(const FactorSet& S, f32x16& acc, const uint4* __restrict__ Wl, char* __restrict__ B,
-                                            const float4* __restrict__ P, const PairBox& p, const PairBox& pn, const char* (&gp)[kBoxLoads],
-                                            f32x4 (&r)[kBoxLoads], int s, int h, int lane, unsigned nlive, float& amax) {
-    asm volatile("" : "+v"(lane), "+v"(s), "+v"(h));   // (the lane's LDS addresses are rebuilt per pair, not hoisted and spilled)
+                                            const float4* __restrict__ P, const PairBox& p, const PairBox& pn, StageRegs& R, int s, int h, int lane, unsigned nlive, float& amax) {
     const uint4* __restrict__ ap = Wl + lane + (3 * K) * 2 * 64;
     const bool live = (unsigned)s < nlive;
     const float4 pi = P[2 * s], pw = P[2 * s + 1];
     const int idx[3] = {__float_as_int(pi.x), __float_as_int(pi.y), __float_as_int(pi.z)};
     const float w1[3] = {pw.x, pw.y, pw.z};
-    // dead entries sit at the volume centre, outside the box: they read slot 0 and store zeros
+    // dead entries sit at the volume centre, outside the box: they read slot 0 with all six weights zero. Their rows are zeros of
+    // either sign for a finite field; a non-finite texel in slot 0 makes them NaN, which no ray's slice holds, but which reaches amax
+    // and sends the launch to the exact path - as the live entry that owns that texel does anyway
     const int jx = live ? idx[mat0(K)] - p.a0 : 0, jy = live ? idx[mat1(K)] - p.b0 : 0, jl = live ? idx[vecm(K)] - p.l0 : 0;
     const float ax1 = w1[mat0(K)], ay1 = w1[mat1(K)], al1 = w1[vecm(K)];
     const float ax0 = 1.f - ax1, ay0 = 1.f - ay1, al0 = 1.f - al1;
+    const float by0 = live ? ay0 : 0.f, by1 = live ? ay1 : 0.f;
     QuadTaps t;
-    t.wnw = ay0 * ax0; t.wne = ay0 * ax1; t.wsw = ay1 * ax0; t.wse = ay1 * ax1;
-    t.wl0 = al0; t.wl1 = al1;
+    t.wnw = by0 * ax0; t.wne = by0 * ax1; t.wsw = by1 * ax0; t.wse = by1 * ax1;
+    t.wl0 = live ? al0 : 0.f; t.wl1 = live ? al1 : 0.f;
     const char* __restrict__ r0 = B + __mul24(__mul24(jy, p.na) + jx, kBoxSlot) + h * 32;
     const char* __restrict__ r1 = r0 + p.na * kBoxSlot;
     const char* __restrict__ rl = B + __mul24(p.npl + jl, kBoxSlot) + h * 32;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        stage_store(B, p, lane, r);
+        stage_store(B, p, lane, R);
         wave_lds_sync();
-        if (c < 2) stage_load<K>(p, lane, c + 1, gp, r);
-        else if constexpr (K < 2) stage_first<K + 1>(S, pn, lane, gp, r);
+        if (c < 2) stage_load<K>(S, p, lane, c + 1, R);
+        else if constexpr (K < 2) stage_first<K + 1>(S, pn, lane, R);
         float x[8];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -1167,24 +1169,28 @@ __device__ __forceinline__ void staged_pair(const FactorSet& S, f32x16& acc, con
             // v_pk_fma_f32 and pays for it in register moves)
             asm("" : "+v"(pv.x), "+v"(pv.y), "+v"(pv.z), "+v"(pv.w));
             const float4 l = taps_line(t);
-            float4 v = make_float4(pv.x * l.x, pv.y * l.y, pv.z * l.z, pv.w * l.w);
-            if (!live) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            x[4 * j] = v.x; x[4 * j + 1] = v.y; x[4 * j + 2] = v.z; x[4 * j + 3] = v.w;
+            x[4 * j] = pv.x * l.x; x[4 * j + 1] = pv.y * l.y; x[4 * j + 2] = pv.z * l.z; x[4 * j + 3] = pv.w * l.w;
             // (fenced: unfenced, both quads' twelve taps are read up front - 48 registers - and the staging addresses are spilled)
             if (j == 0) __builtin_amdgcn_sched_barrier(0);
         }
         basis_chunk(acc, ap, c, x, amax);
-        wave_lds_sync();   // the chunk's box reads are done before the next chunk (or the next pair's gather) overwrites it
+        wave_lds_sync();   // the chunk's box reads are done before the next chunk (or the next tile's positions) overwrites it
     }
 }
 
 constexpr int kPairWaves = 8;                               // waves per workgroup (one copy of the basis operands per workgroup)
 constexpr int kPairBasisVec = kBasisChunksReal * 2 * 64;    // uint4 elements of the nine real chunks
+constexpr int kDeferMax = 64;                               // deferred tiles a wave can hold: one per lane of a register
 
+// Each form of a tile has its own loop. The wave's main loop runs the staged form only; a tile it cannot stage (a pair whose box does
+// not fit, staging switched off, no live entry) is set aside: its index goes into lane nq of one register, the wave's queue. When the
+// queue holds defer_cap tiles, and at the end, a second loop drains it with the gathered form. The two loops share no per-lane state,
+// so each keeps its own lane maps in registers for as long as it runs and neither pays for the other's. bf16 storage (HALF) has the
+// gathered loop only.
 template <bool HALF>
 __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_app_features_p(const ShadeArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (the wave's LDS bases: scalar)
     uint4* __restrict__ Wl = reinterpret_cast<uint4*>(smem);
     float* __restrict__ X = smem + kPairBasisVec * 4 + (size_t)wid * kPairFloats;
     float4* __restrict__ P = reinterpret_cast<float4*>(X + kPairRows * kXld);
@@ -1202,7 +1208,8 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
         const unsigned t = __shfl_up(incl, o);
         if (lane >= o) incl += t;
     }
-    unsigned ntiles = __shfl(incl, a.nlists - 1);
+    // (tile counts and list positions are wave-uniform: held in scalar registers, the loops below branch on them)
+    unsigned ntiles = (unsigned)__builtin_amdgcn_readfirstlane((int)__shfl(incl, a.nlists - 1));
     if (ntiles > a.tile_hi) ntiles = a.tile_hi;
     if (a.split_unsafe && (*a.split_unsafe & kUnsafeBasis)) {   // basis_mat weights beyond the fixed pre-scale's range: the launch is redone on the exact path
         if (a.range_flag && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.range_flag, 1u);
@@ -1211,8 +1218,9 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
     const unsigned wave_stride = gridDim.x * (unsigned)kPairWaves;
     float amax = 0.f;
     unsigned n_staged = 0u, n_gathered = 0u;
-    // tile -> (first entry, live entries) and the lane's position entry (lanes 0..31; dead entries sit at the volume centre and
-    // store zeros); the next tile's positions are fetched while this tile is processed
+    // tile -> (first entry, live entries) and the lane's position entry (lanes 0..31; dead entries get the volume centre: the gathered
+    // form stores zeros for them, the staged form gives them zero weights); the staged loop and the bf16 loop fetch the next tile's
+    // positions while this tile is processed
     auto locate = [&](unsigned tile, unsigned& base, unsigned& nlive, float4& mine) {
         mine = make_float4(0.f, 0.f, 0.f, 0.f);
         base = 0u; nlive = 0u;
@@ -1220,22 +1228,18 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
         const int li = (int)__popcll(__ballot((lane < a.nlists) & (incl <= tile)));
         const unsigned before = li ? __shfl(incl, li - 1) : 0u;
         const unsigned lbase = (unsigned)li * a.list_cap;
-        base = lbase + (tile - before) * 32u;
+        base = (unsigned)__builtin_amdgcn_readfirstlane((int)(lbase + (tile - before) * 32u));
         const unsigned count = lbase + __shfl(cnt_l, li);
-        nlive = count - base < 32u ? count - base : 32u;
-        if (lane < 32 && (unsigned)lane < nlive) mine = a.app_pos[base + (unsigned)lane];
+        nlive = (unsigned)__builtin_amdgcn_readfirstlane((int)(count - base < 32u ? count - base : 32u));
+        // (a scalar base and the lane's own 32-bit offset; left to itself, the compiler keeps app_pos + lane as a 64-bit per-lane pointer
+        // across both loops)
+        const float4* __restrict__ pb = a.app_pos + base;
+        asm volatile("" : "+s"(pb));
+        if (lane < 32 && (unsigned)lane < nlive) mine = pb[lane];
     };
-    unsigned base, nlive, nbase, nnlive;
-    float4 mine, nmine;
-    locate(blockIdx.x * (unsigned)kPairWaves + wid, base, nlive, mine);
-    for (unsigned tile = blockIdx.x * (unsigned)kPairWaves + wid; tile < ntiles; tile += wave_stride, base = nbase, nlive = nnlive, mine = nmine) {
-        asm volatile("; FEATP_MARK tile_begin");   // (tools/featp_count_table.py: the tile loop's instructions by mnemonic)
-        // the lane index behind an opaque copy, per tile: visible, the lane's LDS addresses and item maps are hoisted out of the tile
-        // loop and spilled (the staged and the gathered form together hold more of them than the register file has room for)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int sl = ln & 31, hl = ln >> 5;
-        int ix = 0, iy = 0, iz = 0;
+    // the tile's low taps and high-tap weights, parked in P (lanes 0..31: one entry each)
+    auto park = [&](int ln, const float4& mine, int& ix, int& iy, int& iz) {
+        ix = 0; iy = 0; iz = 0;
         if (ln < 32) {   // (dead entries sit at the volume centre: in the box like every list entry)
             const Axes3 A = sample_axes_inbox(F.app, mine.x, mine.y, mine.z);
             // list slots that were reserved but never written (a budgeted launch that overflowed: this kernel is already queued when
@@ -1243,69 +1247,113 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
             // (parked_axes: high tap = min(low + 1, size - 1)); such rows belong to no ray's slice and are never composited
             ix = min(max(A.a[0].i0, 0), F.app.W[0] - 1); iy = min(max(A.a[1].i0, 0), F.app.H[0] - 1);
             iz = min(max(A.a[2].i0, 0), F.app.H[1] - 1);
-            P[2 * ln] = make_float4(__int_as_float(ix), __int_as_float(iy), __int_as_float(iz), mine.w);
-            P[2 * ln + 1] = make_float4(A.a[0].w1, A.a[1].w1, A.a[2].w1, 0.f);
+            const int sl = ln & 31;   // (= ln here: the address the tile's readers use)
+            P[2 * sl] = make_float4(__int_as_float(ix), __int_as_float(iy), __int_as_float(iz), mine.w);
+            P[2 * sl + 1] = make_float4(A.a[0].w1, A.a[1].w1, A.a[2].w1, 0.f);
         }
-        locate(tile + wave_stride, nbase, nnlive, nmine);
-        wave_lds_sync();
-        f32x16 acc = {0};
-        if constexpr (HALF) {   // bf16 storage keeps the gather (8-B texels: half the bytes already)
-            gather_pair<0, HALF>(F.app, X, P, ln, nlive);
-            wave_lds_sync();
-            pair_basis<0>(acc, Wl, X + sl, hl, ln, amax);
-            wave_lds_sync();
-            gather_pair<1, HALF>(F.app, X, P, ln, nlive);
-            wave_lds_sync();
-            pair_basis<1>(acc, Wl, X + sl, hl, ln, amax);
-            wave_lds_sync();
-            gather_pair<2, HALF>(F.app, X, P, ln, nlive);
-            wave_lds_sync();
-            pair_basis<2>(acc, Wl, X + sl, hl, ln, amax);
-            n_gathered += 3u;
-        } else {
-            // staged where the pair's tap box fits the wave's LDS box, gathered where it does not (wave-uniform, per pair)
-            const TileBox tb = tile_box(ix, iy, iz, ln < 32 && (unsigned)ln < nlive);
-            const bool on = a.feature_staging != 0;
-            const PairBox b0 = pair_box<0>(tb, nlive, on), b1 = pair_box<1>(tb, nlive, on), b2 = pair_box<2>(tb, nlive, on);
-            char* __restrict__ B = reinterpret_cast<char*>(X);
-            const char* gp[kBoxLoads];
-            f32x4 r[kBoxLoads];
-            stage_first<0>(F.app, b0, ln, gp, r);
-            if (b0.fits) staged_pair<0>(F.app, acc, Wl, B, P, b0, b1, gp, r, sl, hl, ln, nlive, amax);
-            else {
-                gather_pair<0, HALF>(F.app, X, P, ln, nlive);
-                wave_lds_sync();
-                pair_basis<0>(acc, Wl, X + sl, hl, ln, amax);
-                wave_lds_sync();
-                stage_first<1>(F.app, b1, ln, gp, r);
-            }
-            if (b1.fits) staged_pair<1>(F.app, acc, Wl, B, P, b1, b2, gp, r, sl, hl, ln, nlive, amax);
-            else {
-                gather_pair<1, HALF>(F.app, X, P, ln, nlive);
-                wave_lds_sync();
-                pair_basis<1>(acc, Wl, X + sl, hl, ln, amax);
-                wave_lds_sync();
-                stage_first<2>(F.app, b2, ln, gp, r);
-            }
-            if (b2.fits) staged_pair<2>(F.app, acc, Wl, B, P, b2, b2, gp, r, sl, hl, ln, nlive, amax);
-            else {
-                gather_pair<2, HALF>(F.app, X, P, ln, nlive);
-                wave_lds_sync();
-                pair_basis<2>(acc, Wl, X + sl, hl, ln, amax);
-            }
-            const unsigned ns = (b0.fits ? 1u : 0u) + (b1.fits ? 1u : 0u) + (b2.fits ? 1u : 0u);
-            n_staged += ns; n_gathered += 3u - ns;
-        }
+    };
+    // lane (s, h) register v holds feature (v & 3) + 8 (v >> 2) + 4 h: four float4 stores per lane. Column 27 (a zero of the
+    // padded basis) carries the entry's compositing weight to the head, which hands it on in app_rgb.w
+    auto store_rows = [&](unsigned tile, const f32x16& acc, unsigned nlive, int sl, int hl) {
         const f32x16 accb = acc * kWUnscale;
-        // lane (s, h) register v holds feature (v & 3) + 8 (v >> 2) + 4 h: four float4 stores per lane. Column 27 (a zero of the
-        // padded basis) carries the entry's compositing weight to the head, which hands it on in app_rgb.w
-        float* __restrict__ row = a.ctx.feat32 + ((size_t)tile * 32 + sl) * 32 + 4 * hl;
+        float* __restrict__ rb = a.ctx.feat32 + (size_t)tile * 1024;   // (scalar base, as in locate)
+        asm volatile("" : "+s"(rb));
+        float* __restrict__ row = rb + (unsigned)(sl * 32 + 4 * hl);
         const float wgt = (hl == 0 && (unsigned)sl < nlive) ? P[2 * sl].w : 0.f;   // lane (s, 0) holds columns 24..27 in registers 12..15
 #pragma unroll
         for (int g = 0; g < 4; ++g)
             *reinterpret_cast<float4*>(row + 8 * g) = make_float4(accb[4 * g], accb[4 * g + 1], accb[4 * g + 2], (g == 3 && hl == 0) ? wgt : accb[4 * g + 3]);
         wave_lds_sync();   // X and P reads done before the next tile overwrites them
-        asm volatile("; FEATP_MARK tile_end");
+    };
+    // one tile in the gathered form: gather_pair + pair_basis per plane / line pair
+    auto gathered_tile = [&](unsigned tile, unsigned nlive, const float4& mine, int ln) {
+        const int sl = ln & 31, hl = ln >> 5;
+        int ix, iy, iz;
+        park(ln, mine, ix, iy, iz);
+        wave_lds_sync();
+        f32x16 acc = {0};
+        gather_pair<0, HALF>(F.app, X, P, ln, nlive);
+        wave_lds_sync();
+        pair_basis<0>(acc, Wl, X + sl, hl, ln, amax);
+        wave_lds_sync();
+        gather_pair<1, HALF>(F.app, X, P, ln, nlive);
+        wave_lds_sync();
+        pair_basis<1>(acc, Wl, X + sl, hl, ln, amax);
+        wave_lds_sync();
+        gather_pair<2, HALF>(F.app, X, P, ln, nlive);
+        wave_lds_sync();
+        pair_basis<2>(acc, Wl, X + sl, hl, ln, amax);
+        n_gathered += 3u;
+        store_rows(tile, acc, nlive, sl, hl);
+    };
+    unsigned tile = blockIdx.x * (unsigned)kPairWaves + wid;
+    if constexpr (HALF) {   // bf16 storage keeps the gather (8-B texels: half the bytes already)
+        unsigned base, nlive, nbase, nnlive;
+        float4 mine, nmine;
+        locate(tile, base, nlive, mine);
+        for (; tile < ntiles; tile += wave_stride, base = nbase, nlive = nnlive, mine = nmine) {
+            // (the lane index behind an opaque copy, per tile: visible, the gather's per-lane item maps are hoisted out of the tile loop
+            // and spilled)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            locate(tile + wave_stride, nbase, nnlive, nmine);
+            gathered_tile(tile, nlive, mine, ln);
+        }
+    } else {
+        const bool on = a.feature_staging != 0;
+        const unsigned cap = (unsigned)__builtin_amdgcn_readfirstlane(min(max(a.defer_cap, 1), kDeferMax));
+        int dq = 0;           // lane i: the i-th deferred tile
+        unsigned nq = 0u;     // deferred tiles in dq (wave-uniform)
+        while (true) {
+            {
+                // the lane index behind an opaque copy, once per entry into the staged loop: what the loop derives from it (the staging
+                // split, the lane's box addresses) is set up here, in front of the loop, and is dead again when the queue is drained
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                const int sl = ln & 31, hl = ln >> 5;
+                unsigned base, nlive, nbase, nnlive;
+                float4 mine, nmine;
+                locate(tile, base, nlive, mine);
+                // (a slot's registers are written only where the pair has that slot: given values here, once per entry, they are the
+                // staged loop's own; left undefined, they count as live from the top of the kernel, across the gathered loop too)
+                StageRegs R = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, nullptr, nullptr, nullptr, nullptr};
+                for (; tile < ntiles && nq < cap; tile += wave_stride, base = nbase, nlive = nnlive, mine = nmine) {
+                    asm volatile("; FEATP_MARK tile_begin");   // (tools/featp_count_table.py: the staged loop's instructions by mnemonic)
+                    int ix, iy, iz;
+                    park(ln, mine, ix, iy, iz);
+                    locate(tile + wave_stride, nbase, nnlive, nmine);
+                    const TileBox tb = tile_box(ix, iy, iz, ln < 32 && (unsigned)ln < nlive);
+                    const PairBox b0 = pair_box<0>(tb), b1 = pair_box<1>(tb), b2 = pair_box<2>(tb);
+                    if (!(on && nlive > 0u && b0.fits && b1.fits && b2.fits)) {   // wave-uniform: set aside for the gathered loop
+                        if ((unsigned)lane == nq) dq = (int)tile;
+                        ++nq;
+                        continue;
+                    }
+                    wave_lds_sync();
+                    f32x16 acc = {0};
+                    char* __restrict__ B = reinterpret_cast<char*>(X);
+                    stage_first<0>(F.app, b0, ln, R);
+                    staged_pair<0>(F.app, acc, Wl, B, P, b0, b1, R, sl, hl, ln, nlive, amax);
+                    staged_pair<1>(F.app, acc, Wl, B, P, b1, b2, R, sl, hl, ln, nlive, amax);
+                    staged_pair<2>(F.app, acc, Wl, B, P, b2, b2, R, sl, hl, ln, nlive, amax);
+                    n_staged += 3u;
+                    store_rows(tile, acc, nlive, sl, hl);
+                    asm volatile("; FEATP_MARK tile_end");
+                }
+            }
+            for (unsigned i = 0; i < nq; ++i) {
+                asm volatile("; FEATP_MARK gathered_begin");
+                int ln = lane;
+                asm volatile("" : "+v"(ln));
+                const unsigned t = (unsigned)__builtin_amdgcn_readlane(dq, (int)i);
+                unsigned base, nlive;
+                float4 mine;
+                locate(t, base, nlive, mine);
+                gathered_tile(t, nlive, mine, ln);
+            }
+            nq = 0u;
+            if (tile >= ntiles) break;
+        }
     }
     if (a.range_flag && __any(!(amax <= 60000.f)) && lane == 0) atomicOr(a.range_flag, 1u);
     if (a.staging_counts && lane == 0) {   // (tile, pair) units of this wave: staged / gathered
@@ -1892,7 +1940,7 @@ int launch_shade_list(t2n_field* f, const float4* app_pos, const int* app_ray, c
         fa.ctx = ShadeCtx{nullptr, feat, nullptr, nullptr};
         fa.ctx_rows = ws_tiles * 32u; fa.tile_hi = ws_tiles;
         fa.range_flag = flag; fa.split_unsafe = f->split_unsafe;
-        fa.feature_staging = f->feature_staging; fa.staging_counts = f->staging_counts;
+        fa.feature_staging = f->feature_staging; fa.staging_counts = f->staging_counts; fa.defer_cap = f->feature_defer_cap;
         timing_begin(f, T2N_K_APPFEAT, s);
         {
             const size_t lds_p = (size_t)kPairBasisVec * 16 + (size_t)kPairWaves * kPairFloats * sizeof(float);
@@ -1903,7 +1951,8 @@ int launch_shade_list(t2n_field* f, const float4* app_pos, const int* app_ray, c
                 attr_p = true;
             }
             const unsigned long long wg = ((unsigned long long)ws_tiles + kPairWaves - 1) / kPairWaves;
-            const dim3 grid_p((unsigned)(wg < 512u ? (wg ? wg : 1u) : 512u));   // two workgroups (16 waves) per CU
+            const unsigned wg_max = f->feature_workgroups > 0 ? (unsigned)f->feature_workgroups : 512u;   // two workgroups (16 waves) per CU
+            const dim3 grid_p((unsigned)(wg < wg_max ? (wg ? wg : 1u) : wg_max));
             if (half) hipLaunchKernelGGL(k_app_features_p<true>, grid_p, dim3(64 * kPairWaves), lds_p, s, fa);
             else hipLaunchKernelGGL(k_app_features_p<false>, grid_p, dim3(64 * kPairWaves), lds_p, s, fa);
         }

@@ -364,6 +364,7 @@ class TensorBase(nn.Module):
         self.frame_width = 0              # set to the image width when eval rays are whole row-major frames: enables the
                                           # 8x8-tile marcher (shared dot-product tables); 0 = unknown -> per-ray marcher
         self.mlp_exact_fp32 = False       # False: f16 two-way-split MFMA products; True: exact fp32 MFMA (forward and backward)
+        self.feature_stage_shape = (0, 0)  # (most workgroups, deferred-tile queue capacity) of the feature stage; 0 = default (tests)
         self.feature_staging = True       # feature stage of eval frames: taps read from a per-tile texel box in LDS where it fits
                                           # (same rows bit for bit; False = every tap gathered); see feature_staging_counts()
         # 'fp32' (default) or 'bf16' (BASELINE configs[4]): the forward gathers read bf16 copies of the 12 factor tensors;
@@ -802,6 +803,7 @@ class TensorBase(nn.Module):
             self._storage_set = None
             self._frame_w_set = None
             self._staging_set = None
+            self._stage_shape_set = (0, 0)
             self._head_rows_set = 32
             self._alpha_key = "unset"
         queued = False     # device work queued by this call (mask / parameter uploads)
@@ -839,6 +841,10 @@ class TensorBase(nn.Module):
             _lib.check(lib.t2n_field_set_feature_staging(self._handle, 1 if self.feature_staging else 0),
                        "t2n_field_set_feature_staging")
             self._staging_set = bool(self.feature_staging)
+        shape = tuple(int(v) for v in self.feature_stage_shape)
+        if getattr(self, "_stage_shape_set", (0, 0)) != shape:
+            _lib.check(lib.t2n_field_set_feature_stage_shape(self._handle, shape[0], shape[1]), "t2n_field_set_feature_stage_shape")
+            self._stage_shape_set = shape
         # (rayMarch_weight_thres = 0 — `weight > thres`, models/tensorBase.py:477 — is a legitimate setting: 0 then means off)
         et = max(0.0, min(float(self.early_termination or 0.0), float(self.rayMarch_weight_thres)))
         if getattr(self, "_term_set", None) != et:

@@ -2,7 +2,8 @@
 """k_app_features_p<false>: the instructions of ONE tile (32 appearance samples: every basic block of the tile loop in the compiler's
 assembly, the exec-masked ones included) by mnemonic, priced with the per-class issue costs of bench.py's issue model (VALU 5, LDS 8,
 MFMA 21 cycles; a 16-byte-per-lane gather 16 cycles of the texture addresser's 64 B/clk), and what of it is removable without changing
-the arithmetic. Usage: featp_count_table.py t2n_shade.s"""
+the arithmetic. The kernel has one loop per form; MARK names the loop to count: tile_begin (default, the staged loop) or gathered_begin (the
+loop that drains the deferred tiles with the gathered form). Usage: featp_count_table.py t2n_shade.s [MARK]"""
 import collections
 import re
 import sys
@@ -32,9 +33,10 @@ def main():
     lines = open(sys.argv[1]).read().split("\n")
     start = next(i for i, l in enumerate(lines) if l.startswith("_ZN3t2n16k_app_features_pILb0EE"))
     end = next(i for i, l in enumerate(lines) if i > start and ".end_amdhsa_kernel" in l or (i > start and l.startswith(".Lfunc_end")))
+    mark = sys.argv[2] if len(sys.argv) > 2 else "tile_begin"
     header = None
     for i in range(start, end):
-        if "FEATP_MARK tile_begin" in lines[i]:
+        if "FEATP_MARK " + mark in lines[i]:
             j = i
             while not re.match(r"\.LBB\d+_\d+:", lines[j]):
                 j -= 1
@@ -44,11 +46,11 @@ def main():
     for l in lines[start:end]:
         m = re.match(r"\.(LBB\d+_\d+):(.*)", l)
         if m:
-            in_loop = m.group(1)[1:] == header or f"Header={header}" in m.group(2)
+            in_loop = m.group(1)[1:] == header or re.search(rf"Header={header}\b", m.group(2)) is not None
             continue
         m2 = re.match(r"; %bb\.\d+:(.*)", l)
         if m2:
-            in_loop = f"Header={header}" in m2.group(1)
+            in_loop = re.search(rf"Header={header}\b", m2.group(1)) is not None   # (BB7_20 is not BB7_208)
             continue
         t = l.strip()
         if not in_loop or not t or t.startswith((";", ".")) or t.endswith(":"):
@@ -61,8 +63,8 @@ def main():
         tot[kl] += v
         cyc[k] = v * cost
     total_cyc = sum(cyc.values())
-    print("k_app_features_p<false>, one tile of one wave (32 samples x 144 channels): %d instructions, %.1f k issue cycles by the per-class "
-          "cost table" % (sum(c.values()), total_cyc / 1e3))
+    print("k_app_features_p<false>, loop %s, one tile of one wave (32 samples x 144 channels): %d instructions, %.1f k issue cycles by the per-class "
+          "cost table" % (mark, sum(c.values()), total_cyc / 1e3))
     print("by class: " + ", ".join(f"{k} {v}" for k, v in tot.most_common()))
     print(f"{'mnemonic':30s}{'count':>7s}{'cycles each':>13s}{'k cycles':>10s}{'share':>8s}")
     for k, v in sorted(c.items(), key=lambda kv: -cyc[kv[0]]):
