@@ -725,7 +725,7 @@ int t2n_mesh_filter_emit(const int32_t* faces, int64_t n_faces, const int32_t* l
  *                  data-parallel all-reduce of both; a non-zero vote word withholds the update on every rank), 3: both.
  *   losses         device float[4] = {mse, depth loss, transmittance loss, total} of the batch
  * host_batch: the call itself copies host_batch_bytes from pinned host memory to batch_buffer (asynchronously, ahead of everything that
- * reads the batch, with an engine copy; T2N_COPY_KERNEL=1: a 16-byte-aligned pinned batch is read by the step's zero-fill launch itself). Pipelined form — an eager call with T2N_FLAG_PIPELINE, phases = 3, host_batch set and a workspace of TWICE
+ * reads the batch, with an engine copy). Pipelined form — an eager call with T2N_FLAG_PIPELINE, phases = 3, host_batch set and a workspace of TWICE
  * t2n_train_step_workspace_bytes: the copy and the step's early part (zero fills, the march — it reads the density factors only —, the
  * plan, the appearance binning) are enqueued on the library's side stream right behind the PREVIOUS step's density Adam instead of
  * behind `stream`, i.e. they run beside the previous step's appearance scatter / weight-gradient GEMMs / Adam. The two halves of the
@@ -762,7 +762,7 @@ int t2n_train_step(t2n_field* f, const t2n_train_step_args* a, t2n_stream stream
  * is (by value; NULL clears; host-only: no stream work, nothing is read here), and a flagged phases & 1 call fills its own batch —
  * a->rays (ray_stride must be 6), a->rgb_target, a->depth_target, destinations inside batch_buffer — from the rows ids[0..n_rays) as its
  * first device work: further rows of the step's zero-fill launch (no extra launch; a captured step keeps its DAG), on the stream the
- * early part runs on, behind the engine copy of host_batch (always the engine copy: T2N_COPY_KERNEL is ignored by a gathering step),
+ * early part runs on, behind the engine copy of host_batch,
  * which then covers ids | jitter | hyper only (2 n_rays + 32 words where the plain form sends 11 n_rays + 32). An id outside [0, n_rows) is clamped into range by the kernel: a caller error, never an
  * out-of-bounds read. The flag without a source: T2N_ERR_STATE; n_rows < 1 or ray_stride < 6: T2N_ERR_INVALID (both before anything is
  * enqueued). phases = 2 and phases = 4 calls ignore the flag. The source's rows must have been written on `stream` (or be complete) when

@@ -2,7 +2,10 @@
 // TensorBase.forward (text2nerf_main.py:589). Sample coordinates are detached in the reference
 // (models/tensoRF.py:208-210,226-228), so gradients flow only into the factor tensors, basis_mat and the MLP.
 //
-// Pipeline (all on the caller's stream; `rows` = padded appearance-sample rows, 32 per shade tile):
+// Pipeline (`rows` = padded appearance-sample rows, 32 per shade tile). Streams of t2n_render_backward: steps 1, 2, 3, the input-gradient
+// chain of 3-4, 5 and 6 run on the caller's stream; 2b on the first side stream; the operand packing of k_mlp_bwd_ss (in front of step 2)
+// and the weight-gradient GEMMs of the fused head (behind the chain) on the second. Both are joined in front of step 6.
+// T2N_BWD_SERIAL=1, the atomic scatters and the heads without the fused chain keep everything on the caller's stream.
 //   1  k_shade (ctx mode)      re-run the appearance forward, keeping X[rows,144], feat[rows,32], h0/h1[rows,128]
 //   2  k_bwd_march             per ray: recompute alpha/T/w from the kept sigma, dL/dw -> dL/dalpha (reverse scan) -> dL/dsigma
 //                              -> dL/dfeature; emits per appearance sample go = dL/d(pre-sigmoid rgb); counts the samples of every
@@ -16,64 +19,30 @@
 //   4  gemm_tn / gemm_nn       fp32-MFMA GEMMs: dW1 = g1^T h0, g0 = (g1 W1) * [h0 > 0], dW0 = g0^T PE(feat), gx = g0 W0,
 //                              PE backward -> gf, dWb = gf^T X, gX = gf Wb; k_colsum for the biases
 //   5  k_app_bin, k_bin_scan,  appearance scatter: records sorted by 16x16-texel plane tile, accumulated in LDS (ds_add_f64), flushed once per
-//      k_bwd_tile_accum<48>    tile segment (global-atomic path: k_bwd_app_scatter); runs beside the weight-gradient GEMMs (third stream)
+//      k_bwd_tile_accum<48>    tile segment (global-atomic path: k_bwd_app_scatter); runs beside the weight-gradient GEMMs
 //   6  k_relayout_add          channel-last gradient buffers -> += reference-layout [1,C,H,W] gradient tensors
-// This file: k_bwd_march, the scatters (density blocks, appearance tiles, the atomic paths) and the driver (workspace carve, streams,
-// t2n_render_backward). Steps 3-4 live in t2n_bwd_mlp.hip (+ t2n_gemm_h.hip, t2n_mlp_bwd_ss.hip), the training loss in t2n_loss.hip.
+// This file: the kernels of steps 2, 2b, 5 and 6 (the atomic paths too), ONE host launcher per stage (declared in t2n_backward.h with the
+// workspace carve), the owner of the side streams and events, and the driver t2n_render_backward. The fused training step enqueues the
+// same launchers in its own order (t2n_train.hip). Steps 3-4 live in t2n_bwd_mlp.hip (+ t2n_gemm_h.hip, t2n_mlp_bwd_ss.hip), the
+// training loss in t2n_loss.hip.
 #include <stdlib.h>
 
 #include <mutex>
 
+#include "t2n_backward.h"
 #include "t2n_device.h"
 
 namespace t2n {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-__host__ __device__ constexpr int unit_of(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }
-__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-struct TilePrefix { unsigned t[kLists + 1]; };   // tiles before each sub-list (host-computed from the counters)
-struct GradSet { float* plane[3]; float* line[3]; };
-// The same in device memory, for a backward that never reads the counters on the host (T2N_FLAG_DEVICE_ROWS): tile prefix and row
-// count from the forward's counters (k_bwd_plan), clipped to the row CAPACITY the caller's buffers hold; overflow = the count
-// exceeded it (the rows beyond take no part in this backward: the caller learns it from the forward's posted counters)
-struct BwdPlan { TilePrefix tp; unsigned rows; unsigned overflow; };
-
 __device__ __forceinline__ unsigned slot_to_row(unsigned slot, unsigned list_cap, const TilePrefix& tp) {
     const unsigned l = slot / list_cap;
     return tp.t[l] * 32u + (slot - l * list_cap);
-}
-
-// Scatter d(feature)/d(plane taps, line taps) for factor pair K, ONE CHANNEL PER LANE: the 16 lanes of a sample cover 16
-// consecutive channels = one 64-B line per tap, so every atomic instruction touches 4 lines x 16 lanes (a 4-lane/float4
-// mapping would visit each line four times). `coff` = channel index of this lane inside the C-channel texel, `g` =
-// dL/d(P_c * L_c) for that channel. Value taps are re-gathered (scalar, coalesced per 16 lanes).
-template <int K>
-__device__ __forceinline__ void scatter_chan(const FactorSet& S, const GradSet& G, int C, int coff, float xn, float yn, float zn,
-                                             float g) {
-    TapIdx o;
-    compute_taps<K>(S, C / 4, 0, xn, yn, zn, o);   // float4-unit offsets of channel 0 of each tap
-    const float* __restrict__ P = S.plane[K];
-    const float* __restrict__ Ln = S.line[K];
-    const unsigned nw = o.nw * 4 + coff, ne = o.ne * 4 + coff, sw = o.sw * 4 + coff, se = o.se * 4 + coff;
-    const unsigned l0 = o.l0 * 4 + coff, l1 = o.l1 * 4 + coff;
-    float pv = P[nw] * o.wnw;
-    pv = fmaf(P[ne], o.wne, pv); pv = fmaf(P[sw], o.wsw, pv); pv = fmaf(P[se], o.wse, pv);
-    const float lv = fmaf(Ln[l1], o.wl1, Ln[l0] * o.wl0);
-    const float gp = g * lv, gl = g * pv;
-    float* gP = G.plane[K];
-    float* gL = G.line[K];
-    if (o.wnw != 0.f) atomicAdd(gP + nw, gp * o.wnw);
-    if (o.wne != 0.f) atomicAdd(gP + ne, gp * o.wne);
-    if (o.wsw != 0.f) atomicAdd(gP + sw, gp * o.wsw);
-    if (o.wse != 0.f) atomicAdd(gP + se, gp * o.wse);
-    if (o.wl0 != 0.f) atomicAdd(gL + l0, gl * o.wl0);
-    if (o.wl1 != 0.f) atomicAdd(gL + l1, gl * o.wl1);
 }
 
 // Sliding-window scatter: consecutive samples of a ray (and consecutive appearance samples of the list) move by less
@@ -182,9 +151,7 @@ __device__ __forceinline__ void scatter_win(const FactorSet& S, const GradSet& G
 // (3) write a 16-B record per sample into its bin's run, (4) one workgroup per segment of one bin's records accumulates in
 // LDS and flushes once. Appearance: bins = 16x16-texel plane tiles (one record per sample AND plane; ds_add_f64 on a staged
 // 17x17x16 tile + the whole line, k_bwd_tile_accum). Density: bins = 15^3-cell blocks, one record per sample (k_bwd_den_block).
-constexpr int kBinTile = 16;      // texels per tile edge (footprints reach one texel further: 17 staged)
-constexpr int kBinCopies = 32;    // privatised histogram / cursor copies (every ray starts in the camera's tile)
-constexpr int kBinSegApp = 512;   // smallest segment (sizes the segment list); the scan picks the actual size per call
+// (the bins' constants and geometries: t2n_backward.h) Segments of the appearance accumulate: kBinSegApp records at least
 // (512 work items of >= 512 records until the staging of a segment got cheap — round 6 — and the accounting showed its fixed cost
 // per segment: 256 items of >= 1 024 records now, -1 ... -2 % of the 16 384-ray step; 256-record segments: +8 %; profiles/round6_train_ab.txt)
 #ifndef T2N_ACC_TARGET_SEGS_APP
@@ -196,18 +163,6 @@ constexpr int kBinSegApp = 512;   // smallest segment (sizes the segment list); 
 constexpr unsigned kAccTargetSegsApp = T2N_ACC_TARGET_SEGS_APP;   // accumulate work items aimed at: whole rounds over 256 CUs
 constexpr unsigned kAccGrid = 2048;   // accumulate workgroups launched (grid-stride over the segment list)
 
-struct BinGeom { int tw[3], before[3], total; };
-static BinGeom bin_geom(const FactorSet& S) {
-    BinGeom g;
-    int t = 0;
-    for (int k = 0; k < 3; ++k) {
-        g.tw[k] = (S.W[k] + kBinTile) / kBinTile;              // cell + 1 in [0, W]
-        g.before[k] = t;
-        t += g.tw[k] * ((S.H[k] + kBinTile) / kBinTile);
-    }
-    g.total = t;
-    return g;
-}
 // tile ids (global over the three planes) of a sample; axis a of the grid pairs with coordinate a (see sample_axes)
 __device__ __forceinline__ void bin_keys(const FactorSet& S, const BinGeom& G, float xn, float yn, float zn, int key[3]) {
     const int cx = (axis_cell(xn, S.W[0]) + 1) / kBinTile, cy = (axis_cell(yn, S.H[0]) + 1) / kBinTile,
@@ -216,22 +171,7 @@ __device__ __forceinline__ void bin_keys(const FactorSet& S, const BinGeom& G, f
     key[1] = G.before[1] + cz * G.tw[1] + cx;
     key[2] = G.before[2] + cz * G.tw[2] + cy;
 }
-// Density: 3-D blocks of kBlk^3 cells (k_bwd_den_block). The three density pairs share their axes (plane k spans two of them, line k the
-// third), so ONE key per sample serves all six gradients. cell + 1 lies in [0, size]: (size + kBlk) / kBlk blocks per axis.
-constexpr int kBlk = 15;          // cells per block edge: taps reach one further, 16 per axis = the MFMA tile edge
-struct BlockGeom { int nb[3]; int size[3]; int total; int copies; };
-static BlockGeom block_geom(const FactorSet& S) {
-    BlockGeom g;
-    g.size[0] = S.W[0]; g.size[1] = S.H[0]; g.size[2] = S.H[1];
-    for (int a = 0; a < 3; ++a) g.nb[a] = (g.size[a] + kBlk) / kBlk;
-    g.total = g.nb[0] * g.nb[1] * g.nb[2];
-    g.copies = kBinCopies;   // privatised histogram copies (every ray starts in the camera's block)
-    return g;
-}
-// the density pairs really share their axes (TensorVMSplit: plane k = grid[mat1] x grid[mat0], line k = grid[vec])
-static bool block_geom_ok(const FactorSet& S) {
-    return S.C == 16 && S.W[1] == S.W[0] && S.L[2] == S.W[0] && S.W[2] == S.H[0] && S.L[1] == S.H[0] && S.H[2] == S.H[1] && S.L[0] == S.H[1];
-}
+// density: the key of a sample's 15^3-cell block (BlockGeom, t2n_backward.h): ONE key per sample serves all six gradients
 __device__ __forceinline__ int block_key(const BlockGeom& G, float xn, float yn, float zn) {
     const int bx = (axis_cell(xn, G.size[0]) + 1) / kBlk, by = (axis_cell(yn, G.size[1]) + 1) / kBlk, bz = (axis_cell(zn, G.size[2]) + 1) / kBlk;
     return (bz * G.nb[1] + by) * G.nb[0] + bx;
@@ -698,8 +638,7 @@ constexpr int kGsize = kBlkE * kGsz;
 constexpr int kDenThreads = 512;
 // records per segment: a block's six result tiles are flushed (12 288 + 1 536 global atomics) once per SEGMENT, and the splat itself is
 // cheap (~8 ns per 1000 records per CU), so blocks are split only when they hold very many records (the camera's block of a C3
-// batch: 57 000 of 2.5 M): 4 000 segments of ~700 records took 262 us, 1 300 of up to 16 384 take 73
-constexpr unsigned kDenSeg = 16384;
+// batch: 57 000 of 2.5 M): 4 000 segments of ~700 records took 262 us, 1 300 of up to 16 384 (kDenSeg) take 73
 struct DenBlockArgs {
     FactorSet S; GradSet G; BlockGeom geom; const int4* segs; const unsigned* nseg; const float4* recs;
 };
@@ -1157,7 +1096,10 @@ __global__ __launch_bounds__(256) void k_early_bins(const AppBinArgs ab, const B
     else den_count_body<true>(ca, blockIdx.x - nb_app);
 }
 // doubles: tile + line accumulators; floats: staged values; per-wave tap tables (64 records x 3 float4)
-static size_t tile_accum_lds(int C, int Lmax, int threads = kAccThreads) {
+// (the lines staged whole: sized for the longest of the grid's three)
+static size_t tile_accum_lds(const FactorSet& S, int C, int threads = kAccThreads) {
+    int Lmax = 0;
+    for (int k = 0; k < 3; ++k) Lmax = S.L[k] > Lmax ? S.L[k] : Lmax;
     const size_t cells = (size_t)(kBinTile + 1) * (kBinTile + 1) * C + (size_t)(Lmax + 2) * C;
     return cells * 8 + cells * 4 + (size_t)(threads / 64) * 64 * 3 * 16;
 }
@@ -1262,45 +1204,140 @@ int shared_side_streams(void** a, void** b) {
     if (b && !*b) *b = (void*)g_side[dev][1];
     return T2N_OK;
 }
+int ensure_side_streams(t2n_field* f, bool streams) {
+    if (streams && (!f->side_stream || !f->gemm_stream)) { const int rc = shared_side_streams(&f->side_stream, &f->gemm_stream); if (rc) return rc; }
+    void** const own[6] = {&f->ev_fork, &f->ev_join, &f->ev_fork2, &f->ev_join2, &f->ev_pack, &f->ev_den};
+    auto make = [](void*& e) { hipEvent_t x; T2N_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming)); e = (void*)x; return (int)T2N_OK; };
+    for (void** e : own) if (!*e) { const int rc = make(*e); if (rc) return rc; }
+    for (void*& e : f->train_ev) if (!e) { const int rc = make(e); if (rc) return rc; }
+    return T2N_OK;
+}
 
-// Activation / gradient rows of the backward pass. Buffers whose lifetimes do not overlap (or that are rewritten
-// element-in-place by the same thread) share storage: g1 over h1, g0 over h0, gx over xpe, gf over feat32, gX over x144.
-struct BwdCarve { size_t x144, feat32, h0, h1, go, xpe, part, gpack, hist, bin_total, tile_start, nseg, segs, recs, a_hist, a_bin_total, a_tile_start, a_nseg, a_segs, a_recs, plan, total; unsigned seg_cap, a_seg_cap; };
-static size_t al256(size_t x) { return (x + 255) / 256 * 256; }
-static BwdCarve bwd_carve(int64_t rows, int64_t n_rays, int n_samples, int n_tiles, int n_blocks, int k0 = 351, bool rows_kept = false) {   // k0: inputs of MLP layer 0; n_blocks: density bins x copies; rows_kept: the activation rows live in the forward's workspace (fused step): none here
-    BwdCarve c;
-    size_t o = 0;
-    const size_t R = (size_t)rows;
-    const size_t RA = rows_kept ? 0 : R;
-    c.x144 = o; o = al256(o + RA * 144 * 4);
-    c.feat32 = o; o = al256(o + RA * 32 * 4);
-    c.h0 = o; o = al256(o + RA * 128 * 4);
-    c.h1 = o; o = al256(o + RA * 128 * 4);
-    c.go = o; o = al256(o + R * 16);
-    // (fused step: the encoding is never materialised — the rows hold G0 [128] | GF [32] | GX [144] only)
-    c.xpe = o; o = al256(o + R * (size_t)(rows_kept ? 304 : ((k0 + 3) & ~3)) * 4);
-    c.part = o; o = al256(o + tn_part_bytes(rows, k0));
-    c.gpack = o; o = al256(o + (gemm_h_pack_bytes(k0) > mlp_bwd_ss_pack_bytes() ? gemm_h_pack_bytes(k0) : mlp_bwd_ss_pack_bytes()));   // packed W^T operands of the input-gradient GEMMs (t2n_gemm_h.hip / t2n_mlp_bwd_ss.hip)
-    // block-binned density scatter: worst case one record per sample
-    const size_t cap = (size_t)n_rays * (size_t)n_samples;
-    c.seg_cap = (unsigned)(cap / kDenSeg + (size_t)n_blocks + 1);
-    c.hist = o; o = al256(o + (size_t)n_blocks * 4);
-    c.bin_total = o; o = al256(o + (size_t)n_blocks * 4);
-    c.tile_start = o; o = al256(o + ((size_t)n_blocks + 1) * 4);
-    c.nseg = o; o = al256(o + 4);
-    c.segs = o; o = al256(o + (size_t)c.seg_cap * 16);
-    c.recs = o; o = al256(o + cap * 16);
-    // the same for the appearance samples (one record per activation row and plane)
-    c.a_seg_cap = (unsigned)(3 * R / kBinSegApp + (size_t)n_tiles + 1);
-    c.a_hist = o; o = al256(o + (size_t)n_tiles * kBinCopies * 4);
-    c.a_bin_total = o; o = al256(o + (size_t)n_tiles * 4);
-    c.a_tile_start = o; o = al256(o + ((size_t)n_tiles + 1) * 4);
-    c.a_nseg = o; o = al256(o + 4);
-    c.a_segs = o; o = al256(o + (size_t)c.a_seg_cap * 16);
-    c.a_recs = o; o = al256(o + 3 * R * 16);
-    c.plan = o; o = al256(o + sizeof(BwdPlan));
-    c.total = o;
-    return c;
+// ---- one launcher per stage (t2n_backward.h) -----------------------------------------------------------------------------------------
+bool binned_scatter_ok(const t2n_field* f, int64_t n_rays, int n_samples) {
+    // T2N_BWD_ATOMIC_SCATTER=1 asks for the sliding-window global-atomic path (read once per process)
+    static const bool force_atomic = getenv("T2N_BWD_ATOMIC_SCATTER") && atoi(getenv("T2N_BWD_ATOMIC_SCATTER")) != 0;
+    return !force_atomic && tile_accum_lds(f->dev.den, 16) <= 160 * 1024 && block_geom_ok(f->dev.den) && (uint64_t)n_rays * n_samples * 3 < 0x7fffffffull;
+}
+static GradSet grad_set(const t2n_field* f, bool app) {
+    GradSet g;
+    for (int k = 0; k < 3; ++k) { g.plane[k] = app ? f->gbuf_app_plane[k] : f->gbuf_den_plane[k]; g.line[k] = app ? f->gbuf_app_line[k] : f->gbuf_den_line[k]; }
+    return g;
+}
+// the field as the kernels of this call see it: NDC calls carry their depth table in `jitter`
+static FieldDev call_field(const BwdCall& k) {
+    FieldDev F = k.f->dev;
+    F.ztab = (k.flags & T2N_FLAG_NDC) ? k.jitter : nullptr;
+    return F;
+}
+static unsigned ray_blocks(const BwdCall& k) { return (unsigned)((k.n_rays + 3) / 4); }   // one wave per ray
+
+int launch_bwd_march(const BwdCall& k, bool bin, const float* d_rgb, const float* d_depth, const float* d_w, hipStream_t s, const BwdLoss* loss,
+                     bool count) {
+    const bool train = (k.flags & T2N_FLAG_TRAIN) != 0;
+    if ((loss && !(train && bin)) || (!count && !loss)) { set_error("launch_bwd_march: no such form of the per-ray pass"); return T2N_ERR_INVALID; }
+    BwdMarchArgs a{};
+    a.F = call_field(k);
+    a.gden = grad_set(k.f, false);
+    a.rays = k.rays; a.n_rays = k.n_rays; a.ray_stride = k.ray_stride; a.n_samples = k.n_samples; a.npad = (k.n_samples + 63) & ~63;
+    a.jitter = k.jitter; a.sigma = (const float*)(k.fw + k.c.sigma); a.ray_app = (const int4*)(k.fw + k.c.ray_app);
+    a.app_rgb = (const float4*)(k.fw + k.c.app_rgb); a.rgb_raw = (const float4*)(k.fw + k.c.rgb_raw);
+    a.d_rgb = d_rgb; a.d_depth = d_depth; a.d_w = d_w; a.go = (float4*)(k.bw + k.b.go); a.list_cap = k.c.list_cap; a.tp = k.tp; a.plan = k.plan;
+    a.add_bg = (k.flags & T2N_FLAG_ADD_BG) ? 1 : 0;
+    a.gfeat = (float*)(k.fw + k.c.sigma); a.hist = (unsigned*)(k.bw + k.b.hist); a.geom = block_geom(k.f->dev.den);
+    if (loss) {
+        a.rgb = loss->rgb; a.depth = loss->depth; a.rgb_t = loss->rgb_t; a.depth_t = loss->depth_t;
+        a.w_depth = loss->w_depth; a.w_trans = loss->w_trans; a.delta = loss->delta; a.loss_part = loss->part;
+    }
+    const size_t lds = (size_t)4 * 4 * a.npad * sizeof(float);
+    const dim3 grid(ray_blocks(k));
+    if (loss && !count) hipLaunchKernelGGL((k_bwd_march<true, true, true, false>), grid, dim3(256), lds, s, a);
+    else if (loss) hipLaunchKernelGGL((k_bwd_march<true, true, true>), grid, dim3(256), lds, s, a);
+    else if (bin && train) hipLaunchKernelGGL((k_bwd_march<true, true>), grid, dim3(256), lds, s, a);
+    else if (bin) hipLaunchKernelGGL((k_bwd_march<false, true>), grid, dim3(256), lds, s, a);
+    else if (train) hipLaunchKernelGGL((k_bwd_march<true, false>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((k_bwd_march<false, false>), grid, dim3(256), lds, s, a);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
+int launch_den_scan(const BwdCall& k, hipStream_t s) {
+    const BlockGeom g = block_geom(k.f->dev.den);
+    const BwdCarve& b = k.b;
+    launch_bin_scan((unsigned*)(k.bw + b.hist), g.total, g.copies, (unsigned*)(k.bw + b.bin_total), (unsigned*)(k.bw + b.tile_start), (int4*)(k.bw + b.segs),
+                    (unsigned*)(k.bw + b.nseg), b.seg_cap, kDenSeg, 0u, kDenSeg, s);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+// (the counting pass of k_early_bins reads the field, the geometry, the rays and the cursor only)
+static BinArgs den_bin_args(const BwdCall& k) {
+    BinArgs ba;
+    ba.F = call_field(k); ba.geom = block_geom(k.f->dev.den);
+    ba.rays = k.rays; ba.n_rays = k.n_rays; ba.ray_stride = k.ray_stride; ba.n_samples = k.n_samples;
+    ba.jitter = k.jitter; ba.gfeat = (const float*)(k.fw + k.c.sigma); ba.ray_app = (const int4*)(k.fw + k.c.ray_app);
+    ba.cursor = (unsigned*)(k.bw + k.b.hist); ba.tile_start = (const unsigned*)(k.bw + k.b.tile_start); ba.recs = (float4*)(k.bw + k.b.recs);
+    return ba;
+}
+int launch_den_scatter(const BwdCall& k, bool all, hipStream_t s) {
+    const bool train = (k.flags & T2N_FLAG_TRAIN) != 0;
+    if (all && !train) { set_error("launch_den_scatter: records of every in-box sample are a form of train calls"); return T2N_ERR_INVALID; }
+    const BinArgs ba = den_bin_args(k);
+    if (all) hipLaunchKernelGGL((k_bwd_bin<true, true>), dim3(ray_blocks(k)), dim3(256), 0, s, ba);
+    else if (train) hipLaunchKernelGGL((k_bwd_bin<true>), dim3(ray_blocks(k)), dim3(256), 0, s, ba);
+    else hipLaunchKernelGGL((k_bwd_bin<false>), dim3(ray_blocks(k)), dim3(256), 0, s, ba);
+    DenBlockArgs da;
+    da.S = k.f->dev.den; da.G = grad_set(k.f, false); da.geom = ba.geom; da.segs = (const int4*)(k.bw + k.b.segs);
+    da.nseg = (const unsigned*)(k.bw + k.b.nseg); da.recs = (const float4*)(k.bw + k.b.recs);
+    hipLaunchKernelGGL(k_bwd_den_block, dim3(k.b.seg_cap < kAccGrid ? k.b.seg_cap : kAccGrid), dim3(kDenThreads), 0, s, da);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
+static AppBinArgs app_bin_args(const BwdCall& k) {
+    AppBinArgs ab;
+    ab.S = k.f->dev.app; ab.geom = bin_geom(k.f->dev.app); ab.app_pos = (const float4*)(k.fw + k.c.app_pos);
+    ab.counters = (const unsigned*)(k.fw + k.c.counters); ab.list_cap = k.c.list_cap; ab.tp = k.tp; ab.rows = k.rows; ab.plan = k.plan;
+    ab.hist = (unsigned*)(k.bw + k.b.a_hist); ab.tile_start = (const unsigned*)(k.bw + k.b.a_tile_start); ab.recs = (float4*)(k.bw + k.b.a_recs);
+    return ab;
+}
+static unsigned app_bin_blocks(const BwdCall& k) { return (unsigned)((k.rows + 255) / 256); }   // one lane per row
+int launch_app_count(const BwdCall& k, bool with_density, hipStream_t s) {
+    if (with_density && !(k.flags & T2N_FLAG_TRAIN)) { set_error("launch_app_count: the early density count is a form of train calls"); return T2N_ERR_INVALID; }
+    const AppBinArgs ab = app_bin_args(k);
+    const unsigned nbk = app_bin_blocks(k);
+    if (with_density) hipLaunchKernelGGL(k_early_bins, dim3(nbk + ray_blocks(k)), dim3(256), 0, s, ab, den_bin_args(k), nbk);
+    else hipLaunchKernelGGL((k_app_bin<0>), dim3(nbk), dim3(256), 0, s, ab);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+int launch_app_records(const BwdCall& k, bool scan_one_launch, hipStream_t s) {
+    const AppBinArgs ab = app_bin_args(k);
+    const BwdCarve& b = k.b;
+    launch_bin_scan(ab.hist, ab.geom.total, kBinCopies, (unsigned*)(k.bw + b.a_bin_total), (unsigned*)(k.bw + b.a_tile_start), (int4*)(k.bw + b.a_segs),
+                    (unsigned*)(k.bw + b.a_nseg), b.a_seg_cap, 0u, kAccTargetSegsApp, (unsigned)T2N_ACC_SEG_MIN, s, scan_one_launch);
+    hipLaunchKernelGGL((k_app_bin<1>), dim3(app_bin_blocks(k)), dim3(256), 0, s, ab);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+int launch_app_accum(const BwdCall& k, const float* gx, bool half_groups, hipStream_t s) {
+    TileAccumArgs ta;
+    ta.S = k.f->dev.app; ta.G = grad_set(k.f, true); ta.geom = bin_geom(k.f->dev.app); ta.segs = (const int4*)(k.bw + k.b.a_segs);
+    ta.nseg = (const unsigned*)(k.bw + k.b.a_nseg); ta.recs = (const float4*)(k.bw + k.b.a_recs);
+    ta.gx = gx; ta.gx_ld = 144;
+    static bool attr_set = false;
+    if (!attr_set) {
+        T2N_HIP(hipFuncSetAttribute((const void*)k_bwd_tile_accum<48>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        T2N_HIP(hipFuncSetAttribute((const void*)k_bwd_tile_accum<48, 8, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
+        attr_set = true;
+    }
+    const unsigned segs = k.b.a_seg_cap < kAccGrid ? k.b.a_seg_cap : kAccGrid;
+    const size_t lds8 = tile_accum_lds(k.f->dev.den, 8, 256);
+    if (half_groups && lds8 <= 80 * 1024)   // two workgroups per CU: one accumulates while the other stages / zeroes / flushes
+        hipLaunchKernelGGL((k_bwd_tile_accum<48, 8, 256>), dim3(segs, 6), dim3(256), lds8, s, ta);
+    else
+        hipLaunchKernelGGL((k_bwd_tile_accum<48>), dim3(segs, 3), dim3(kAccThreads), tile_accum_lds(k.f->dev.den, 16), s, ta);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
 }
 
 // the 12 channel-last gradient buffers are slices of ONE allocation (density planes, density lines, appearance planes, appearance
@@ -1347,25 +1384,11 @@ static int ensure_grad_buffers(t2n_field* f) {
 // next capacity from it without ever waiting: every record arrives, late at worst.
 __global__ __launch_bounds__(64) void k_bwd_plan(const unsigned* __restrict__ counters, unsigned list_cap, unsigned rows_cap, unsigned kept_rows,
                                                  BwdPlan* __restrict__ plan, unsigned* host_rec, unsigned seq) {
-    const int lane = threadIdx.x;
-    unsigned cnt = lane < kLists ? counters[lane * kCounterStride] : 0u;
-    if (cnt > list_cap) cnt = list_cap;
-    unsigned incl = (cnt + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    const unsigned excl = incl - (cnt + 31u) / 32u;
-    if (lane < kLists) plan->tp.t[lane] = excl;
-    const unsigned total = __shfl(incl, kLists - 1);
-    if (lane == 0) {
-        plan->tp.t[kLists] = total;
-        const bool stated = counters[kKeptMagicWord] == kKeptMagic && counters[kKeptRowsWord] == kept_rows;
-        const unsigned rows = total * 32u;
-        const unsigned ovf = (!stated || rows > rows_cap) ? 1u : 0u;
-        plan->overflow = ovf;
-        plan->rows = !stated ? 0u : (rows < rows_cap ? rows : rows_cap);
+    // (the forward's statement, read by every lane: uniform loads)
+    const bool stated = counters[kKeptMagicWord] == kKeptMagic && counters[kKeptRowsWord] == kept_rows;
+    unsigned ovf;
+    const unsigned rows = plan_prefix(counters, list_cap, rows_cap, stated, plan, ovf);
+    if (threadIdx.x == 0) {
         if (host_rec) {
             volatile unsigned* h = host_rec;
             h[seq & 7u] = rows;
@@ -1508,6 +1531,8 @@ extern "C" int t2n_render_backward(t2n_field* f, const float* rays, int64_t n_ra
     int rc = T2N_OK;
     const BinGeom geom = bin_geom(f->dev.den);
     const BlockGeom bgeom = block_geom(f->dev.den);
+    // binned scatters (density: 3-D blocks; appearance: plane tiles) where they serve this call, else the sliding-window global-atomic paths
+    const bool bin = binned_scatter_ok(f, n_rays, n_samples);
     // T2N_FLAG_DEVICE_ROWS: nothing is read back. The row CAPACITY is what both workspaces hold (the forward's kept activation rows, the
     // backward's row buffers); k_bwd_plan derives tile prefix and row count on the device and every row-streaming kernel clips to it.
     const bool dev_rows = (flags & T2N_FLAG_DEVICE_ROWS) != 0;
@@ -1519,16 +1544,8 @@ extern "C" int t2n_render_backward(t2n_field* f, const float* rays, int64_t n_ra
         }
         // EVERY precondition of the device-side plan is checked here, before anything is launched or forked (the checks further
         // down stay as assertions: a refusal there would leave queued kernels and unjoined side streams behind)
-        {
-            int Lm = 0;
-            for (int k = 0; k < 3; ++k) Lm = f->dev.den.L[k] > Lm ? f->dev.den.L[k] : Lm;
-            const bool force_atomic_env = getenv("T2N_BWD_ATOMIC_SCATTER") && atoi(getenv("T2N_BWD_ATOMIC_SCATTER")) != 0;
-            if (force_atomic_env || tile_accum_lds(16, Lm) > 160 * 1024 || !block_geom_ok(f->dev.den) || (uint64_t)n_rays * n_samples * 3 >= 0x7fffffffull) {
-                set_error("t2n_render_backward: T2N_FLAG_DEVICE_ROWS needs the binned scatters (grid lines within the LDS budget)");
-                return T2N_ERR_UNSUPPORTED;
-            }
-            if (!g->mlp_w1 || !g->mlp_w0) { set_error("t2n_render_backward: T2N_FLAG_DEVICE_ROWS needs the weight-gradient tensors of both hidden layers"); return T2N_ERR_INVALID; }
-        }
+        if (!bin) { set_error("t2n_render_backward: T2N_FLAG_DEVICE_ROWS needs the binned scatters (grid lines within the LDS budget)"); return T2N_ERR_UNSUPPORTED; }
+        if (!g->mlp_w1 || !g->mlp_w0) { set_error("t2n_render_backward: T2N_FLAG_DEVICE_ROWS needs the weight-gradient tensors of both hidden layers"); return T2N_ERR_INVALID; }
         int64_t lo = 0, hi = (int64_t)kc.rows / 32;     // largest capacity (in tiles) whose backward buffers fit
         while (lo < hi) {
             const int64_t mid = (lo + hi + 1) / 2;
@@ -1598,112 +1615,41 @@ extern "C" int t2n_render_backward(t2n_field* f, const float* rays, int64_t n_ra
     timing_end(f, T2N_K_BWD_MLP, s);
 
     // 2. per-ray backward + density scatter
-    bool side = false;   // the density scatter was put on the side stream: joined before step 6
-    hipStream_t den_stream = s;   // the stream the density gradients are finished on
+    static const bool serial = getenv("T2N_BWD_SERIAL") != nullptr;
+    const bool side = bin && !serial && rows > 0;   // the density scatter goes on the side stream: joined before step 6
+    if ((rc = ensure_side_streams(f, side))) return rc;
+    hipStream_t sd = (hipStream_t)f->side_stream, sg = (hipStream_t)f->gemm_stream;
+    const BwdCall call{f, rays, n_rays, ray_stride, n_samples, jitter, flags, fw, c, bw, b, tp, plan, rows};
     bool side_gemm = false;   // the weight-gradient GEMMs were put on the third stream: joined before step 6
-    bool packed_early = false;   // k_mlp_bwd_ss's operands were packed in front of k_bwd_march
-    bool pack_side = false;      // ... on the third stream: joined in front of k_mlp_bwd_ss
-    bool bin = false;
-    size_t lds_bin = 0;
-    {
-        BwdMarchArgs a;
-        a.F = f->dev;
-        for (int k = 0; k < 3; ++k) { a.gden.plane[k] = f->gbuf_den_plane[k]; a.gden.line[k] = f->gbuf_den_line[k]; }
-        a.rays = rays; a.n_rays = n_rays; a.ray_stride = ray_stride; a.n_samples = n_samples; a.npad = (n_samples + 63) & ~63;
-        a.jitter = jitter; a.sigma = (const float*)(fw + c.sigma); a.ray_app = (const int4*)(fw + c.ray_app);
-        a.app_rgb = app_rgb; a.rgb_raw = (const float4*)(fw + c.rgb_raw);
-        a.d_rgb = d_rgb; a.d_depth = d_depth; a.d_w = d_weights; a.go = go; a.list_cap = c.list_cap; a.tp = tp; a.plan = plan;
-        a.add_bg = (flags & T2N_FLAG_ADD_BG) ? 1 : 0;
-        const size_t lds = (size_t)4 * 4 * a.npad * sizeof(float);
-        const unsigned nb = (unsigned)((n_rays + 3) / 4);
-        // binned scatters (density: 3-D blocks; appearance: plane tiles, as long as the grid's lines fit the LDS budget) unless
-        // T2N_BWD_ATOMIC_SCATTER=1 asks for the sliding-window global-atomic path
-        int Lmax = 0;
-        for (int k = 0; k < 3; ++k) Lmax = f->dev.den.L[k] > Lmax ? f->dev.den.L[k] : Lmax;
-        const size_t lds_acc = tile_accum_lds(16, Lmax);
-        static const bool force_atomic = getenv("T2N_BWD_ATOMIC_SCATTER") && atoi(getenv("T2N_BWD_ATOMIC_SCATTER")) != 0;
-        bin = !force_atomic && lds_acc <= 160 * 1024 && block_geom_ok(f->dev.den) && (uint64_t)n_rays * n_samples * 3 < 0x7fffffffull;
-        lds_bin = lds_acc;
-        if (plan && !bin) { set_error("t2n_render_backward: T2N_FLAG_DEVICE_ROWS needs the binned scatters (grid lines within the LDS budget)"); return T2N_ERR_UNSUPPORTED; }
-        a.gfeat = (float*)(fw + c.sigma); a.hist = (unsigned*)(bw + b.hist); a.geom = bgeom;
-        if (bin) {
-            so.zero(a.hist, (size_t)bgeom.total * bgeom.copies * 4);
-            if (rows > 0 && f->dev.app.C == 48) so.zero(bw + b.a_hist, (size_t)bin_geom(f->dev.app).total * kBinCopies * 4);
-        }
-        // the fused input-gradient chain's operands are packed now, while the stream is alone on the GPU
-        const bool pack_now = rows > 0 && !generic && !simple && !gemm_fp32_mode(f) && f->desc.app_dim == 27 && K0 == 351;
-        if (pack_now) so.zero(mlp_bwd_ss_absmax_words((void*)(bw + b.gpack)), 16);
-        if ((rc = launch_setup(so, s))) return rc;
-        static const bool serial = getenv("T2N_BWD_SERIAL") != nullptr;
-        if (pack_now) {
-            // ... on the third stream (idle until the weight-gradient GEMMs): two 6-us kernels off the caller's stream, joined in front
-            // of k_mlp_bwd_ss, behind k_bwd_march and layer 2
-            hipStream_t sp = s;
-#ifndef T2N_PACK_ON_CALLER_STREAM
-#define T2N_PACK_ON_CALLER_STREAM 0
-#endif
-            if (!serial && bin && !T2N_PACK_ON_CALLER_STREAM) {
-                if (!f->gemm_stream || !f->ev_fork2) {
-                    hipEvent_t e0, e1;
-                    { const int rcs = shared_side_streams(&f->side_stream, &f->gemm_stream); if (rcs) return rcs; }
-                    T2N_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-                    T2N_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-                    f->ev_fork2 = (void*)e0; f->ev_join2 = (void*)e1;
-                }
-                if (!f->ev_pack) { hipEvent_t e; T2N_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); f->ev_pack = (void*)e; }
-                sp = (hipStream_t)f->gemm_stream;
-                T2N_HIP(hipEventRecord((hipEvent_t)f->ev_fork2, s));
-                T2N_HIP(hipStreamWaitEvent(sp, (hipEvent_t)f->ev_fork2, 0));
-                pack_side = true;
-            }
-            if ((rc = mlp_bwd_ss_pack(f, (void*)(bw + b.gpack), sp, true, true))) return rc;
-            if (pack_side) T2N_HIP(hipEventRecord((hipEvent_t)f->ev_pack, sp));
-        }
-        packed_early = pack_now;
-        timing_begin(f, T2N_K_BWD_MARCH, s);
-        if (!bin) {
-            if (flags & T2N_FLAG_TRAIN) hipLaunchKernelGGL((k_bwd_march<true, false>), dim3(nb), dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((k_bwd_march<false, false>), dim3(nb), dim3(256), lds, s, a);
-        } else {
-            if (flags & T2N_FLAG_TRAIN) hipLaunchKernelGGL((k_bwd_march<true, true>), dim3(nb), dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((k_bwd_march<false, true>), dim3(nb), dim3(256), lds, s, a);
-            // The density scatter (scan -> records -> LDS accumulate: atomic-latency- and LDS-bound, little VALU, no MFMA) shares
-            // nothing with the MLP backward and the appearance scatter below but the finished k_bwd_march: it runs on a side stream
-            // beside them and is joined before the gradients leave this call (T2N_BWD_SERIAL=1: one stream).
-            hipStream_t sd = s;
-            if (!serial && rows > 0) {
-                if (!f->side_stream || !f->ev_fork) {
-                    hipEvent_t e0, e1;
-                    { const int rcs = shared_side_streams(&f->side_stream, &f->gemm_stream); if (rcs) return rcs; }
-                    T2N_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-                    T2N_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-                    f->ev_fork = (void*)e0; f->ev_join = (void*)e1;
-                }
-                sd = (hipStream_t)f->side_stream;
-                T2N_HIP(hipEventRecord((hipEvent_t)f->ev_fork, s));
-                T2N_HIP(hipStreamWaitEvent(sd, (hipEvent_t)f->ev_fork, 0));
-                side = true;
-            }
-            launch_bin_scan(a.hist, bgeom.total, bgeom.copies, (unsigned*)(bw + b.bin_total), (unsigned*)(bw + b.tile_start), (int4*)(bw + b.segs), (unsigned*)(bw + b.nseg), b.seg_cap, kDenSeg,
-                            0u, kDenSeg, sd);
-            BinArgs ba;
-            ba.F = f->dev; ba.geom = bgeom; ba.rays = rays; ba.n_rays = n_rays; ba.ray_stride = ray_stride; ba.n_samples = n_samples;
-            ba.jitter = jitter; ba.gfeat = a.gfeat; ba.ray_app = a.ray_app; ba.cursor = a.hist; ba.tile_start = (const unsigned*)(bw + b.tile_start); ba.recs = (float4*)(bw + b.recs);
-            if (flags & T2N_FLAG_TRAIN) hipLaunchKernelGGL((k_bwd_bin<true>), dim3(nb), dim3(256), 0, sd, ba);
-            else hipLaunchKernelGGL((k_bwd_bin<false>), dim3(nb), dim3(256), 0, sd, ba);
-            DenBlockArgs da;
-            da.S = f->dev.den; da.G = a.gden; da.geom = bgeom; da.segs = (const int4*)(bw + b.segs);
-            da.nseg = (const unsigned*)(bw + b.nseg); da.recs = (const float4*)(bw + b.recs);
-            hipLaunchKernelGGL(k_bwd_den_block, dim3(b.seg_cap < kAccGrid ? b.seg_cap : kAccGrid), dim3(kDenThreads), 0, sd, da);
-            if (side) T2N_HIP(hipEventRecord((hipEvent_t)f->ev_join, sd));
-            den_stream = sd;
-        }
-        // the density gradients of this call are final behind this point of `den_stream` (t2n_field_wait_density_grads)
-        if (!f->ev_den) { hipEvent_t e; T2N_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); f->ev_den = (void*)e; }
-        T2N_HIP(hipEventRecord((hipEvent_t)f->ev_den, den_stream));
-        timing_end(f, T2N_K_BWD_MARCH, s);
-        T2N_HIP(hipGetLastError());
+    // the fused input-gradient chain's operands are packed now, while the stream is alone on the GPU
+    const bool packed_early = rows > 0 && !generic && !simple && !gemm_fp32_mode(f) && f->desc.app_dim == 27 && K0 == 351;
+    const bool pack_side = packed_early && side;   // ... on the third stream: joined in front of k_mlp_bwd_ss
+    if (bin) {
+        so.zero(bw + b.hist, (size_t)bgeom.total * bgeom.copies * 4);
+        if (rows > 0 && f->dev.app.C == 48) so.zero(bw + b.a_hist, (size_t)bin_geom(f->dev.app).total * kBinCopies * 4);
     }
+    if (packed_early) so.zero(mlp_bwd_ss_absmax_words((void*)(bw + b.gpack)), 16);
+    if ((rc = launch_setup(so, s))) return rc;
+    if (packed_early) {
+        // ... on the third stream (idle until the weight-gradient GEMMs): two 6-us kernels off the caller's stream, joined in front
+        // of k_mlp_bwd_ss, behind k_bwd_march and layer 2
+        if (pack_side && (rc = fork_stream(s, sg, f->ev_fork2))) return rc;
+        if ((rc = mlp_bwd_ss_pack(f, (void*)(bw + b.gpack), pack_side ? sg : s, true, true))) return rc;
+        if (pack_side) T2N_HIP(hipEventRecord((hipEvent_t)f->ev_pack, sg));
+    }
+    timing_begin(f, T2N_K_BWD_MARCH, s);
+    if ((rc = launch_bwd_march(call, bin, d_rgb, d_depth, d_weights, s))) return rc;
+    if (bin) {
+        // The density scatter (scan -> records -> LDS accumulate: atomic-latency- and LDS-bound, little VALU, no MFMA) shares
+        // nothing with the MLP backward and the appearance scatter below but the finished k_bwd_march: it runs on a side stream
+        // beside them and is joined before the gradients leave this call (T2N_BWD_SERIAL=1: one stream).
+        if (side && (rc = fork_stream(s, sd, f->ev_fork))) return rc;
+        if ((rc = launch_den_scan(call, side ? sd : s)) || (rc = launch_den_scatter(call, false, side ? sd : s))) return rc;
+        if (side) T2N_HIP(hipEventRecord((hipEvent_t)f->ev_join, sd));
+    }
+    // the density gradients of this call are final behind this point of their stream (t2n_field_wait_density_grads)
+    T2N_HIP(hipEventRecord((hipEvent_t)f->ev_den, side ? sd : s));
+    timing_end(f, T2N_K_BWD_MARCH, s);
 
     if (rows > 0) {
         const t2n_field_params* P = &f->params_ref;
@@ -1727,20 +1673,9 @@ extern "C" int t2n_render_backward(t2n_field* f, const float* rays, int64_t n_ra
             // -> the MLP gradients, through `part`) and the appearance scatter (GX -> the factor gradient buffers). The GEMMs wait on
             // memory latency and workgroup barriers, the scatter on LDS atomics: they run side by side, the GEMMs on a third stream
             // that is joined before the gradients leave this call (T2N_BWD_SERIAL=1: one stream).
-            hipStream_t sg = s;
-            if (side) {
-                if (!f->gemm_stream || !f->ev_fork2) {
-                    hipEvent_t e0, e1;
-                    { const int rcs = shared_side_streams(&f->side_stream, &f->gemm_stream); if (rcs) return rcs; }
-                    T2N_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-                    T2N_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-                    f->ev_fork2 = (void*)e0; f->ev_join2 = (void*)e1;
-                }
-                sg = (hipStream_t)f->gemm_stream;
-                T2N_HIP(hipEventRecord((hipEvent_t)f->ev_fork2, s));
-                T2N_HIP(hipStreamWaitEvent(sg, (hipEvent_t)f->ev_fork2, 0));
-                side_gemm = true;
-            }
+            side_gemm = side;
+            if (side_gemm) { if ((rc = fork_stream(s, sg, f->ev_fork2))) return rc; }
+            else sg = s;
             if (plan && (!g->mlp_w1 || !g->mlp_w0)) { set_error("t2n_render_backward: T2N_FLAG_DEVICE_ROWS needs the weight-gradient tensors of both hidden layers"); return T2N_ERR_INVALID; }
             if (g->mlp_w1) launch_gemm_tn(4, gemm_fp32, g1, 128, h0, 128, rows, 128, 128, g->mlp_w1, 128, part, sg, nullptr, g->mlp_b1, rows_dev);
             else if (g->mlp_b1) launch_colsum((const float*)g1, 128, (long long)rows, 128, g->mlp_b1, sg);
@@ -1776,28 +1711,14 @@ extern "C" int t2n_render_backward(t2n_field* f, const float* rays, int64_t n_ra
         timing_end(f, T2N_K_BWD_MLP, s);
         T2N_HIP(hipGetLastError());
         // 5. appearance scatter
-        AppScatterArgs sa;
-        sa.F = f->dev;
-        for (int k = 0; k < 3; ++k) { sa.gapp.plane[k] = f->gbuf_app_plane[k]; sa.gapp.line[k] = f->gbuf_app_line[k]; }
-        sa.app_pos = app_pos; sa.counters = counters; sa.list_cap = c.list_cap; sa.gxapp = gxapp;
         timing_begin(f, T2N_K_BWD_SCATTER, s);
         if (bin && f->dev.app.C == 48) {
             // tile-binned: count -> scan -> write records -> LDS accumulate, 16 channels per workgroup
-            AppBinArgs ab;
-            ab.S = f->dev.app; ab.geom = bin_geom(f->dev.app); ab.app_pos = app_pos; ab.counters = counters; ab.list_cap = c.list_cap;
-            ab.plan = plan; ab.tp = tp; ab.rows = rows; ab.hist = (unsigned*)(bw + b.a_hist); ab.tile_start = (const unsigned*)(bw + b.a_tile_start); ab.recs = (float4*)(bw + b.a_recs);
-            const unsigned nbk = (unsigned)((rows + 255) / 256);
-            hipLaunchKernelGGL((k_app_bin<0>), dim3(nbk), dim3(256), 0, s, ab);
-            launch_bin_scan(ab.hist, ab.geom.total, kBinCopies, (unsigned*)(bw + b.a_bin_total), (unsigned*)(bw + b.a_tile_start), (int4*)(bw + b.a_segs), (unsigned*)(bw + b.a_nseg),
-                            b.a_seg_cap, 0u, kAccTargetSegsApp, (unsigned)T2N_ACC_SEG_MIN, s);
-            hipLaunchKernelGGL((k_app_bin<1>), dim3(nbk), dim3(256), 0, s, ab);
-            TileAccumArgs ta;
-            ta.S = f->dev.app; ta.G = sa.gapp; ta.geom = ab.geom; ta.segs = (const int4*)(bw + b.a_segs);
-            ta.nseg = (const unsigned*)(bw + b.a_nseg); ta.recs = (const float4*)(bw + b.a_recs);
-            ta.gx = gxapp; ta.gx_ld = 144;
-            T2N_HIP(hipFuncSetAttribute((const void*)k_bwd_tile_accum<48>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bin));
-            hipLaunchKernelGGL((k_bwd_tile_accum<48>), dim3(b.a_seg_cap < kAccGrid ? b.a_seg_cap : kAccGrid, 3), dim3(kAccThreads), lds_bin, s, ta);
+            if ((rc = launch_app_count(call, false, s)) || (rc = launch_app_records(call, false, s)) || (rc = launch_app_accum(call, gxapp, false, s))) return rc;
         } else {
+            AppScatterArgs sa;
+            sa.F = f->dev; sa.gapp = grad_set(f, true);
+            sa.app_pos = app_pos; sa.counters = counters; sa.list_cap = c.list_cap; sa.gxapp = gxapp;
             unsigned blocks = (unsigned)((rows / 32 + 3) / 4);
             if (blocks > 2048) blocks = 2048;
             if (blocks == 0) blocks = 1;
@@ -1889,624 +1810,5 @@ extern "C" int t2n_field_factor_buffer(const t2n_field* f, int t, void** ptr) {
     if (!f->uploaded || f->factor_bf16) { set_error("t2n_field_factor_buffer: needs an uploaded field with fp32 factor storage"); return T2N_ERR_STATE; }
     float* const* tab[4] = {f->buf_den_plane, f->buf_den_line, f->buf_app_plane, f->buf_app_line};
     *ptr = (void*)tab[t / 3][t % 3];
-    return T2N_OK;
-}
-
-// =====================================================================================================================================
-// t2n_train_step: one optimisation step of text2nerf_main.py:547-601 as ONE submission (include/t2n.h). The kernels are those of
-// t2n_render_forward (KEEP_CTX, train), t2n_train_loss, t2n_render_backward (T2N_FLAG_DEVICE_ROWS) and the optimiser entry points; what is
-// new is the ORDER: every launch that does not lie on the step's dependency chain runs on a side stream beside it, and nothing about a
-// step is decided on the host.
-//   s  (caller)  setup -> march -> shade (kept rows) -> composite -> loss -> bwd_march -> mlp_bwd_ss -> tile_accum -> Adam (factors)
-//   sa (side)    TV seed of the gradient buffer (beside the march) ........ density binning + scatter (behind bwd_march)
-//   sb (bin)     plan (rows, tile prefix, verdict, Adam scalars, host record) -> appearance binning (needs the forward's lists only)
-//   sg (gemm)    layer-2 gradients (behind bwd_march) -> weight-gradient GEMMs (behind mlp_bwd_ss) -> Adam (head) -> operand re-packs
-// =====================================================================================================================================
-#ifndef T2N_ACC_CG8
-#define T2N_ACC_CG8 1
-#endif
-#ifndef T2N_SEED_AFTER_MARCH
-#define T2N_SEED_AFTER_MARCH 1
-#endif
-namespace t2n {
-
-// zero fills of one step as ONE launch: region r = blockIdx.y (a uniform index into the kernel arguments)
-constexpr int kZeroRegions = 12;
-// T2N_FLAG_GATHER_BATCH: the batch rows of a device-resident training set, by index (one more grid row of the zero-fill launch)
-struct GatherOps { const float* rays; const float* rgb; const float* depth; const int* ids; float* d_rays; float* d_rgb; float* d_depth;
-    long long n_rows; unsigned n; int stride; int vec; };
-struct ZeroOps { unsigned* ptr[kZeroRegions]; unsigned long long words[kZeroRegions]; int n = 0;
-    const uint4* up_src = nullptr; uint4* up_dst = nullptr; unsigned long long up_n16 = 0;   // optional upload: 16-byte words from pinned host memory (grid row n)
-    int g_row = -1; GatherOps g = {};   // optional gather (grid row g_row, behind the zero fills and the upload row)
-    bool add(void* p, size_t bytes) { if (!p || !bytes) return true; if (n >= kZeroRegions) return false; ptr[n] = (unsigned*)p; words[n] = (bytes + 3) / 4; ++n; return true; } };
-__global__ __launch_bounds__(256) void k_zero_regions(const ZeroOps o) {
-    const int r = blockIdx.y;
-    if (r == o.n && o.up_src) {   // the batch: read over the host link by the kernel itself (same steady-state time as an engine copy in front of the launch, which stalled the stream for ~5 ms once per process)
-        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < o.up_n16; i += (unsigned long long)gridDim.x * 256)
-            o.up_dst[i] = o.up_src[i];
-        return;
-    }
-    if (r == o.g_row) {   // one thread per batch row: rays[id] (24 B, three 8-byte loads when source and destination allow), rgbs[id], depths[id]
-        const GatherOps& g = o.g;
-        for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < g.n; i += gridDim.x * 256u) {
-            long long id = g.ids[i];
-            id = id < 0 ? 0 : (id >= g.n_rows ? g.n_rows - 1 : id);     // (memory safety does not depend on the caller)
-            const float* __restrict__ sr = g.rays + id * g.stride;
-            float* __restrict__ dr = g.d_rays + (size_t)i * 6;
-            if (g.vec) {
-                const float2 a = reinterpret_cast<const float2*>(sr)[0], b = reinterpret_cast<const float2*>(sr)[1], c = reinterpret_cast<const float2*>(sr)[2];
-                reinterpret_cast<float2*>(dr)[0] = a; reinterpret_cast<float2*>(dr)[1] = b; reinterpret_cast<float2*>(dr)[2] = c;
-            } else {
-                const float a0 = sr[0], a1 = sr[1], a2 = sr[2], a3 = sr[3], a4 = sr[4], a5 = sr[5];
-                dr[0] = a0; dr[1] = a1; dr[2] = a2; dr[3] = a3; dr[4] = a4; dr[5] = a5;
-            }
-            const float* __restrict__ sc = g.rgb + id * 3;
-            const float c0 = sc[0], c1 = sc[1], c2 = sc[2];
-            float* __restrict__ dc = g.d_rgb + (size_t)i * 3;
-            dc[0] = c0; dc[1] = c1; dc[2] = c2;
-            g.d_depth[i] = g.depth[id];
-        }
-        return;
-    }
-    unsigned* __restrict__ p = o.ptr[r];
-    const unsigned long long n = o.words[r];
-    if ((((uintptr_t)p) & 15u) == 0) {
-        uint4* __restrict__ p4 = reinterpret_cast<uint4*>(p);
-        const unsigned long long n4 = n / 4;
-        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (unsigned long long)gridDim.x * 256) p4[i] = make_uint4(0u, 0u, 0u, 0u);
-        for (unsigned long long i = n4 * 4 + (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) p[i] = 0u;
-    } else {
-        for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) p[i] = 0u;
-    }
-}
-
-// The plan of a fused step (one wave, right behind the forward's march): k_bwd_plan's tile prefix / row count / overflow from the
-// sub-list counters, and with them the step's VERDICT — a step whose rows exceed the capacity applies no update — Adam's step count and
-// this step's bias-corrected scalars (torch.optim.Adam: step_size = lr / (1 - beta1^t), denom = sqrt(v) / sqrt(1 - beta2^t) + eps, in
-// double like the host entry points), the vote word behind the head gradients and the record in pinned host memory.
-__global__ __launch_bounds__(64) void k_train_plan(const unsigned* __restrict__ counters, unsigned list_cap, unsigned rows_cap, BwdPlan* __restrict__ plan,
-                                                   TrainState* __restrict__ st, const float* __restrict__ hyper, float beta1, float beta2, float* vote,
-                                                   unsigned* host_rec, unsigned slot) {
-    TrainScalars* __restrict__ sc = &st->sc[slot];
-    const int lane = threadIdx.x;
-    unsigned cnt = lane < kLists ? counters[lane * kCounterStride] : 0u;
-    if (cnt > list_cap) cnt = list_cap;
-    unsigned incl = (cnt + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    const unsigned excl = incl - (cnt + 31u) / 32u;
-    if (lane < kLists) plan->tp.t[lane] = excl;
-    const unsigned total = __shfl(incl, kLists - 1);
-    const unsigned rows = total * 32u;
-    const unsigned ovf = rows > rows_cap ? 1u : 0u;
-    const unsigned step = st->step + (ovf ? 0u : 1u);     // (every lane reads the old value; lane 0 writes below)
-    if (lane < 19 && !ovf) {
-        const double bc1 = 1.0 - pow((double)beta1, (double)step);
-        sc->lr_over_bc1[lane] = (float)((double)hyper[lane] / bc1);
-        if (lane == 0) sc->inv_bc2_sqrt = (float)(1.0 / sqrt(1.0 - pow((double)beta2, (double)step)));
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {
-        plan->tp.t[kLists] = total;
-        plan->overflow = ovf;
-        plan->rows = rows < rows_cap ? rows : rows_cap;
-        const unsigned seq = st->seq;
-        st->seq = seq + 1u;
-        sc->skip = ovf;
-        st->step = step;
-        if (ovf) st->skipped = st->skipped + 1u;
-        if (vote) *vote = ovf ? 1.f : 0.f;
-        if (host_rec) {
-            // ONE 8-byte store per record into fine-grained pinned memory: {rows needed, (sequence + 1) << 1 | withheld}. No fence: a
-            // system-scope release writes the L2 back (60 us behind the march's 50 MB of output), and the host needs no ordering between
-            // records — an entry whose sequence number is not the one it waits for has simply not arrived yet
-            volatile unsigned long long* h = reinterpret_cast<volatile unsigned long long*>(host_rec);
-            h[2 + (seq & 15u)] = ((unsigned long long)(((seq + 1u) << 1) | ovf) << 32) | rows;
-            host_rec[1] = step; host_rec[2] = st->skipped;
-        }
-    }
-}
-// Data-parallel steps (phases 1 | all-reduce | 2): the vote word came back from the all-reduce of the head gradients. A rank whose own
-// rows fitted but whose peers' did not withholds its update too: the optimistic count of k_train_plan is taken back.
-__global__ __launch_bounds__(64) void k_train_commit(TrainState* __restrict__ st, const float* __restrict__ vote, unsigned* host_rec, unsigned slot) {
-    if (threadIdx.x != 0) return;
-    if (*vote != 0.f && !st->sc[slot].skip) {
-        st->sc[slot].skip = 1u; st->step = st->step - 1u; st->skipped = st->skipped + 1u;
-        if (host_rec) {
-            volatile unsigned long long* h = reinterpret_cast<volatile unsigned long long*>(host_rec);
-            const unsigned seq = st->seq - 1u;
-            h[2 + (seq & 15u)] = h[2 + (seq & 15u)] | (1ull << 32);
-            host_rec[1] = st->step; host_rec[2] = st->skipped;
-        }
-    }
-}
-__global__ __launch_bounds__(64) void k_train_set_step(TrainState* st, unsigned step, unsigned* host_rec) {
-    if (threadIdx.x == 0) { st->step = step; if (host_rec) ((volatile unsigned*)host_rec)[1] = step; }
-}
-
-struct TrainCarve { size_t fwd, fwd_bytes, bwd, bwd_bytes, g1, rgb, depth, part, total; };
-static TrainCarve train_carve(const t2n_field* f, int64_t R, int N, int64_t rows) {
-    TrainCarve t;
-    const BinGeom geom = bin_geom(f->dev.den);
-    const BlockGeom bg = block_geom(f->dev.den);
-    size_t o = 0;
-    const Carve c = carve_workspace(R, N, true, false);
-    t.fwd = o; t.fwd_bytes = al256(c.total) + (size_t)rows * (144 + 32 + 128 + 128) * 4; o = al256(o + t.fwd_bytes);
-    t.bwd = o; t.bwd_bytes = bwd_carve(rows, R, N, geom.total, bg.total * bg.copies, 351, true).total; o = al256(o + t.bwd_bytes);
-    t.g1 = o; o = al256(o + (size_t)rows * 128 * 4);
-    t.rgb = o; o = al256(o + (size_t)R * 12);
-    t.depth = o; o = al256(o + (size_t)R * 4);
-    t.part = o; o = al256(o + (size_t)((R + 3) / 4) * 12);
-    t.total = o;
-    return t;
-}
-static size_t train_dev_bytes() { return 256 + al256(mlp_bwd_ss_pack_bytes()); }
-static bool train_supported(const t2n_field* f) {
-    return f->desc.shading == T2N_SHADE_MLP_FEA_NOVIEW && f->desc.app_dim == 27 && f->dev.app.C == 48 && f->dev.den.C == 16 && f->mlp_split &&
-           !f->factor_bf16 && !f->dev.alpha && block_geom_ok(f->dev.den);
-}
-static int train_ensure(t2n_field* f, hipStream_t s) {
-    if (!f->train_dev) {
-        T2N_HIP(hipMalloc(&f->train_dev, train_dev_bytes()));
-        T2N_HIP(hipMemsetAsync(f->train_dev, 0, 256, s));
-        T2N_HIP(hipHostMalloc((void**)&f->train_host, 64 * sizeof(unsigned), hipHostMallocDefault));
-        for (int i = 0; i < 64; ++i) f->train_host[i] = 0u;
-        f->train_packed = false;
-    }
-    int rc;
-    if ((rc = shared_side_streams(&f->side_stream, &f->gemm_stream))) return rc;
-    for (auto& e : f->train_ev) if (!e) { hipEvent_t x; T2N_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming)); e = (void*)x; }
-    if (!f->ev_den) { hipEvent_t e; T2N_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); f->ev_den = (void*)e; }
-    return T2N_OK;
-}
-// the backward chain's transposed split-f16 operands + the forward's packed head operands from the CURRENT head weights
-// (the forward pack reads every weight anyway: it leaves the four matrices' largest magnitudes in the chain pack's absmax words — zeroed
-// by the head Adam launch in front of it — so the chain pack is one short launch; a pack kernel that scanned the matrices itself took
-// 60-105 us at the end of the step's longest chain)
-static int train_repack(t2n_field* f, const t2n_field_params* p, hipStream_t s) {
-    int rc;
-    void* gpack = (char*)f->train_dev + 256;
-    if ((rc = launch_pack_mlp(f, p, s, (unsigned*)mlp_bwd_ss_absmax_words(gpack)))) return rc;
-    if ((rc = mlp_bwd_ss_pack(f, gpack, s, true, false, true))) return rc;
-    f->train_packed = true;
-    return T2N_OK;
-}
-
-}  // namespace t2n
-
-extern "C" size_t t2n_train_step_workspace_bytes(const t2n_field* f, int64_t n_rays, int n_samples, int64_t rows_capacity) {
-    if (!f || n_rays <= 0 || n_samples <= 0 || rows_capacity < 32) return 0;
-    return train_carve(f, n_rays, n_samples, rows_capacity / 32 * 32).total;
-}
-
-extern "C" int t2n_field_train_set_step(t2n_field* f, uint32_t step, t2n_stream stream) {
-    if (!f) { set_error("t2n_field_train_set_step: NULL field"); return T2N_ERR_INVALID; }
-    int rc;
-    if ((rc = train_ensure(f, (hipStream_t)stream))) return rc;
-    hipLaunchKernelGGL(k_train_set_step, dim3(1), dim3(64), 0, (hipStream_t)stream, (TrainState*)f->train_dev, (unsigned)step, f->train_host);
-    T2N_HIP(hipGetLastError());
-    return T2N_OK;
-}
-
-extern "C" int t2n_field_set_train_source(t2n_field* f, const t2n_train_source* src) {
-    if (!f) { set_error("t2n_field_set_train_source: NULL field"); return T2N_ERR_INVALID; }
-    if (!src) { f->train_src = t2n_train_source{}; f->train_src_set = false; f->train_src_fresh = false; return T2N_OK; }
-    if (src->n_rows < 1 || src->ray_stride < 6 || !src->rays || !src->rgb || !src->depth || !src->ids) {
-        set_error("t2n_field_set_train_source: n_rows %lld (>= 1), ray_stride %d (>= 6) or a NULL pointer", (long long)src->n_rows, src->ray_stride);
-        return T2N_ERR_INVALID;
-    }
-    const t2n_train_source& o = f->train_src;
-    if (!f->train_src_set || o.rays != src->rays || o.rgb != src->rgb || o.depth != src->depth || o.n_rows != src->n_rows || o.ray_stride != src->ray_stride)
-        f->train_src_fresh = true;
-    f->train_src = *src; f->train_src_set = true;
-    return T2N_OK;
-}
-
-extern "C" int t2n_field_train_record(const t2n_field* f, uint32_t out[36]) {
-    if (!f || !out) { set_error("t2n_field_train_record: NULL argument"); return T2N_ERR_INVALID; }
-    if (!f->train_host) { for (int i = 0; i < 36; ++i) out[i] = 0u; return T2N_OK; }
-    // pinned layout: words 1, 2 = steps applied / withheld (informational: written without ordering), then 16 eight-byte records
-    // {rows needed, (sequence + 1) << 1 | withheld} at sequence & 15. out[0] = number of consecutive records present from the field's
-    // first step on, i.e. records of sequence numbers < out[0] have all landed (the host keeps its own count of what it consumed).
-    const volatile unsigned long long* h = reinterpret_cast<const volatile unsigned long long*>(f->train_host);
-    out[1] = f->train_host[1]; out[2] = f->train_host[2]; out[3] = 0u;
-    unsigned newest = 0u;
-    for (int k = 0; k < 16; ++k) {
-        const unsigned long long e = h[2 + k];
-        const unsigned tag = (unsigned)(e >> 32);
-        out[4 + 2 * k] = (unsigned)e;           // rows needed
-        out[5 + 2 * k] = tag;                   // (sequence + 1) << 1 | withheld; 0 = never written
-        if ((tag >> 1) > newest) newest = tag >> 1;
-    }
-    out[0] = newest;   // newest sequence number + 1 seen in the ring (records arrive in order: one plan kernel after the other)
-    return T2N_OK;
-}
-
-extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_stream stream) {
-    if (!f || !A || !A->rays || !A->jitter || !A->rgb_target || !A->depth_target || !A->hyper || !A->head_grads || !A->workspace || !A->losses ||
-        A->n_rays <= 0 || A->ray_stride < 6 || A->n_samples <= 0 || !(A->phases & 7u) || ((A->phases & 4u) && A->phases != 4u)) {
-        set_error("t2n_train_step: bad argument");
-        return T2N_ERR_INVALID;
-    }
-    const int sworld = A->shard_world > 1 ? A->shard_world : 1, srank = A->shard_world > 1 ? A->shard_rank : 0;
-    if (srank < 0 || srank >= sworld || (sworld > 1 && (A->phases & 3u) == 3u)) {
-        set_error("t2n_train_step: shard_rank %d of %d, or a sharded step as one call (the gradient exchange lies between phases 1 and 2)", A->shard_rank, A->shard_world);
-        return T2N_ERR_INVALID;
-    }
-    if (A->phases == 4u) {   // sharded optimiser: the gathered body blocks of the other ranks -> the caller's reference-layout tensors
-        if (!f->uploaded || !train_supported(f)) { set_error("t2n_train_step: phases = 4 needs an uploaded field of the fused step's shape"); return T2N_ERR_STATE; }
-        if (sworld < 2) return T2N_OK;
-        return launch_factor_adam_dev(f, &A->params, nullptr, nullptr, 0.f, 0.f, 0.f, nullptr, 0, 12, (hipStream_t)stream, sworld, srank, true);
-    }
-    if (!f->uploaded) { set_error("t2n_train_step: field has no uploaded parameters"); return T2N_ERR_STATE; }
-    if (!train_supported(f)) {
-        set_error("t2n_train_step: needs the fused MLP_Fea_noview head (27 / 6 / 128) in split-f16 mode, 16 + 48 components, fp32 factor storage, no alpha mask");
-        return T2N_ERR_UNSUPPORTED;
-    }
-    const int64_t R = A->n_rays;
-    const int N = A->n_samples;
-    const int64_t rows = A->rows_capacity / 32 * 32;
-    if (N > 1024 || rows < 32 || (uint64_t)R * N * 3 >= 0x7fffffffull || (uint64_t)list_capacity(R, N) * kLists > 0x7fffffffull) {
-        set_error("t2n_train_step: n_samples %d (<= 1024), rows_capacity %lld (>= 32) or n_rays x n_samples out of range", N, (long long)A->rows_capacity);
-        return T2N_ERR_UNSUPPORTED;
-    }
-    int Lmax = 0;
-    for (int k = 0; k < 3; ++k) Lmax = f->dev.den.L[k] > Lmax ? f->dev.den.L[k] : Lmax;
-    const size_t lds_acc = tile_accum_lds(16, Lmax);
-    if (lds_acc > 160 * 1024) { set_error("t2n_train_step: grid lines beyond the LDS budget of the binned scatter"); return T2N_ERR_UNSUPPORTED; }
-    const TrainCarve T = train_carve(f, R, N, rows);
-    if (T.total > A->workspace_bytes) { set_error("t2n_train_step: workspace %zu B < %zu B", A->workspace_bytes, T.total); return T2N_ERR_WORKSPACE; }
-    if (!f->gbuf_all) { set_error("t2n_train_step: the field has no gradient buffer (t2n_field_set_grad_buffer)"); return T2N_ERR_STATE; }
-    // T2N_FLAG_GATHER_BATCH: refused before anything is enqueued
-    const bool gather = (A->flags & T2N_FLAG_GATHER_BATCH) && (A->phases & 1u);
-    if (gather) {
-        if (!f->train_src_set) { set_error("t2n_train_step: T2N_FLAG_GATHER_BATCH without a training source (t2n_field_set_train_source)"); return T2N_ERR_STATE; }
-        const t2n_train_source& S = f->train_src;
-        if (S.n_rows < 1 || S.ray_stride < 6 || !S.rays || !S.rgb || !S.depth || !S.ids) { set_error("t2n_train_step: training source with n_rows %lld, ray_stride %d or a NULL pointer", (long long)S.n_rows, S.ray_stride); return T2N_ERR_INVALID; }
-        if (A->ray_stride != 6) { set_error("t2n_train_step: T2N_FLAG_GATHER_BATCH fills a batch of ray_stride 6 (got %d)", A->ray_stride); return T2N_ERR_INVALID; }
-    }
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = train_ensure(f, s))) return rc;
-    // three streams beside the caller's (one per hardware queue): sa = early part + TV seed + density scatter / Adam, sg = layer 2 +
-    // weight-gradient GEMMs + head step. (With separate streams for the plan / binning, the early part and the caller's batch copy, seven
-    // streams shared four queues: whichever chain landed behind the GEMM chain's queue waited for it — 0.86 or 0.99 ms per step depending
-    // on the order the streams had been created in.)
-    hipStream_t sa = (hipStream_t)f->side_stream, sg = (hipStream_t)f->gemm_stream, sb = sa;
-    hipEvent_t* ev = (hipEvent_t*)f->train_ev;   // 0 begin, 1 seed, 2 march, 3 plan, 4 appbin, 5 bwd_march, 6 chain, 7 gemm-stream join, 8 loss
-    TrainState* st = (TrainState*)f->train_dev;
-    void* gpack = (char*)f->train_dev + 256;
-    float* vote = A->head_grads + (T2N_TRAIN_HEAD_GRAD_FLOATS - 1);
-    const bool do_grad = (A->phases & 1u) != 0, do_opt = (A->phases & 2u) != 0;
-    // pipelined form: the early part of this step on `se`, beside the previous step's tail (see include/t2n.h)
-    // density bins counted from the forward's windows, beside the shade kernel, instead of behind the backward march (as t2n_render_backward
-    // does): takes ~110 us of small kernels off the chain backward march -> density scatter -> density Adam -> next march, at the price of
-    // records for zero-gradient samples and a second evaluation of the sample positions. Small batches are bound by that chain (2 048 rays:
-    // 0.404 -> 0.392 ms; 8 192 rays: 0.575 -> 0.564), large ones by the machine's throughput (16 384 rays: 0.851 -> 0.857, later 0.829 / 0.845 ->
-    // 0.838 / 0.826: nothing either way): taken up to 4 096 rays (the configuration every record of the round ran)
-    // (T2N_DEN_EARLY=0 / 1 forces it; profiles/round6_train_ab.txt)
-    static const int den_env = getenv("T2N_DEN_EARLY") ? atoi(getenv("T2N_DEN_EARLY")) : -1;
-    bool den_early = den_env >= 0 ? den_env != 0 : A->n_rays <= 4096;
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap_status);
-    if (cap_status != hipStreamCaptureStatusNone) den_early = false;   // (the captured step keeps the one DAG its replay was tested with: the early form's extra fork crashed hipStreamEndCapture on ROCm 7.2)
-    const bool pipe = (A->flags & T2N_FLAG_PIPELINE) && A->host_batch && do_grad && do_opt && A->workspace_bytes >= 2 * T.total && cap_status == hipStreamCaptureStatusNone;
-    const bool chain_prev = f->train_chain;               // the previous call was a full step of this form and left its density-Adam event
-    f->train_chain = false;
-    const unsigned par = f->train_calls & 1u;            // scalar slot (always alternates) and, pipelined, workspace half
-    if (do_grad) f->train_calls++;
-    const unsigned slot = do_grad ? par : ((f->train_calls - 1u) & 1u);   // an optimiser-only call takes the slot its gradient call wrote
-    TrainScalars* sc = &st->sc[slot];
-    hipStream_t se = pipe ? sa : s;     // (on sa the early part is ordered behind the previous step's density Adam by the stream itself)
-    // the caller's tensors are the parameters from here on (the optimiser writes them; the packs read them)
-    const t2n_field_params* P = &A->params;
-    if (do_opt && (!P->basis_weight || !P->mlp_w0 || !P->mlp_b0 || !P->mlp_w1 || !P->mlp_b1 || !P->mlp_w2 || !P->mlp_b2)) { set_error("t2n_train_step: NULL head tensor"); return T2N_ERR_INVALID; }
-
-    char* ws = (char*)A->workspace + (pipe ? (size_t)par * T.total : 0);
-    char* fw = ws + T.fwd;
-    char* bw = ws + T.bwd;
-    const Carve c = carve_workspace(R, N, true, false);
-    const KeptRows kr = kept_rows(c.total, T.fwd_bytes);
-    if ((int64_t)kr.rows < rows) { set_error("t2n_train_step: internal carve mismatch (%u kept rows < %lld)", kr.rows, (long long)rows); return T2N_ERR_WORKSPACE; }
-    const BinGeom ageom = bin_geom(f->dev.app);
-    const BinGeom dgeom_t = bin_geom(f->dev.den);
-    const BlockGeom bgeom = block_geom(f->dev.den);
-    const BwdCarve b = bwd_carve(rows, R, N, dgeom_t.total, bgeom.total * bgeom.copies, 351, true);
-    float* rgb = (float*)(ws + T.rgb); float* depth = (float*)(ws + T.depth);
-    const uint32_t flags = (A->flags & T2N_FLAG_ADD_BG) | T2N_FLAG_TRAIN | T2N_FLAG_KEEP_CTX;
-
-    if (do_grad) {
-        if (!f->train_packed) {   // first step / after an upload: the operands an optimiser phase leaves packed behind every later step
-            if ((rc = mlp_bwd_ss_pack(f, gpack, s, false, true))) return rc;
-            f->train_packed = true;
-        }
-        T2N_HIP(hipEventRecord(ev[0], s));
-        // (the previous call left no density-Adam event on sa: behind `stream`; so is the first gather from a training source that changed —
-        // its rows were written on the caller's stream)
-        if (pipe && (!chain_prev || (gather && f->train_src_fresh))) T2N_HIP(hipStreamWaitEvent(se, ev[0], 0));
-        if (gather) f->train_src_fresh = false;
-        const uint4* up_src = nullptr;
-        if (A->host_batch) {
-            if (!A->batch_buffer || !A->host_batch_bytes) { set_error("t2n_train_step: host_batch without batch_buffer / host_batch_bytes"); return T2N_ERR_INVALID; }
-            // The batch goes through the copy engine. T2N_COPY_KERNEL=1: a pinned, 16-byte-aligned batch is read by the zero-fill launch itself
-            // (no engine packet on the compute stream: its once-per-process ~5 ms stall goes away, the steady state is the same) — NOT the
-            // default: in the pipelined form, as the first fused work of a fresh process, that kernel died of a GPU memory fault in 7 of 56
-            // runs (0 of 44 with the engine copy, 0 of 16 unpipelined; tools/r6_fault_loop.sh, profiles/round6_train_ab.txt); unexplained
-            static const bool engine_copy = !(getenv("T2N_COPY_KERNEL") && atoi(getenv("T2N_COPY_KERNEL")) != 0);
-            void* dp = nullptr;
-            // (a gathering step always takes the engine copy: the gather row of the zero-fill launch reads the ids this copy writes, and
-            // rows of one launch are not ordered against each other)
-            if (!engine_copy && !gather && ((uintptr_t)A->host_batch & 15u) == 0 && ((uintptr_t)A->batch_buffer & 15u) == 0 && (A->host_batch_bytes & 15u) == 0 &&
-                hipHostGetDevicePointer(&dp, const_cast<void*>((const void*)A->host_batch), 0) == hipSuccess && dp) up_src = (const uint4*)dp;
-            else { (void)hipGetLastError(); T2N_HIP(hipMemcpyAsync(A->batch_buffer, A->host_batch, A->host_batch_bytes, hipMemcpyHostToDevice, se)); }
-        }
-        // ---- every zero fill of the step in one launch
-        RenderLaunch L;
-        L.rays = A->rays; L.n_rays = R; L.ray_stride = A->ray_stride; L.n_samples = N; L.flags = flags; L.jitter = A->jitter;
-        L.rgb = rgb; L.depth = depth; L.weights = nullptr; L.z_vals = nullptr; L.stats = nullptr;   // (weights / sample depths: recomputed where they are needed)
-        L.counters = (unsigned*)(fw + c.counters); L.acc = (float*)(fw + c.acc); L.ray_app = (int4*)(fw + c.ray_app);
-        L.app_pos = (float4*)(fw + c.app_pos); L.app_rgb = (float4*)(fw + c.app_rgb); L.app_ray = (int*)(fw + c.app_ray);
-        L.list_cap = c.list_cap; L.feat = nullptr; L.feat_rows = 0;
-        L.sigma_ctx = (float*)(fw + c.sigma); L.rgb_raw = (float4*)(fw + c.rgb_raw);
-        float4* go = (float4*)(bw + b.go);
-        {
-            ZeroOps zo;
-            bool ok = zo.add(L.counters, (size_t)kLists * kCounterStride * 4);
-            ok = ok && zo.add(go, (size_t)rows * 16);
-            ok = ok && zo.add(bw + b.hist, (size_t)bgeom.total * bgeom.copies * 4);
-            ok = ok && zo.add(bw + b.a_hist, (size_t)ageom.total * kBinCopies * 4);
-            // (head_grads: left zeroed by the previous optimiser phase — its Adam kernel clears what it consumed; a pipelined early part
-            // must not clear a buffer the previous step's head Adam has yet to read)
-            if (!ok) { set_error("t2n_train_step: zero-fill table overflow"); return T2N_ERR_INVALID; }
-            unsigned long long mx = 1;
-            for (int r = 0; r < zo.n; ++r) mx = zo.words[r] > mx ? zo.words[r] : mx;
-            if (up_src) { zo.up_src = up_src; zo.up_dst = (uint4*)A->batch_buffer; zo.up_n16 = A->host_batch_bytes / 16; mx = zo.up_n16 * 16 > mx ? zo.up_n16 * 16 : mx; }   // (one 16-byte word per thread up to 256 workgroups)
-            if (gather) {   // behind the copy of ids | jitter | hyper on the same stream; device memory only
-                const t2n_train_source& S = f->train_src;
-                zo.g_row = zo.n + (up_src ? 1 : 0);
-                zo.g = GatherOps{S.rays, S.rgb, S.depth, (const int*)S.ids, const_cast<float*>(A->rays), const_cast<float*>(A->rgb_target), const_cast<float*>(A->depth_target),
-                                 (long long)S.n_rows, (unsigned)R, (int)S.ray_stride,
-                                 (((uintptr_t)S.rays | (uintptr_t)A->rays) & 7u) == 0 && (S.ray_stride & 1) == 0 ? 1 : 0};
-                mx = (unsigned long long)R * 16 > mx ? (unsigned long long)R * 16 : mx;   // (one thread per batch row up to 256 workgroups)
-            }
-            unsigned bx = (unsigned)((mx + 4095) / 4096);
-            bx = bx > 256 ? 256 : (bx < 1 ? 1 : bx);
-            hipLaunchKernelGGL(k_zero_regions, dim3(bx, (unsigned)zo.n + (up_src ? 1u : 0u) + (gather ? 1u : 0u)), dim3(256), 0, se, zo);
-        }
-        // ---- forward: march
-        if ((rc = launch_march(f, L, se))) return rc;
-        T2N_HIP(hipEventRecord(ev[2], se));
-        if (pipe) T2N_HIP(hipStreamWaitEvent(s, ev[2], 0));
-        // ---- forward: shade with the activation rows kept, composite; the driver's loss
-        {
-            ShadeCtx ctx{(float*)(fw + kr.x144), (float*)(fw + kr.feat32), (float*)(fw + kr.h0), (float*)(fw + kr.h1)};
-            if ((rc = launch_shade_list(f, L.app_pos, L.app_ray, L.rays, A->ray_stride, L.counters, L.list_cap, L.app_rgb, &ctx, s, false, kr.rows))) return rc;
-        }
-        if ((rc = launch_composite(f, L, s))) return rc;
-        // (the driver's loss is evaluated by k_bwd_march<.., LOSS>; its partial sums are added up by the step's one reduce launch)
-        // ---- sb: plan, then the appearance binning (needs the forward's lists and the plan, not a single gradient)
-        T2N_HIP(hipStreamWaitEvent(sb, ev[2], 0));
-        BwdPlan* plan = (BwdPlan*)(bw + b.plan);
-        hipLaunchKernelGGL(k_train_plan, dim3(1), dim3(64), 0, sb, (const unsigned*)L.counters, c.list_cap, (unsigned)rows, plan, st, A->hyper,
-                           A->beta1, A->beta2, vote, f->train_host, slot);
-        T2N_HIP(hipEventRecord(ev[3], sb));
-        GradSet gapp;
-        for (int k = 0; k < 3; ++k) { gapp.plane[k] = f->gbuf_app_plane[k]; gapp.line[k] = f->gbuf_app_line[k]; }
-        float* GX = (float*)(bw + b.xpe) + (size_t)rows * 160;
-        {
-            AppBinArgs ab;
-            ab.S = f->dev.app; ab.geom = ageom; ab.app_pos = L.app_pos; ab.counters = L.counters; ab.list_cap = c.list_cap;
-            ab.plan = plan; memset(&ab.tp, 0, sizeof(ab.tp)); ab.rows = rows; ab.hist = (unsigned*)(bw + b.a_hist); ab.tile_start = (const unsigned*)(bw + b.a_tile_start); ab.recs = (float4*)(bw + b.a_recs);
-            const unsigned nbk = (unsigned)((rows + 255) / 256);
-            if (den_early) {
-                // + the density scatter's block histogram from the forward's windows (positions only, no gradient needed); its reduce + scan
-                // run on sg while the shade kernel runs: behind the backward march only the record pass and the accumulate pass are left
-                // on the density chain (k_bin_reduce + k_bin_scan took ~110 us there under the concurrency of the input-gradient chain)
-                BinArgs ca;
-                ca.F = f->dev; ca.F.ztab = nullptr; ca.geom = bgeom; ca.rays = A->rays; ca.n_rays = R; ca.ray_stride = A->ray_stride; ca.n_samples = N;
-                ca.jitter = A->jitter; ca.gfeat = nullptr; ca.ray_app = (const int4*)(fw + c.ray_app); ca.cursor = (unsigned*)(bw + b.hist); ca.tile_start = nullptr; ca.recs = nullptr;
-                hipLaunchKernelGGL(k_early_bins, dim3(nbk + (unsigned)((R + 3) / 4)), dim3(256), 0, sb, ab, ca, nbk);
-                T2N_HIP(hipEventRecord(ev[10], sb));
-                T2N_HIP(hipStreamWaitEvent(sg, ev[10], 0));
-                launch_bin_scan((unsigned*)(bw + b.hist), bgeom.total, bgeom.copies, (unsigned*)(bw + b.bin_total), (unsigned*)(bw + b.tile_start), (int4*)(bw + b.segs), (unsigned*)(bw + b.nseg), b.seg_cap, kDenSeg,
-                                0u, kDenSeg, sg);
-                T2N_HIP(hipEventRecord(ev[11], sg));
-            } else
-                hipLaunchKernelGGL((k_app_bin<0>), dim3(nbk), dim3(256), 0, sb, ab);
-            launch_bin_scan(ab.hist, ab.geom.total, kBinCopies, (unsigned*)(bw + b.a_bin_total), (unsigned*)(bw + b.a_tile_start), (int4*)(bw + b.a_segs), (unsigned*)(bw + b.a_nseg),
-                            b.a_seg_cap, 0u, kAccTargetSegsApp, (unsigned)T2N_ACC_SEG_MIN, sb, true);
-            hipLaunchKernelGGL((k_app_bin<1>), dim3(nbk), dim3(256), 0, sb, ab);
-            T2N_HIP(hipEventRecord(ev[4], sb));
-        }
-        // ---- sa: the gradient buffer starts as the TV gradient of the current factors (zero where no weight is set): 140 MB of streaming
-        // beside the shade kernel (matrix cores + LDS) rather than beside the march (gathers: the two slow each other by a third)
-        T2N_HIP(hipStreamWaitEvent(sa, ev[0], 0));     // (behind the previous step's Adam: it read this buffer and wrote the factors)
-        if (T2N_SEED_AFTER_MARCH) T2N_HIP(hipStreamWaitEvent(sa, ev[2], 0));
-        timing_begin(f, T2N_K_TV_SEED, sa);
-        if ((rc = launch_tv_seed_dev(f, A->hyper + 19, sa, sworld, srank))) return rc;
-        timing_end(f, T2N_K_TV_SEED, sa);
-        T2N_HIP(hipEventRecord(ev[1], sa));
-        // ---- backward: per-ray pass
-        float* x144 = (float*)(fw + kr.x144); float* feat32 = (float*)(fw + kr.feat32); float* h0 = (float*)(fw + kr.h0); float* h1 = (float*)(fw + kr.h1);
-        float* part = (float*)(bw + b.part);
-        float* xpe = (float*)(bw + b.xpe);
-        float* G0 = xpe; float* GF = xpe + (size_t)rows * 128;
-        float* G1 = (float*)(ws + T.g1);
-        const unsigned* rows_dev = &plan->rows;
-        T2N_HIP(hipStreamWaitEvent(s, ev[3], 0));
-        {
-            BwdMarchArgs a;
-            a.F = f->dev; a.F.ztab = nullptr;
-            for (int k = 0; k < 3; ++k) { a.gden.plane[k] = f->gbuf_den_plane[k]; a.gden.line[k] = f->gbuf_den_line[k]; }
-            a.rays = A->rays; a.n_rays = R; a.ray_stride = A->ray_stride; a.n_samples = N; a.npad = (N + 63) & ~63;
-            a.jitter = A->jitter; a.sigma = (const float*)(fw + c.sigma); a.ray_app = (const int4*)(fw + c.ray_app);
-            a.app_rgb = L.app_rgb; a.rgb_raw = (const float4*)(fw + c.rgb_raw);
-            a.d_rgb = nullptr; a.d_depth = nullptr; a.d_w = nullptr; a.go = go; a.list_cap = c.list_cap; memset(&a.tp, 0, sizeof(a.tp)); a.plan = plan;
-            a.rgb = rgb; a.depth = depth; a.rgb_t = A->rgb_target; a.depth_t = A->depth_target; a.w_depth = A->w_depth; a.w_trans = A->w_trans; a.delta = A->delta;
-            a.loss_part = (float*)(ws + T.part);
-            a.add_bg = (flags & T2N_FLAG_ADD_BG) ? 1 : 0;
-            a.gfeat = (float*)(fw + c.sigma); a.hist = (unsigned*)(bw + b.hist); a.geom = bgeom;
-            const size_t lds = (size_t)4 * 4 * a.npad * sizeof(float);
-            const unsigned nb = (unsigned)((R + 3) / 4);
-            timing_begin(f, T2N_K_BWD_MARCH, s);
-            if (den_early) hipLaunchKernelGGL((k_bwd_march<true, true, true, false>), dim3(nb), dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((k_bwd_march<true, true, true>), dim3(nb), dim3(256), lds, s, a);
-            timing_end(f, T2N_K_BWD_MARCH, s);
-            T2N_HIP(hipEventRecord(ev[5], s));
-        }
-        float* hg = A->head_grads;   // basis | w0 | b0 | w1 | b1 | w2 | b2
-        float* g_basis = hg; float* g_w0 = g_basis + 27 * 144; float* g_b0 = g_w0 + 128 * 351; float* g_w1 = g_b0 + 128; float* g_b1 = g_w1 + 128 * 128;
-        float* g_w2 = g_b1 + 128; float* g_b2 = g_w2 + 3 * 128;
-        // ---- the input-gradient chain
-        timing_begin(f, T2N_K_BWD_MLP, s);
-        if ((rc = launch_mlp_bwd_ss(f, gpack, (const float4*)go, h1, h0, feat32, G0, GF, GX, rows, s, true, rows_dev, G1))) return rc;
-        timing_end(f, T2N_K_BWD_MLP, s);
-        T2N_HIP(hipEventRecord(ev[6], s));
-        {
-            const unsigned nb = (unsigned)((R + 3) / 4);
-            // ---- sa: density scatter (behind the TV seed on the same stream)
-            T2N_HIP(hipStreamWaitEvent(sa, ev[5], 0));
-            timing_begin(f, T2N_K_BWD_DENSITY, sa);
-            if (den_early) T2N_HIP(hipStreamWaitEvent(sa, ev[11], 0));     // counted, reduced and scanned on sg beside the shade kernel
-            else launch_bin_scan((unsigned*)(bw + b.hist), bgeom.total, bgeom.copies, (unsigned*)(bw + b.bin_total), (unsigned*)(bw + b.tile_start), (int4*)(bw + b.segs), (unsigned*)(bw + b.nseg), b.seg_cap, kDenSeg,
-                                 0u, kDenSeg, sa);
-            BinArgs ba;
-            ba.F = f->dev; ba.F.ztab = nullptr; ba.geom = bgeom; ba.rays = A->rays; ba.n_rays = R; ba.ray_stride = A->ray_stride; ba.n_samples = N;
-            ba.jitter = A->jitter; ba.gfeat = (float*)(fw + c.sigma); ba.ray_app = (const int4*)(fw + c.ray_app); ba.cursor = (unsigned*)(bw + b.hist); ba.tile_start = (const unsigned*)(bw + b.tile_start); ba.recs = (float4*)(bw + b.recs);
-            if (den_early) hipLaunchKernelGGL((k_bwd_bin<true, true>), dim3(nb), dim3(256), 0, sa, ba);
-            else hipLaunchKernelGGL((k_bwd_bin<true>), dim3(nb), dim3(256), 0, sa, ba);
-            DenBlockArgs da;
-            da.S = f->dev.den; for (int k = 0; k < 3; ++k) { da.G.plane[k] = f->gbuf_den_plane[k]; da.G.line[k] = f->gbuf_den_line[k]; } da.geom = bgeom; da.segs = (const int4*)(bw + b.segs);
-            da.nseg = (const unsigned*)(bw + b.nseg); da.recs = (const float4*)(bw + b.recs);
-            hipLaunchKernelGGL(k_bwd_den_block, dim3(b.seg_cap < kAccGrid ? b.seg_cap : kAccGrid), dim3(kDenThreads), 0, sa, da);
-            timing_end(f, T2N_K_BWD_DENSITY, sa);
-            T2N_HIP(hipEventRecord((hipEvent_t)f->ev_den, sa));
-        }
-        // ---- sg: layer 2's weight gradient needs go and the kept h1 only (the chain writes g1 elsewhere in this form)
-        T2N_HIP(hipStreamWaitEvent(sg, ev[5], 0));
-        const WgradRegions WR = wgrad_regions(rows, 351);
-        launch_bwd_l2((const float4*)go, (const float*)h1, rows, f->params_ref.mlp_w2, nullptr, nullptr, nullptr, (float*)((char*)part + WR.l2), sg, rows_dev);
-        T2N_HIP(hipStreamWaitEvent(sg, ev[6], 0));
-        timing_begin(f, T2N_K_BWD_WGRAD, sg);
-        launch_gemm_tn(4, false, G1, 128, h0, 128, rows, 128, 128, g_w1, 128, (float*)((char*)part + WR.tn[0]), sg, nullptr, g_b1, rows_dev, false);
-        launch_gemm_tn(4, false, G0, 128, xpe, 352, rows, 128, 351, g_w0, 351, (float*)((char*)part + WR.tn[1]), sg, feat32, g_b0, rows_dev, false);
-        launch_gemm_tn(1, false, GF, 32, x144, 144, rows, 27, 144, g_basis, 144, (float*)((char*)part + WR.tn[2]), sg, nullptr, nullptr, rows_dev, false);
-        launch_wgrad_reduce((const char*)part, rows, g_w2, g_b2, g_w1, g_w0, g_basis, sg, (const float*)(ws + T.part), R, A->w_depth, A->w_trans, A->losses);
-        timing_end(f, T2N_K_BWD_WGRAD, sg);
-        // ---- appearance scatter: records binned on sb, gradient buffer seeded on sa
-        T2N_HIP(hipStreamWaitEvent(s, ev[4], 0));
-        T2N_HIP(hipStreamWaitEvent(s, ev[1], 0));
-        {
-            TileAccumArgs ta;
-            ta.S = f->dev.app; ta.G = gapp; ta.geom = ageom; ta.segs = (const int4*)(bw + b.a_segs);
-            ta.nseg = (const unsigned*)(bw + b.a_nseg); ta.recs = (const float4*)(bw + b.a_recs);
-            ta.gx = GX; ta.gx_ld = 144;
-            static bool attr_set = false;
-            if (!attr_set) {
-                T2N_HIP(hipFuncSetAttribute((const void*)k_bwd_tile_accum<48>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                T2N_HIP(hipFuncSetAttribute((const void*)k_bwd_tile_accum<48, 8, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-                attr_set = true;
-            }
-            const size_t lds8 = tile_accum_lds(8, Lmax, 256);
-            timing_begin(f, T2N_K_BWD_SCATTER, s);
-            if (T2N_ACC_CG8 && lds8 <= 80 * 1024)   // two workgroups per CU: one accumulates while the other stages / zeroes / flushes
-                hipLaunchKernelGGL((k_bwd_tile_accum<48, 8, 256>), dim3(b.a_seg_cap < kAccGrid ? b.a_seg_cap : kAccGrid, 6), dim3(256), lds8, s, ta);
-            else
-                hipLaunchKernelGGL((k_bwd_tile_accum<48>), dim3(b.a_seg_cap < kAccGrid ? b.a_seg_cap : kAccGrid, 3), dim3(kAccThreads), lds_acc, s, ta);
-            timing_end(f, T2N_K_BWD_SCATTER, s);
-        }
-        T2N_HIP(hipGetLastError());
-        if (!do_opt) {   // gradients final on `s`: join both side chains
-            T2N_HIP(hipEventRecord(ev[7], sg));
-            T2N_HIP(hipStreamWaitEvent(s, ev[7], 0));
-            T2N_HIP(hipStreamWaitEvent(s, (hipEvent_t)f->ev_den, 0));
-            return T2N_OK;
-        }
-    } else {
-        // optimiser-only phase (data-parallel): the vote word has been all-reduced with the head gradients
-        hipLaunchKernelGGL(k_train_commit, dim3(1), dim3(64), 0, s, st, (const float*)vote, f->train_host, slot);
-        T2N_HIP(hipEventRecord(ev[6], s));
-        T2N_HIP(hipStreamWaitEvent(sg, ev[6], 0));
-    }
-    // ---- optimiser. sg: Adam on the seven head tensors, then every packed form of the new head weights (the forward's fp32 and
-    // split-f16 operands, the backward chain's transposed ones) beside the factor tensors' Adam on `s`
-    timing_begin(f, T2N_K_HEAD_STEP, sg);
-    if ((rc = launch_head_adam_dev(P, A->head_grads, A->exp_avg + 12, A->exp_avg_sq + 12, A->beta1, A->beta2, A->eps, sc, sg, true, (unsigned*)mlp_bwd_ss_absmax_words(gpack)))) return rc;
-    f->params_ref.basis_weight = P->basis_weight;
-    f->params_ref.mlp_w0 = P->mlp_w0; f->params_ref.mlp_b0 = P->mlp_b0; f->params_ref.mlp_w1 = P->mlp_w1; f->params_ref.mlp_b1 = P->mlp_b1;
-    f->params_ref.mlp_w2 = P->mlp_w2; f->params_ref.mlp_b2 = P->mlp_b2;
-    for (int k = 0; k < 3; ++k) {
-        f->params_ref.density_plane[k] = P->density_plane[k]; f->params_ref.density_line[k] = P->density_line[k];
-        f->params_ref.app_plane[k] = P->app_plane[k]; f->params_ref.app_line[k] = P->app_line[k];
-    }
-    if ((rc = train_repack(f, P, sg))) return rc;
-    f->ss_dirty = true;
-    timing_end(f, T2N_K_HEAD_STEP, sg);
-    T2N_HIP(hipEventRecord(ev[7], sg));
-    if (do_grad) {
-        // the density factors (a quarter of the bytes) step on sa right behind their scatter, beside the appearance scatter on `s`
-        if ((rc = launch_factor_adam_dev(f, P, A->exp_avg, A->exp_avg_sq, A->beta1, A->beta2, A->eps, sc, 0, 6, sa, sworld, srank))) return rc;
-        T2N_HIP(hipEventRecord(ev[9], sa));
-        f->train_chain = true;      // (the next call's early part may start behind this event)
-        timing_begin(f, T2N_K_ADAM, s);
-        if ((rc = launch_factor_adam_dev(f, P, A->exp_avg, A->exp_avg_sq, A->beta1, A->beta2, A->eps, sc, 6, 6, s, sworld, srank))) return rc;
-        timing_end(f, T2N_K_ADAM, s);
-        T2N_HIP(hipStreamWaitEvent(s, ev[9], 0));
-    } else if ((rc = launch_factor_adam_dev(f, P, A->exp_avg, A->exp_avg_sq, A->beta1, A->beta2, A->eps, sc, 0, 12, s, sworld, srank))) return rc;
-    T2N_HIP(hipStreamWaitEvent(s, ev[7], 0));
-    T2N_HIP(hipGetLastError());
-    return T2N_OK;
-}
-
-// ---- the step as a hipGraph: stream capture of the call above (relaxed mode: the library's side streams join the capture through
-// their event waits), instantiated once, replayed per step
-struct t2n_train_graph { hipGraph_t graph; hipGraphExec_t exec; int nodes; t2n_field* f; };
-
-extern "C" int t2n_train_graph_capture(t2n_field* f, const t2n_train_step_args* a, t2n_stream stream, t2n_train_graph** out) {
-    if (!f || !a || !out) { set_error("t2n_train_graph_capture: NULL argument"); return T2N_ERR_INVALID; }
-    if (!f->train_dev || !f->train_packed) { set_error("t2n_train_graph_capture: run t2n_train_step eagerly once first (lazy state cannot be captured)"); return T2N_ERR_STATE; }
-    // captured on a stream of its own: the caller's may be the legacy default stream, which cannot capture (hipErrorStreamCaptureUnsupported);
-    // the instantiated graph is launched on whatever stream the caller passes to t2n_train_graph_launch
-    (void)stream;
-    hipStream_t s = nullptr;
-    T2N_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    const hipError_t e0 = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
-    if (e0 != hipSuccess) { (void)hipStreamDestroy(s); return hip_fail(e0, "hipStreamBeginCapture"); }
-    const int rc = t2n_train_step(f, a, (t2n_stream)s);
-    hipGraph_t g = nullptr;
-    const hipError_t e = hipStreamEndCapture(s, &g);
-    (void)hipStreamDestroy(s);
-    if (rc) { if (g) (void)hipGraphDestroy(g); return rc; }
-    if (e != hipSuccess || !g) return hip_fail(e, "hipStreamEndCapture");
-    hipGraphExec_t ex = nullptr;
-    const hipError_t e2 = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-    if (e2 != hipSuccess) { (void)hipGraphDestroy(g); return hip_fail(e2, "hipGraphInstantiate"); }
-    size_t n = 0;
-    (void)hipGraphGetNodes(g, nullptr, &n);
-    t2n_train_graph* tg = new t2n_train_graph{g, ex, (int)n, f};
-    *out = tg;
-    return T2N_OK;
-}
-extern "C" int t2n_train_graph_launch(t2n_train_graph* g, t2n_stream stream) {
-    if (!g) { set_error("t2n_train_graph_launch: NULL graph"); return T2N_ERR_INVALID; }
-    t2n_field* f = g->f;
-    if (!f->train_packed) {   // the head was uploaded since the last step (load_state_dict, a step of another optimiser): the captured step
-        // expects the backward chain's operands of the CURRENT weights, which an optimiser phase leaves behind and an upload does not
-        const int rc = mlp_bwd_ss_pack(f, (char*)f->train_dev + 256, (hipStream_t)stream, false, true);
-        if (rc) return rc;
-        f->train_packed = true;
-    }
-    T2N_HIP(hipGraphLaunch(g->exec, (hipStream_t)stream));
-    return T2N_OK;
-}
-extern "C" int t2n_train_graph_nodes(const t2n_train_graph* g) { return g ? g->nodes : 0; }
-extern "C" int t2n_train_graph_destroy(t2n_train_graph* g) {
-    if (!g) return T2N_OK;
-    (void)hipGraphExecDestroy(g->exec);
-    (void)hipGraphDestroy(g->graph);
-    delete g;
     return T2N_OK;
 }

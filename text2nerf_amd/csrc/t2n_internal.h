@@ -136,7 +136,7 @@ struct t2n_field {
     void* ev_pack = nullptr;   // backward: k_mlp_bwd_ss's operand packing (on gemm_stream) is done
     void* gemm_stream = nullptr; void* ev_fork2 = nullptr; void* ev_join2 = nullptr;  // backward: the weight-gradient GEMMs run beside the appearance scatter
     // fused training step (t2n_train_step): device state + the backward chain's packed operands (one allocation), the pinned host record,
-    // a third side stream for the plan + appearance binning and the events of the call's fork / join graph
+    // the events of the call's fork / join graph (the side streams are the two above)
     void* train_dev = nullptr; unsigned* train_host = nullptr; void* train_ev[12] = {};
     unsigned train_calls = 0; bool train_chain = false;   // pipelined steps: stream of a step's early part; calls so far (workspace / scalar slot parity); the previous call left its density-Adam event
     bool train_packed = false;   // the backward chain's operands in train_dev are those of the current head weights
