@@ -6,9 +6,12 @@
 //     D_k[t][l] = sum_c P_k[t][c] * L_k[l][c]      (t over the rectangle, l over the segment, c over the 16 components)
 // so the wave computes the small table D_k = P_k L_k^T ONCE per step on the matrix cores (v_mfma_f32_16x16x4_f32, exact
 // f32: one 16-B load per lane supplies the A operand of four k-steps, lane l holding texel l&15, components 4(l>>4)..+3),
-// parks it in LDS (<= 64 x 16 floats per plane) and every lane reads just its 4 x 2 table entries per plane — 96 B per sample
-// instead of the 1152 B of factor data the per-lane interpolation reads. (The staged-factor variant of this kernel was LDS
-// bandwidth-bound: 72 ds_read_b128 per wave step = 576 clk of the CU's 128 B/clk LDS pipe x 12 resident waves.)
+// parks it in LDS (<= 64 x 16 floats per plane), adds the three tables into ONE 4 x 4 x 4 table S[z][y][x] (one entry per lane:
+// the 4 x 2 entries per plane a lane would read are the terms of the 8 corner values of its cell, table_sum) and every lane
+// reads just the 8 corners of its cell from S — 32 B per sample instead of the 1152 B of factor data the per-lane interpolation
+// reads (and of the 96 B and three interpolations of reading the pair tables: 2 x 65 VALU + 2 x 12 LDS reads per step pair
+// became 18 + 2 x 20 VALU and 4 + 2 x 4 LDS; profiles/march_summed_table_ab.txt). (The staged-factor variant of this kernel was
+// LDS bandwidth-bound: 72 ds_read_b128 per wave step = 576 clk of the CU's 128 B/clk LDS pipe x 12 resident waves.)
 // Against k_march's pass B (16 samples x 4 lanes per step, 18 scattered 64-B gathers per sample; PMC: texture addresser 71 %
 // busy, VALU ~70 %) this removes ~15x of the addresser work and the 4x-redundant per-sample coordinate math. The
 // transmittance is a per-lane running product in sample order — exactly the reference's cumprod order
@@ -28,7 +31,14 @@ namespace t2n {
 // block per plane) covers nearly every step of a pinhole frame; LOG2W = 3 (64 slots, four row blocks) takes the rest.
 constexpr int kMaxLog2W = 2;
 constexpr int kDStrideMax = (1 << (2 * kMaxLog2W)) + 4;   // floats per line row of the transposed table D^T[line row][slot]
-constexpr int kStageFloats = 3 * 16 * kDStrideMax;       // per wave
+constexpr int kPairFloats = 3 * 16 * kDStrideMax;        // per wave: the three pair tables D_k^T
+// the summed table S[z][y][x] (4 x 4 x 4, one entry per lane); a lane reads up to 21 floats past its low corner, so the region is
+// padded to 64 + 32 floats (zeroed once per wave): a read past the last entry stays inside the wave's own region. S sits IN FRONT
+// of the pair tables: the eight entries of a sample are then four ds_read2_b32 off ONE address register (the instruction's two
+// offsets are 8-bit dword counts; behind the 960 floats of the pair tables every read pair needs an address of its own).
+constexpr int kSumFloats = 96;
+constexpr int kStageFloats = kPairFloats + kSumFloats;   // per wave
+static_assert(63 + 21 < kSumFloats && kStageFloats % 4 == 0, "summed table: the farthest read stays in the wave's region; 16-B aligned regions");
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 struct TileArgs {
@@ -96,8 +106,9 @@ __device__ __forceinline__ unsigned wave_or_u(unsigned v) {
 }
 
 // The dot-product tables of one wave step (see the file header). amn[a] = lowest tap index of axis a over the wave; every axis
-// spans at most 2^LOG2W taps. table_build computes D_k^T[line row][slot] for the three pairs into the wave's LDS area;
-// table_read returns a lane's density feature from its 4 x 2 entries per pair. Several samples per lane may share one build.
+// spans at most 2^LOG2W taps. table_build computes D_k^T[line row][slot] for the three pairs into the wave's LDS area, table_sum
+// adds them into S, table_read3 returns a lane's density feature from its 8 entries of S. Several samples per lane may share
+// one build.
 template <int LOG2W>
 __device__ __forceinline__ void table_build(const FactorSet& S, const int (&amn)[3], float* __restrict__ stD, int l15, int lq) {
     constexpr int WS = 1 << LOG2W, SL = WS * WS, NB = SL / 16, ST = SL + 4;
@@ -121,7 +132,7 @@ __device__ __forceinline__ void table_build(const FactorSet& S, const int (&amn)
     // phase 2: D_k^T[line row][slot] = sum_c L_k[row][c] P_k[slot][c]; the lane holds slots 4 lq..+3 of line row l15
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        float* __restrict__ Dk = stD + k * 16 * ST + l15 * ST + lq * 4;
+        float* __restrict__ Dk = stD + kSumFloats + k * 16 * ST + l15 * ST + lq * 4;
 #pragma unroll
         for (int mb = 0; mb < NB; ++mb) {
             f32x4_t d = {0.f, 0.f, 0.f, 0.f};
@@ -133,33 +144,42 @@ __device__ __forceinline__ void table_build(const FactorSet& S, const int (&amn)
         }
     }
 }
-// A lane's density feature from the tables: per pair ONE table offset (low line row, low plane cell); the other seven entries sit at
-// fixed distances from it, because a high tap is the low tap + 1 wherever its weight is not zero (axis_taps: the clamp at the
-// grid's last texel comes with weight 0). There the entry one step further is read instead of the clamped one - a finite table
-// value (every slot of the 16 line rows is written by each build, the four pad floats of a row are zeroed once per wave) times a
-// zero weight: the sum is the same. 12 address computations and 24 single reads per sample became 3 and 12 paired reads.
+// The three pair tables summed into ONE 4 x 4 x 4 table, once per build: the 24 entries a lane read from them are the terms of the 8
+// corner values of its cell in
+//     S[z][y][x] = D_0^T[z][y << 2 | x] + D_1^T[y][z << 2 | x] + D_2^T[x][z << 2 | y]
+// (pair 0 = plane (x, y) x line z, pair 1 = plane (x, z) x line y, pair 2 = plane (y, z) x line x), so a sample's density feature is
+// the trilinear interpolation of S over that cell. Lane e = z << 4 | y << 2 | x adds its three terms in a fixed order and stores
+// S[e]; the caller fences before and after. `lane` arrives behind an opaque copy (see the call site): the three offsets are lane
+// constants the compiler would otherwise keep in registers across the whole step loop.
 template <int LOG2W>
-__device__ __forceinline__ float table_read(const Axes3& A, const int (&amn)[3], const float* __restrict__ stD) {
-    constexpr int WS = 1 << LOG2W, SL = WS * WS, ST = SL + 4;
-    float part = 0.f;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int m0 = mat0(k), m1 = mat1(k), vv = vecm(k);
-        const Axis& ax = A.a[m0];
-        const Axis& ay = A.a[m1];
-        const Axis& al = A.a[vv];
-        // (24-bit multiply: full rate; v_mul_lo_u32 is quarter rate)
-        const int off = k * 16 * ST + (int)__umul24((unsigned)(al.i0 - amn[vv]), (unsigned)ST) + ((ay.i0 - amn[m1]) << LOG2W) + (ax.i0 - amn[m0]);
-        const float* __restrict__ D = stD + off;
-        const float wnw = ay.w0 * ax.w0, wne = ay.w0 * ax.w1, wsw = ay.w1 * ax.w0, wse = ay.w1 * ax.w1;
-        float v0 = D[0] * wnw, v1 = D[ST] * wnw;
-        v0 = fmaf(D[1], wne, v0); v1 = fmaf(D[ST + 1], wne, v1);
-        v0 = fmaf(D[WS], wsw, v0); v1 = fmaf(D[ST + WS], wsw, v1);
-        v0 = fmaf(D[WS + 1], wse, v0); v1 = fmaf(D[ST + WS + 1], wse, v1);
-        part = fmaf(v0, al.w0, part);
-        part = fmaf(v1, al.w1, part);
-    }
-    return part;
+__device__ __forceinline__ void table_sum(float* __restrict__ stD, int lane) {
+    static_assert(LOG2W == 2, "the summed table is one entry per lane: 4 taps per axis");
+    constexpr int ST = (1 << (2 * LOG2W)) + 4;
+    const unsigned x = (unsigned)lane & 3u, y = ((unsigned)lane >> 2) & 3u, z = (unsigned)lane >> 4;
+    const float* __restrict__ D = stD + kSumFloats;
+    // (24-bit multiplies: full rate)
+    const float d0 = D[__umul24(z, (unsigned)ST) + ((unsigned)lane & 15u)];
+    const float d1 = D[16 * ST + __umul24(y, (unsigned)ST) + (z << 2 | x)];
+    const float d2 = D[32 * ST + __umul24(x, (unsigned)ST) + (z << 2 | y)];
+    stD[lane] = (d0 + d1) + d2;
+}
+// A lane's density feature from the summed table: ONE offset (the low corner of its cell); the other seven entries sit at fixed
+// distances from it, because a high tap is the low tap + 1 wherever its weight is not zero (axis_taps: the clamp at the grid's last
+// texel comes with weight 0). There the entry one step further is read instead of the clamped one - a finite value (every entry of S
+// is written by each build from slots table_build fills with clamped texels, the padding behind S is zeroed once per wave) times a
+// zero weight: the sum is the same. The order of the additions is fixed (it does not depend on the box origin).
+// `org` = (amn[2] << 4) + (amn[1] << 2) + amn[0]: the box origin's part of the offset, wave-uniform.
+__device__ __forceinline__ float table_read3(const Axes3& A, int org, const float* __restrict__ stS) {
+    const Axis& ax = A.a[0];
+    const Axis& ay = A.a[1];
+    const Axis& az = A.a[2];
+    const float* __restrict__ D = stS + (((az.i0 << 4) + ((ay.i0 << 2) + ax.i0)) - org);
+    const float wnw = ay.w0 * ax.w0, wne = ay.w0 * ax.w1, wsw = ay.w1 * ax.w0, wse = ay.w1 * ax.w1;
+    float v0 = D[0] * wnw, v1 = D[16] * wnw;
+    v0 = fmaf(D[1], wne, v0); v1 = fmaf(D[17], wne, v1);
+    v0 = fmaf(D[4], wsw, v0); v1 = fmaf(D[20], wsw, v1);
+    v0 = fmaf(D[5], wse, v0); v1 = fmaf(D[21], wse, v1);
+    return fmaf(v1, az.w1, v0 * az.w0);
 }
 
 template <int K>
@@ -228,7 +248,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DENSE ? T2N
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
     float* __restrict__ stD = smem + (size_t)wid * kStageFloats;
-    for (int i = lane; i < kStageFloats; i += 64) stD[i] = 0.f;   // the rows' pad floats stay zero (table_read may touch them with weight 0)
+    for (int i = lane; i < kStageFloats; i += 64) stD[i] = 0.f;   // the padding behind S stays zero (table_read3 may touch it with weight 0)
     lds_fence_w();
     float* __restrict__ wt = smem + 4 * kStageFloats + (size_t)wid * kDenseFloats;   // DENSE only
     const FieldDev& F = a.F;
@@ -341,10 +361,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DENSE ? T2N
             if (ranged && span <= 4) {
                 table_build<2>(F.den, amn, stD, l15, lq);
                 lds_fence_w();
+                {
+                    // (the lane index behind an opaque copy, per build: visible, the sum pass's three lane offsets are hoisted out of
+                    // the step loop and spilled)
+                    int ln = lane;
+                    asm volatile("" : "+v"(ln));
+                    table_sum<2>(stD, ln);
+                }
+                lds_fence_w();
                 MT_T(p_build);
+                // (the origin's offset as ONE scalar the compiler cannot take apart again: left visible it subtracts the three
+                // amn[] from the three tap indices of every sample, one vector instruction each)
+                int org = (amn[2] << 4) + (amn[1] << 2) + amn[0];
+                asm volatile("" : "+s"(org));
 #pragma unroll
                 for (int q = 0; q < kSteps; ++q)
-                    if (ok[q]) part[q] = table_read<2>(A[q], amn, stD);
+                    if (ok[q]) part[q] = table_read3(A[q], org, stD);
                 lds_fence_w();
                 MT_T(p_read);
             } else {
