@@ -517,6 +517,39 @@ int t2n_train_loss(const float* rgb, const float* depth, const float* weights, c
                    const float* depth_t, int64_t n_rays, int n_samples, float w_depth, float w_trans, float delta, float* d_rgb,
                    float* d_depth, float* d_weights, float* losses, void* workspace, size_t workspace_bytes, t2n_stream stream);
 
+/* The reference's other depth losses (utils.py:301-342, selected upstream by --type_depth_loss, e_opt.py:20) as the depth term of the
+ * driver's loss. depth_kind:
+ *   0 "mse"     mean((depth - depth_t)^2): t2n_train_loss itself, bit-equal outputs (text2nerf_main.py:563-575);
+ *   1 "gnll"    compute_depth_loss + is_not_in_expected_distribution (utils.py:301-320): |mean over the K applying rays of
+ *               1/2 (log v + (mu - y)^2 / v)|, var = sum_n (z - mu)^2 w + 1e-8, v = max(var, 1e-3), a ray applies when
+ *               |mu - y| - target_std > 0 or target_std^2 < var; K = 0: loss 0, gradients exactly 0;
+ *   2 "si_log"  compute_depth_loss_scale_invariant (utils.py:324-331): mean |d + alpha|, d = log mu - log y, alpha = -mean d
+ *               (non-positive depths give IEEE's NaN / inf, as upstream);
+ *   3 "ssi"     scale_shift_invariant_loss (utils.py:333-342): y ~ s z + t by weighted least squares over all R x N samples
+ *               (float64 moments; rank-deficient systems follow the pseudo-inverse), then mean(w (s z + t - y)^2) with s, t
+ *               rounded to float32 as upstream's multiplication does; gradient to the weights only.
+ * t2n_train_loss_ex: t2n_train_loss with that depth term: losses[4] = {mse, depth term, transmittance loss, mse + w_depth * term +
+ * w_trans * transmittance}, d_depth and d_weights carry w_depth times the term's gradients (d_weights: plus the transmittance
+ * term's, written once, exact zeros where neither contributes); NaN depths count as 0 and get no d_depth (text2nerf_main.py:559-560).
+ * aux (device, 4 doubles): gnll {K, signed mean NLL}, si_log {alpha}, ssi {s, t}, the rest 0. Every scalar that couples the rays
+ * stays on the device; sums in a fixed order (two calls give the same bits). workspace: t2n_train_loss_ex_workspace_bytes(n_rays),
+ * 8-byte aligned.
+ * t2n_depth_loss: the depth term alone (kind 1..3) with its gradients for upstream gradient 1: loss (1 float), d_depth [R] and
+ * d_weights [R,N] (either may be NULL); weights / z_vals may be NULL for si_log, depth for ssi; no NaN rule. workspace:
+ * t2n_depth_loss_workspace_bytes(n_rays), 8-byte aligned. Python: losses.compute_depth_loss, compute_depth_loss_scale_invariant,
+ * scale_shift_invariant_loss.
+ * T2N_ERR_INVALID (before any launch): NULL / non-positive argument, unknown kind, target_std <= 0 for gnll, misaligned workspace;
+ * T2N_ERR_WORKSPACE: workspace too small. */
+size_t t2n_train_loss_ex_workspace_bytes(int64_t n_rays);
+int t2n_train_loss_ex(const float* rgb, const float* depth, const float* weights, const float* z_vals, const float* rgb_t,
+                      const float* depth_t, int64_t n_rays, int n_samples, float w_depth, float w_trans, float delta, int depth_kind,
+                      float target_std, float* d_rgb, float* d_depth, float* d_weights, float* losses, double* aux, void* workspace,
+                      size_t workspace_bytes, t2n_stream stream);
+size_t t2n_depth_loss_workspace_bytes(int64_t n_rays);
+int t2n_depth_loss(int kind, const float* depth, const float* weights, const float* z_vals, const float* depth_t, int64_t n_rays,
+                   int n_samples, float target_std, float* loss, double* aux, float* d_depth, float* d_weights, void* workspace,
+                   size_t workspace_bytes, t2n_stream stream);
+
 /* ---- SURVEY.md 8(f-1), optional: the dense tail of the training step as streaming kernels.
  * t2n_tv_grad_add: grad += d/dparam [ weight * TVLoss(param) ] for one reference-layout plane [1,C,H,W]
  *   (utils.py:488-504; the driver's term is TV_loss_*(tvreg) * TV_weight with TV_loss_* = sum_planes 1e-2 * TVLoss,

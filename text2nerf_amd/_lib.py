@@ -21,6 +21,7 @@ FLAG_PIPELINE = 64
 FLAG_GATHER_BATCH = 128
 SHADE_IDS = {"MLP_Fea_noview": 0, "SH": 1, "RGB": 2, "MLP_Fea": 3, "MLP_PE": 4, "MLP": 5}   # MLP_PE: rejected in tensorf.py (broken upstream)
 ACT_IDS = {"softplus": 0, "relu": 1}
+DEPTH_KINDS = {"mse": 0, "gnll": 1, "si_log": 2, "ssi": 3}   # depth_kind of t2n_train_loss_ex / t2n_depth_loss
 MASK_U8, MASK_I32, MASK_I64, MASK_F32, MASK_F64 = 0, 1, 2, 3, 4   # T2N_MASK_*: dtypes t2n_format_views reads a mask in
 
 
@@ -153,6 +154,13 @@ SIGNATURES = {
     "t2n_train_loss_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "t2n_train_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float,
                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_train_loss_ex_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "t2n_train_loss_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float,
+                                    C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_depth_loss_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "t2n_depth_loss": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "t2n_field_set_factor_storage": (C.c_int, [C.c_void_p, C.c_int]),
     "t2n_frame_postprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -99,3 +99,103 @@ class TransMittanceLoss_mask(nn.Module):
     def forward(self, transmittance, mask):
         mean_trans = torch.mean(transmittance * mask, dim=1)
         return torch.mean(mean_trans ** 2)
+
+
+# ---- the reference's depth losses (utils.py:301-342) on device tensors: one HIP call each (t2n_depth_loss) ------------------------------
+class _DepthLoss(torch.autograd.Function):
+    """One of the depth terms of csrc/t2n_depth_loss.hip (kind 1 gnll, 2 si_log, 3 ssi) as (loss, aux): the forward call also writes the
+    gradients for upstream gradient 1 (d_depth [R], d_weights [R, N]) and keeps them; the backward multiplies them by grad_output, so
+    the function composes with OctreeRender_trilinear_fast(..., is_train=True) in an otherwise unchanged autograd loop. `aux` (4
+    float64, on the device) is not differentiable. z_vals gets no gradient (the renderer's sample depths carry none)."""
+
+    @staticmethod
+    def forward(ctx, kind, target_std, depth, weights, z_vals, target):
+        lib = _lib.load()
+        ref = depth if depth is not None else weights
+        dev = ref.device
+        f32 = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()      # noqa: E731
+        dep, w, z, y = f32(depth), f32(weights), f32(z_vals), f32(target)
+        R = int(y.shape[0])
+        N = int(w.shape[1]) if w is not None else 1
+        want_d = depth is not None and ctx.needs_input_grad[2]
+        want_w = weights is not None and ctx.needs_input_grad[3] and kind != 2
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        aux = torch.empty(4, device=dev, dtype=torch.float64)
+        d_depth = torch.empty(R, device=dev, dtype=torch.float32) if want_d else None
+        d_w = torch.empty(R, N, device=dev, dtype=torch.float32) if want_w else None
+        ws = torch.empty(int(lib.t2n_depth_loss_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.t2n_depth_loss(kind, _lib.ptr(dep), _lib.ptr(w), _lib.ptr(z), _lib.ptr(y), R, N, float(target_std), _lib.ptr(loss),
+                                          _lib.ptr(aux), _lib.ptr(d_depth), _lib.ptr(d_w), _lib.ptr(ws), ws.numel(),
+                                          _lib.current_stream_ptr(dev)), "t2n_depth_loss")
+        ctx.grads = (d_depth, d_w)       # this call's own outputs; of the inputs only shape and dtype are needed again
+        ctx.like = tuple(None if t is None else (tuple(t.shape), t.dtype) for t in (depth, weights))
+        ctx.mark_non_differentiable(aux)
+        return loss.reshape(()), aux
+
+    @staticmethod
+    def backward(ctx, grad_loss, grad_aux):
+        d_depth, d_w = ctx.grads
+        depth, weights = ctx.like            # (shape, dtype) of the inputs, or None
+        g = grad_loss.detach().to(torch.float32)
+        g_depth = g_w = None
+        if depth is not None and ctx.needs_input_grad[2]:
+            g_depth = (d_depth * g).reshape(depth[0]).to(depth[1])
+        if weights is not None and ctx.needs_input_grad[3]:
+            g_w = (d_w * g).reshape(weights[0]).to(weights[1]) if d_w is not None \
+                else torch.zeros(weights[0], dtype=weights[1], device=g.device)
+        return None, None, g_depth, g_w, None, None
+
+
+def _device_rays(name, **tensors):
+    """The shared checks of the depth-loss functions: device tensors (no CPU fallback) of matching ray counts."""
+    from ._lib import T2NError
+    for k, t in tensors.items():
+        if not torch.is_tensor(t):
+            raise T2NError(f"{name}: {k} must be a tensor")
+        if not t.is_cuda:
+            raise T2NError(f"{name}: {k} is on {t.device}; the depth losses run as HIP kernels on device tensors (no CPU fallback)")
+    rows = {k: int(t.shape[0]) if t.dim() else -1 for k, t in tensors.items()}
+    if len(set(rows.values())) != 1 or -1 in rows.values():
+        raise T2NError(f"{name}: the tensors disagree about the number of rays: {rows}")
+    return next(iter(rows.values()))
+
+
+def is_not_in_expected_distribution(depth_mean, depth_var, depth_measurement_mean, depth_measurement_std):
+    """utils.py:301-304: the rays a depth measurement does not yet explain — |mean - measurement| exceeds the measurement's standard
+    deviation, or the ray's termination variance exceeds the measurement's. Elementwise torch ops; compute_depth_loss evaluates
+    the same predicate inside its kernel."""
+    off_mean = torch.abs(depth_mean - depth_measurement_mean) - depth_measurement_std
+    return (off_mean > 0) | (depth_var > depth_measurement_std * depth_measurement_std)
+
+
+def compute_depth_loss(depth_map, z_vals, weights, target_depth, target_std=0.1):
+    """utils.py:306-320 on device tensors (t2n_depth_loss, kind gnll): the Gaussian negative log-likelihood (nn.GaussianNLLLoss(eps=0.001))
+    of the rendered depth under the ray's own termination variance, over the rays is_not_in_expected_distribution selects, as an
+    absolute value. Returns the reference's shapes: a scalar, or a (1,) zero tensor that requires grad when no ray is selected or
+    there is no ray — which of the two is known on the device only, so this function (like upstream's boolean indexing) waits for
+    the kernel; TensorVMSplit.train_step(depth_loss="gnll") does not."""
+    if depth_map.shape[0] == 0:
+        return torch.zeros((1,), device=depth_map.device, requires_grad=True)
+    _device_rays("compute_depth_loss", depth_map=depth_map, z_vals=z_vals, weights=weights, target_depth=target_depth)
+    loss, aux = _DepthLoss.apply(1, float(target_std), depth_map, weights, z_vals, target_depth)
+    if float(aux[0]) == 0.0:
+        return torch.zeros((1,), device=depth_map.device, requires_grad=True)
+    return loss
+
+
+def compute_depth_loss_scale_invariant(depth_map, target_depth):
+    """utils.py:324-331 on device tensors (t2n_depth_loss, kind si_log): mean |log depth - log target + alpha| with alpha the mean
+    log-ratio. Non-positive depths give NaN / inf, as upstream."""
+    _device_rays("compute_depth_loss_scale_invariant", depth_map=depth_map, target_depth=target_depth)
+    return _DepthLoss.apply(2, 0.0, depth_map, None, None, target_depth)[0]
+
+
+def scale_shift_invariant_loss(z_vals, weights, target_depth):
+    """utils.py:333-342 on device tensors (t2n_depth_loss, kind ssi): the weighted least-squares fit target ~ s z + t over all samples
+    (float64 normal equations on the device instead of statsmodels on a host copy; rank-deficient systems follow the pseudo-inverse),
+    then mean(weights (s z + t - target)^2). Returns (loss, s, t). Unlike upstream, `s` and `t` are float64 0-d DEVICE tensors, not
+    host floats: nothing is read back. The gradient goes to `weights` alone (the fit sees them detached, as upstream)."""
+    _device_rays("scale_shift_invariant_loss", z_vals=z_vals, weights=weights, target_depth=target_depth)
+    loss, aux = _DepthLoss.apply(3, 0.0, None, weights, z_vals, target_depth)
+    return loss, aux[0], aux[1]

@@ -32,6 +32,14 @@ _SEED_MIN_RAYS = 8192
 _WORKSPACE = {}
 
 
+def _depth_kind(name) -> int:
+    """depth_kind of t2n_train_loss_ex for train_step's `depth_loss` keyword."""
+    kind = _lib.DEPTH_KINDS.get(name)
+    if kind is None:
+        raise T2NError(f"depth_loss={name!r}: expected one of {', '.join(map(repr, _lib.DEPTH_KINDS))}")
+    return kind
+
+
 def _ws_key(device):
     device = torch.device(device)
     if device.type != "cuda":
@@ -1380,7 +1388,8 @@ class TensorBase(nn.Module):
         return grads
 
     def train_step(self, rays, rgb_target, depth_target, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
-                   tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None):
+                   tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None, depth_loss="mse",
+                   depth_std=0.1):
         """One optimisation step of text2nerf_main.py:547-590 without the autograd graph: render (train mode, CPU-generator jitter
         like models/tensorBase.py:313-317) -> the driver's loss as ONE kernel that emits d_rgb / d_depth / d_weights
         (t2n_train_loss) -> t2n_render_backward -> optimizer.step(). `optimizer`: optim.TVAdam(field=self) (TV terms via `tv`, as
@@ -1400,10 +1409,18 @@ class TensorBase(nn.Module):
         truncated gradient). Host batches take the PIPELINED form of the call: the step's early part (batch copy, march, plan, appearance
         binning) runs beside the previous step's tail. `graph=True` (single process): the call captured once per input buffer into a
         hipGraph and replayed — one submission per step, but ROCm's graph executor serialises what the eager call overlaps (1.02 against
-        0.86 ms per 16 384-ray step measured), so it is opt-in. The returned loss tensor is a fixed buffer the next step overwrites."""
+        0.86 ms per 16 384-ray step measured), so it is opt-in. The returned loss tensor is a fixed buffer the next step overwrites.
+        `depth_loss`: the depth term, "mse" (the driver's, the default), or one of the reference's other depth losses (utils.py:301-342,
+        --type_depth_loss): "gnll" (compute_depth_loss with `depth_std` as its target_std), "si_log"
+        (compute_depth_loss_scale_invariant) or "ssi" (scale_shift_invariant_loss) — t2n_train_loss_ex. The returned tensor keeps its
+        layout [mse, depth term, transmittance loss, mse + w_depth * term + w_trans * transmittance]; `self.last_depth_aux` is the
+        call's device float64 tensor of the term's coupling scalars (gnll: K, signed mean NLL; si_log: alpha; ssi: s, t; None for
+        "mse"). The one-call step has the mse term folded in: any other kind takes the composed route, and `fused=True` with it raises."""
         lib = _lib.load()
         params = self._autograd_params()
-        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph)
+        kind = _depth_kind(depth_loss)
+        self.__dict__["last_depth_aux"] = None
+        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, kind)
         if fuse is not None:
             fs, N, flags, use_graph = fuse
             return fs.step(rays, rgb_target, depth_target, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce)
@@ -1439,11 +1456,21 @@ class TensorBase(nn.Module):
             rgb, depth, z, w, ws = self._render_raw(rays, N, flags, jitter, True, keep_ctx=True, reuse_ctx=True)
             d_rgb, d_depth, d_w = torch.empty_like(rgb), torch.empty_like(depth), torch.empty_like(w)
             losses = torch.empty(4, device=dev)
-            lws = torch.empty(int(lib.t2n_train_loss_workspace_bytes(R)), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(lib.t2n_train_loss(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
-                                              float(w_depth), float(w_trans), float(delta), _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w),
-                                              _lib.ptr(losses), _lib.ptr(lws), lws.numel(), _lib.current_stream_ptr(dev)), "t2n_train_loss")
+            if kind == 0:
+                lws = torch.empty(int(lib.t2n_train_loss_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.t2n_train_loss(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
+                                                  float(w_depth), float(w_trans), float(delta), _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w),
+                                                  _lib.ptr(losses), _lib.ptr(lws), lws.numel(), _lib.current_stream_ptr(dev)), "t2n_train_loss")
+            else:
+                lws = torch.empty(int(lib.t2n_train_loss_ex_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+                aux = torch.empty(4, dtype=torch.float64, device=dev)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.t2n_train_loss_ex(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
+                                                     float(w_depth), float(w_trans), float(delta), kind, float(depth_std), _lib.ptr(d_rgb),
+                                                     _lib.ptr(d_depth), _lib.ptr(d_w), _lib.ptr(losses), _lib.ptr(aux), _lib.ptr(lws), lws.numel(),
+                                                     _lib.current_stream_ptr(dev)), "t2n_train_loss_ex")
+                self.__dict__["last_depth_aux"] = aux
             # head gradients: views of one flat buffer (one memset), installed as .grad of the 7 head tensors
             self._head_flat.zero_()
             views, off = [], 0
@@ -1483,7 +1510,8 @@ class TensorBase(nn.Module):
         return losses
 
     def train_step_indexed(self, source, ids, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
-                           tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None):
+                           tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None, depth_loss="mse",
+                           depth_std=0.1):
         """`train_step` on rows `ids` of a `dataset.DeviceTrainSet` (rays, colours and depths kept on the device): same keyword
         arguments, same arithmetic, same draws from the CPU generator in the same order. `ids`: an int64 (as SimpleSampler returns it) or
         int32 tensor. On the host its range is checked before anything is drawn or queued — an id outside [0, len(source)) or a
@@ -1493,18 +1521,26 @@ class TensorBase(nn.Module):
         the fused step does not apply this is `train_step(*source.rows(ids), ...)`."""
         from .dataset import check_ids
         ids = check_ids(ids, len(source))
-        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph)
+        self.__dict__["last_depth_aux"] = None
+        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph,
+                                    _depth_kind(depth_loss))
         if fuse is not None:
             fs, N, flags, use_graph = fuse
             return fs.step_indexed(source, ids, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce)
         rays, rgb_t, dep_t = source.rows(ids)
         return self.train_step(rays, rgb_t, dep_t, optimizer, N_samples=N_samples, white_bg=white_bg, w_depth=w_depth, w_trans=w_trans,
                                delta=delta, tv=tv, all_reduce=all_reduce, all_reduce_averages=all_reduce_averages, speculative=speculative,
-                               fused=False if fused is None else fused, graph=graph)
+                               fused=False if fused is None else fused, graph=graph, depth_loss=depth_loss, depth_std=depth_std)
 
-    def _fused_step_for(self, optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph):
+    def _fused_step_for(self, optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, depth_kind=0):
         """The fuse decision of train_step / train_step_indexed: None (the composed step), or (the field's FusedStep for this optimiser,
-        N, flags, use_graph) with the background coin drawn — the first draw of a fused step from the CPU generator."""
+        N, flags, use_graph) with the background coin drawn — the first draw of a fused step from the CPU generator. A depth term other
+        than "mse" (depth_kind != 0) cannot fuse: the one-call step's loss is folded into its backward."""
+        if depth_kind != 0:
+            if fused:
+                raise T2NError("train_step(fused=True): the one-call step computes the \"mse\" depth term only; depth_loss=gnll / si_log / ssi "
+                               "runs on the composed route (fused=None or False)")
+            return None
         can_fuse = self._can_fuse_train_step(optimizer) and (all_reduce is None or all_reduce_averages) and not speculative
         if fused and not can_fuse:
             raise T2NError("train_step(fused=True): needs the tuned field shape with the MLP_Fea_noview head (split-f16 arithmetic), fp32 factor "
