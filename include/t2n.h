@@ -285,7 +285,8 @@ typedef struct t2n_generic_desc {
 size_t t2n_generic_workspace_bytes(int64_t n_rays, int n_samples);
 /* the same + room for channel-last staging copies of the factor tensors and the appearance-sample list: with this much workspace the
  * FORWARD runs as cooperative kernels (thread per sample for the density, a workgroup per 64 appearance samples for features + head)
- * instead of the plain form — 1 500 x per sample apart on a wide 128^3 field. Same outputs and context; the backward is unchanged. */
+ * instead of the plain form — 1 500 x per sample apart on a wide 128^3 field. Same outputs and context; the backward's kernel form
+ * (t2n_generic_backward_staged) reuses the staged copies and the list. */
 size_t t2n_generic_workspace_bytes_desc(const t2n_generic_desc* desc, int64_t n_rays, int n_samples);
 int t2n_generic_forward(const t2n_generic_desc* desc, const t2n_field_params* params, const float* rays, int64_t n_rays, int ray_stride,
                         int n_samples, uint32_t flags, const float* jitter, float* rgb, float* depth, float* weights, float* z_vals,
@@ -294,6 +295,29 @@ int t2n_generic_backward(const t2n_generic_desc* desc, const t2n_field_params* p
                          int n_samples, uint32_t flags, const float* jitter, const float* weights, const float* z_vals,
                          const float* d_rgb, const float* d_depth, const float* d_weights, const t2n_field_grads* grads,
                          void* workspace, size_t workspace_bytes, t2n_stream stream);
+/* The same backward as kernels (csrc/t2n_generic_bwd.hip; what autograd derives for models/tensorBase.py:436-507, :19-26, :406-410, the heads
+ * :11-17 + :29-39 + :62-159 and models/tensoRF.py:205-239): a wave per ray for the reverse scan, the factor gradients scattered into
+ * channel-last copies (lanes along the components of a tap row) and transposed into `grads` at the end, the MLP's weight, bias and basis
+ * gradients as exact-fp32 MFMA GEMMs over row chunks with partial slabs and a reduce (no atomics on them: deterministic; the factor
+ * gradients carry float-atomic arrival order), in passes of `pass_rows` appearance-list entries issued for the worst case and clipped to
+ * the forward's device-side count. `workspace` is the forward's, as t2n_generic_backward receives it: its staged factor copies, list,
+ * count and context are reused. t2n_generic_backward_plan (host only, touches no device) says whether the kernel form applies —
+ * kernel_form 1: the forward ran its kernel form (head LDS <= 160 KB, T2N_GENERIC_PLAIN unset), the head is SH, RGB or an MLP with <= 512
+ * inputs, and T2N_GENERIC_PLAIN_BWD is unset — and how much scratch it needs; where it does not apply, t2n_generic_backward_staged
+ * returns T2N_ERR_UNSUPPORTED before it queues anything and the caller takes t2n_generic_backward. pass_rows: 0 = 262144; rounded up to a
+ * multiple of 64 and clipped to the call's n_rays * n_samples (rounded likewise). No host read, no allocation, no synchronisation. */
+typedef struct t2n_generic_bwd_plan {
+    int kernel_form;          /* 1: the kernels, 0: the plain form (t2n_generic_backward) */
+    uint32_t pass_rows;       /* list entries per head pass (a multiple of 64) */
+    uint32_t max_passes;      /* ceil(n_rays * n_samples / pass_rows) */
+    size_t workspace_bytes;   /* of bwd_workspace (0 when kernel_form is 0) */
+} t2n_generic_bwd_plan;
+int t2n_generic_backward_plan(const t2n_generic_desc* desc, int64_t n_rays, int n_samples, uint32_t pass_rows, t2n_generic_bwd_plan* out);
+int t2n_generic_backward_staged(const t2n_generic_desc* desc, const t2n_field_params* params, const float* rays, int64_t n_rays,
+                                int ray_stride, int n_samples, uint32_t flags, const float* jitter, const float* weights,
+                                const float* z_vals, const float* d_rgb, const float* d_depth, const float* d_weights,
+                                const t2n_field_grads* grads, void* workspace, size_t workspace_bytes, void* bwd_workspace,
+                                size_t bwd_bytes, uint32_t pass_rows, t2n_stream stream);
 /* getDenseAlpha on the general-shape path (models/tensorBase.py:328-344, compute_alpha :412-434): alpha = 1 - exp(-sigma * length) at
  * the nodes aabb_min*(1-s) + aabb_max*s of a dense grid, s = (lin_x[i], lin_y[j], lin_z[k]) (device arrays holding torch.linspace(0,1,g));
  * sigma = 0 where the descriptor's alpha_volume (if any) samples <= 0. alpha is [gx][gy][gz]. Only the density factors and the

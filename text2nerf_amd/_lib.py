@@ -57,6 +57,11 @@ class GenericDesc(C.Structure):   # t2n_generic_desc: the general-shape path (cs
                 ("alpha_volume", C.c_void_p), ("alpha_dims", C.c_int32 * 3), ("alpha_aabb_min", C.c_float * 3),
                 ("alpha_aabb_max", C.c_float * 3)]
 
+
+class GenericBwdPlan(C.Structure):   # t2n_generic_bwd_plan: the general-shape backward's form and scratch (csrc/t2n_generic_bwd.hip)
+    _fields_ = [("kernel_form", C.c_int), ("pass_rows", C.c_uint32), ("max_passes", C.c_uint32), ("workspace_bytes", C.c_size_t)]
+
+
 TRAIN_HYPER_FLOATS = 32
 TRAIN_HEAD_GRAD_FLOATS = 27 * 144 + 128 * 351 + 128 + 128 * 128 + 128 + 3 * 128 + 3 + 1   # + the vote word
 TRAIN_HEAD_SIZES = (27 * 144, 128 * 351, 128, 128 * 128, 128, 3 * 128, 3)
@@ -229,6 +234,10 @@ SIGNATURES = {
     "t2n_generic_backward": (C.c_int, [C.POINTER(GenericDesc), C.POINTER(FieldParams), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FieldGrads),
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_generic_backward_plan": (C.c_int, [C.POINTER(GenericDesc), C.c_int64, C.c_int, C.c_uint32, C.POINTER(GenericBwdPlan)]),
+    "t2n_generic_backward_staged": (C.c_int, [C.POINTER(GenericDesc), C.POINTER(FieldParams), C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                              C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(FieldGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "t2n_generic_dense_alpha": (C.c_int, [C.POINTER(GenericDesc), C.POINTER(FieldParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "t2n_generic_filter_rays": (C.c_int, [C.POINTER(GenericDesc), C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,

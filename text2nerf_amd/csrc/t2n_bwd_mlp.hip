@@ -341,7 +341,6 @@ __global__ __launch_bounds__(256) void k_pe_bwd(const float* __restrict__ gx, co
 
 // split of a [rows] x (M<=128) x N weight-gradient GEMM into row chunks: ~768 workgroups, chunk a multiple of 32 rows
 constexpr int kL2Blocks = 1024;   // workgroups of k_bwd_l2 (four per CU)
-struct TnPlan { int chunk_rows, chunks, ng, ldp; };
 TnPlan tn_plan(int64_t rows, int N) {
     TnPlan p;
     p.ng = (N + 127) / 128;

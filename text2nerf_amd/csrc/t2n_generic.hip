@@ -1,12 +1,20 @@
 // General-shape render path: field / head shapes beyond what the tuned kernels hold (more than 16 density or 48 appearance
 // components per plane, app_dim > 27 / fea_pe > 6 / featureC > 128 on the MLP heads). The reference is generic in all of them
-// (models/tensoRF.py:144-160, models/tensorBase.py:62-159, e_opt.py:83-107); here they run as a plain restatement — one thread per
-// ray for the march, one thread per appearance sample for the head, loops over the component / unit counts, parameters read in place
-// in the reference's own layouts ([1,C,H,W] planes, [1,C,L,1] lines), gradients accumulated with atomics into those layouts. No MFMA,
-// no LDS staging: a path that removes the shape limit, not a fast one (the driver's configuration never comes here). NDC sampling (the
-// depth table in FieldDev::ztab, |d|-scaled distances, unit view directions) and the AlphaGridMask (the descriptor's volume, tested in
-// gen_point: masked samples are neither evaluated nor differentiated) in every kernel, forward and backward; getDenseAlpha on the
-// reference layouts (k_gen_dense_alpha) and filtering_rays from the descriptor (the field path's k_filter_bbox / k_filter_alpha).
+// (models/tensoRF.py:144-160, models/tensorBase.py:62-159, e_opt.py:83-107). Two forms of each direction live on this path:
+//   forward   the kernel form (k_gen_stage ... k_gen_head below: channel-last staging of the factors in the workspace, a wave per ray
+//             for the scan, an appearance list, MLP layers 0 / 1 on the exact-fp32 matrix cores through k_dense), taken whenever the
+//             head's LDS fits; and the plain form (k_gen_march / k_gen_shade<false>: a thread per ray / per sample, parameters read in
+//             place in the reference's layouts) as the fallback and the A/B partner (T2N_GENERIC_PLAIN=1).
+//   backward  the kernel form in t2n_generic_bwd.hip (t2n_generic_backward_staged: reverse scan with a wave per ray, factor gradients
+//             scattered into channel-last copies with lanes along the components, the head's weight gradients as fp32-MFMA GEMMs with
+//             partial slabs and a reduce, input gradients through k_dense with transposed weights), taken when the forward ran its kernel
+//             form and the head is SH, RGB or an MLP with <= 512 inputs; and the plain form here (t2n_generic_backward: k_gen_bwd_march +
+//             k_gen_shade<true>, global atomics into the reference layouts) for every other shape and for A/B runs
+//             (T2N_GENERIC_PLAIN_BWD=1).
+// NDC sampling (the depth table in FieldDev::ztab, |d|-scaled distances, unit view directions) and the AlphaGridMask (the descriptor's
+// volume, tested in gen_point: masked samples are neither evaluated nor differentiated) in every kernel of both forms and directions;
+// getDenseAlpha on the reference layouts (k_gen_dense_alpha) and filtering_rays from the descriptor (the field path's k_filter_bbox /
+// k_filter_alpha). The shared argument blocks, carves and inline helpers are in t2n_generic.h.
 //
 // Replaces: models/tensorBase.py:293-323 (sample_ray_ndc, sample_ray), :436-507 (forward, its NDC and mask lines :441-456), :19-26
 // (raw2alpha), :406-410 (feature2density), :11-17 + :62-159 (the heads), :29-39 (SH / RGB), :328-344 + :412-434 (getDenseAlpha /
@@ -14,91 +22,10 @@
 #include <stdlib.h>
 
 #include "t2n_device.h"
+#include "t2n_generic.h"
 
 namespace t2n {
 
-constexpr int kGenDimMax = 64, kGenHidMax = 256, kGenInMax = 4096;
-
-struct GenArgs {
-    FieldDev F;                       // scalars only (aabb, step, thresholds, activation); the factor sets of F are unused here
-    int grid[3], Cd[3], Ca[3], app_dim, shading, fea_pe, view_pe, fC, in0;
-    const float* dp[3]; const float* dl[3]; const float* ap[3]; const float* al[3];
-    const float* basis; const float* w0; const float* b0; const float* w1; const float* b1; const float* w2; const float* b2;
-    float* g_dp[3]; float* g_dl[3]; float* g_ap[3]; float* g_al[3];
-    float* g_basis; float* g_w0; float* g_b0; float* g_w1; float* g_b1; float* g_w2; float* g_b2;
-    const float* rays; long long n_rays; int ray_stride; int N; int train; int add_bg;
-    const float* jitter;
-    float* rgb; float* depth;         // outputs
-    float* w; float* z;               // [R, N] rows (the caller's tensors or workspace)
-    float* sigma; float* T;           // [R, N] context: density and transmittance in front of every sample
-    float* rgb_s;                     // [R, N, 3] colours of the appearance samples (context)
-    float* acc; float* raw;           // [R] opacity, [R, 3] colour before the clamp
-    const float* d_rgb; const float* d_depth; const float* d_w;   // upstream gradients
-    float* go;                        // [R, N, 3] dL/d colour of the appearance samples (backward scratch)
-    unsigned long long* stats;
-};
-
-struct Tap3 { Axis a[3]; };
-__device__ __forceinline__ Tap3 gen_taps(const GenArgs& a, float xn, float yn, float zn) {
-    Tap3 t;
-    t.a[0] = axis_taps(xn, a.grid[0]); t.a[1] = axis_taps(yn, a.grid[1]); t.a[2] = axis_taps(zn, a.grid[2]);
-    return t;
-}
-// plane k of a factor set in the reference layout: value(c, y, x) = P[(c * H + y) * W + x], H = grid[mat1(k)], W = grid[mat0(k)]
-__device__ __forceinline__ float gen_plane(const float* __restrict__ P, int c, int H, int W, const Axis& ax, const Axis& ay) {
-    const float* __restrict__ p = P + (size_t)c * H * W;
-    float v = p[(size_t)ay.i0 * W + ax.i0] * (ay.w0 * ax.w0);
-    v = fmaf(p[(size_t)ay.i0 * W + ax.i1], ay.w0 * ax.w1, v);
-    v = fmaf(p[(size_t)ay.i1 * W + ax.i0], ay.w1 * ax.w0, v);
-    v = fmaf(p[(size_t)ay.i1 * W + ax.i1], ay.w1 * ax.w1, v);
-    return v;
-}
-__device__ __forceinline__ float gen_line(const float* __restrict__ Ln, int c, int Lsz, const Axis& al) {
-    const float* __restrict__ p = Ln + (size_t)c * Lsz;
-    return fmaf(p[al.i1], al.w1, p[al.i0] * al.w0);
-}
-__device__ __forceinline__ void gen_plane_add(float* __restrict__ G, int c, int H, int W, const Axis& ax, const Axis& ay, float g) {
-    float* __restrict__ p = G + (size_t)c * H * W;
-    atomicAdd(p + (size_t)ay.i0 * W + ax.i0, g * (ay.w0 * ax.w0));
-    atomicAdd(p + (size_t)ay.i0 * W + ax.i1, g * (ay.w0 * ax.w1));
-    atomicAdd(p + (size_t)ay.i1 * W + ax.i0, g * (ay.w1 * ax.w0));
-    atomicAdd(p + (size_t)ay.i1 * W + ax.i1, g * (ay.w1 * ax.w1));
-}
-__device__ __forceinline__ void gen_line_add(float* __restrict__ G, int c, int Lsz, const Axis& al, float g) {
-    float* __restrict__ p = G + (size_t)c * Lsz;
-    atomicAdd(p + al.i0, g * al.w0);
-    atomicAdd(p + al.i1, g * al.w1);
-}
-
-__device__ __forceinline__ float gen_density_feature(const GenArgs& a, const Tap3& t) {
-    float feat = 0.f;
-    for (int k = 0; k < 3; ++k) {
-        const int W = a.grid[mat0(k)], H = a.grid[mat1(k)], Lz = a.grid[vecm(k)];
-        const Axis& ax = t.a[mat0(k)]; const Axis& ay = t.a[mat1(k)]; const Axis& al = t.a[vecm(k)];
-        for (int c = 0; c < a.Cd[k]; ++c) feat = fmaf(gen_plane(a.dp[k], c, H, W, ax, ay), gen_line(a.dl[k], c, Lz, al), feat);
-    }
-    return feat;
-}
-
-// box test, eval z gate and — when the field carries one — the AlphaGridMask (models/tensorBase.py:451-456): a masked sample is not
-// evaluated and gets no density gradient. MASK = false: coordinates of a sample already known to be valid (the appearance kernels)
-template <bool MASK = true>
-__device__ __forceinline__ bool gen_point(const GenArgs& a, const Ray& ray, float z, float& xn, float& yn, float& zn) {
-    bool ok = a.train ? sample_point<true>(a.F, ray, z, xn, yn, zn) : sample_point<false>(a.F, ray, z, xn, yn, zn);
-    if (MASK && a.F.alpha && ok) ok = alpha_pass(a.F, ray, z);
-    return ok;
-}
-// z_i: t_min + step (i [+ u]), or the NDC depth table (F.ztab) shared by all rays
-__device__ __forceinline__ float gen_z(const GenArgs& a, const Ray& ray, int i, float u) {
-    return a.train ? sample_z<true>(a.F, ray, i, u) : sample_z<false>(a.F, ray, i, 0.f);
-}
-// the ray's jitter draw (train mode; on the NDC path `jitter` is the [N] depth table instead)
-__device__ __forceinline__ float gen_u(const GenArgs& a, long long r) { return (a.train && !a.F.ztab) ? a.jitter[r] : 0.f; }
-// the heads' view direction: the ray's d, divided by |d| on the NDC path (models/tensorBase.py:445)
-__device__ __forceinline__ void gen_dir(const GenArgs& a, const Ray& ray, float* dir) {
-    dir[0] = ray.dx; dir[1] = ray.dy; dir[2] = ray.dz;
-    if (a.F.ztab) { dir[0] = dir[0] / ray.norm; dir[1] = dir[1] / ray.norm; dir[2] = dir[2] / ray.norm; }
-}
 
 // ---- march: one thread per ray --------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_gen_march(const GenArgs a) {
@@ -163,14 +90,6 @@ __device__ __forceinline__ int gen_inputs(const GenArgs& a, const float* __restr
         for (int d = 0; d < 3; ++d) for (int o = 0; o < a.view_pe; ++o) fn(n++, cosf(dir[d] * (float)(1 << o)), -1, 0.f);
     }
     return n;
-}
-__device__ __forceinline__ void gen_sh9(const float* dir, float* sh) {   // models/sh.py:4-14,87-112 (degree 2)
-    const float dx = dir[0], dy = dir[1], dz = dir[2];
-    const float C0 = 0.28209479177387814f, C1 = 0.4886025119029199f;
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz, xy = dx * dy, yz = dy * dz, xz = dx * dz;
-    sh[0] = C0; sh[1] = -C1 * dy; sh[2] = C1 * dz; sh[3] = -C1 * dx;
-    sh[4] = 1.0925484305920792f * xy; sh[5] = -1.0925484305920792f * yz; sh[6] = 0.31539156525252005f * (2.0f * zz - xx - yy);
-    sh[7] = -1.0925484305920792f * xz; sh[8] = 0.5462742152960396f * (xx - yy);
 }
 // hidden layers: h = b + W x (row-major [out, in] like nn.Linear), pre-activation values kept (the backward needs the ReLU masks)
 __device__ __forceinline__ void gen_linear(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ x, int nin, int nout,
@@ -363,7 +282,7 @@ __global__ __launch_bounds__(64) void k_gen_bwd_march(const GenArgs a) {
 }
 
 // =====================================================================================================================================
-// The forward as kernels (round 6; the backward above stays the plain restatement): what made the first form 1 500 x slower than the tuned
+// The forward as kernels (round 6; the backward's kernel form is t2n_generic_bwd.hip, the one above its plain form): what made the first form 1 500 x slower than the tuned
 // path per sample was its shape, not its arithmetic — one THREAD walked a whole ray (2 500 waves for a 400 x 400 frame) reading
 // [1, C, H, W] factors one component per cache line, and one thread ran a whole MLP out of scratch memory. Here:
 //   k_gen_stage      the twelve factor tensors -> channel-last copies in the workspace ([pos][C]: a tap's components are contiguous)
@@ -379,23 +298,12 @@ __global__ __launch_bounds__(64) void k_gen_bwd_march(const GenArgs a) {
 //                    passes are issued for the worst case and clipped to the device-side count (T2N_GENERIC_VALU_HEAD=1: the VALU form)
 // Taken when the workspace has room for the staged copies and the list (t2n_generic_workspace_bytes_desc); same outputs and context as
 // the plain form (the backward reads them), values equal to rounding (the density sums are bit-identical).
-struct GenFast {
-    const float* dp[3]; const float* dl[3]; const float* ap[3]; const float* al[3];   // channel-last copies
-    int* list; unsigned* count; unsigned cap;
-    int ncol;
-    const float* w0p; const float* w1p; int ld0, ld1;   // MLP weights with rows padded to multiples of 16 floats (64-byte aligned rows: s_load_dwordx16)
-    // MLP layers on the matrix cores (k_dense of t2n_heads.hip, exact-fp32 MFMA): the head kernel then only WRITES the input rows of
-    // one pass of the list — entries [row0, row0 + rows_cap) — to x0 [rows_cap][ldx]; k_gen_out finishes from h1
-    float* x0; int ldx; unsigned row0, rows_cap; HeadPlanDev* plan;
-    int hbc;   // columns of Hb (a multiple of 16): the head kernel's LDS staging of the input rows
-};
 __global__ __launch_bounds__(256) void k_gen_padrows(const float* __restrict__ src, float* __restrict__ dst, int rows, int n, int ld) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)rows * ld) return;
     const int r = (int)(t / ld), j = (int)(t - (long long)r * ld);
     dst[t] = j < n ? src[(size_t)r * n + j] : 0.f;
 }
-struct GenStageArgs { const float* src[12]; float* dst[12]; int C[12]; long long HW[12]; unsigned block0[13]; };
 __global__ __launch_bounds__(256) void k_gen_stage(const GenStageArgs a) {
     __shared__ float tile[64][65];
     int t = 0;
@@ -832,7 +740,7 @@ __global__ __launch_bounds__(256) void k_gen_out(const GenArgs a, const GenFast 
 
 // the scalars of a FieldDev from the descriptor (no factor sets), and the AlphaGridMask when the descriptor carries one: the same
 // fields t2n_field_set_alpha_mask fills, with the normalisation scale (1 / size) * 2 of AlphaGridMask.__init__ (models/tensorBase.py:46-47)
-static int gen_field(FieldDev& F, const t2n_generic_desc* d, const char* who) {
+int gen_field(FieldDev& F, const t2n_generic_desc* d, const char* who) {
     memset(&F, 0, sizeof(F));
     for (int k = 0; k < 3; ++k) { F.aabb0[k] = d->aabb_min[k]; F.aabb1[k] = d->aabb_max[k]; F.inv[k] = d->inv_aabb_size[k]; }
     F.shift = d->density_shift; F.dscale = d->distance_scale; F.thres = d->weight_thres; F.step = d->step_size;
@@ -848,7 +756,7 @@ static int gen_field(FieldDev& F, const t2n_generic_desc* d, const char* who) {
     return T2N_OK;
 }
 
-static int gen_fill(GenArgs& a, const t2n_generic_desc* d, const t2n_field_params* p, const char* who) {
+int gen_fill(GenArgs& a, const t2n_generic_desc* d, const t2n_field_params* p, const char* who) {
     if (!d || !p) { set_error("%s: NULL argument", who); return T2N_ERR_INVALID; }
     memset(&a, 0, sizeof(a));
     FieldDev& F = a.F;
@@ -880,8 +788,7 @@ static int gen_fill(GenArgs& a, const t2n_generic_desc* d, const t2n_field_param
     return T2N_OK;
 }
 
-struct GenCarve { size_t w, z, sigma, T, rgb_s, acc, raw, go, total; };
-static GenCarve gen_carve(int64_t R, int N, bool own_wz) {
+GenCarve gen_carve(int64_t R, int N, bool own_wz) {
     GenCarve c;
     size_t o = 0;
     const size_t rn = (size_t)R * N * 4;
@@ -892,10 +799,7 @@ static GenCarve gen_carve(int64_t R, int N, bool own_wz) {
     return c;
 }
 
-// staged (channel-last) factor copies + the appearance list behind the plain carve
-struct GenStageCarve { size_t t[12], list, count, w0p, w1p, plan, x0, h0, h1, total; unsigned rows_cap; int ldx, ldh; };
-constexpr long long kGenPassRows = 262144;   // list entries per pass of the matrix-core head (x0 + h0 + h1: 3.4 KB per row at 351 / 256 / 256)
-static GenStageCarve gen_stage_carve(const t2n_generic_desc* d, int64_t R, int N, size_t base) {
+GenStageCarve gen_stage_carve(const t2n_generic_desc* d, int64_t R, int N, size_t base) {
     GenStageCarve c;
     size_t o = (base + 255) / 256 * 256;
     for (int q = 0; q < 4; ++q)
@@ -930,7 +834,7 @@ static GenStageCarve gen_stage_carve(const t2n_generic_desc* d, int64_t R, int N
 }
 // rows_only: the kernel writes the input rows and leaves the layers to k_dense — Hb then holds the feature partials and the staging
 // rounds only (4 D columns rounded up to 16), which lets two workgroups share a CU's LDS (one wave per SIMD hid none of the gather's latency)
-static size_t gen_head_lds(const t2n_generic_desc* d, bool rows_only = false) {
+size_t gen_head_lds(const t2n_generic_desc* d, bool rows_only) {
     const size_t ncol = (size_t)d->app_n_comp[0] + d->app_n_comp[1] + d->app_n_comp[2], D = (size_t)d->app_dim;
     const size_t hb = rows_only ? (4 * D + 15) / 16 * 16 : (4 * D > (size_t)d->feature_c ? 4 * D : (size_t)d->feature_c);
     return (ncol * D + D * 64 + 16 * 64 + hb * 64) * sizeof(float);
@@ -959,6 +863,45 @@ __global__ __launch_bounds__(256) void k_gen_dense_alpha(const GenArgs a, const 
     alpha[p] = 1.f - expf((-sg) * length);
 }
 
+// the forward takes its kernel form when the head's LDS fits and T2N_GENERIC_PLAIN is not set (and the workspace has room, which the
+// caller of this predicate checks against ITS workspace)
+bool gen_forward_staged(const t2n_generic_desc* d) {
+    static const bool plain = getenv("T2N_GENERIC_PLAIN") && atoi(getenv("T2N_GENERIC_PLAIN")) != 0;
+    return !plain && gen_head_lds(d) <= 160 * 1024;
+}
+static int gen_head_attrs() {
+    static bool attr_set = false;
+    if (!attr_set) { T2N_HIP(hipFuncSetAttribute((const void*)k_gen_head, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                     T2N_HIP(hipFuncSetAttribute((const void*)k_gen_head_rows<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                     T2N_HIP(hipFuncSetAttribute((const void*)k_gen_head_rows<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; }
+    return T2N_OK;
+}
+void gen_fast_bind(GenFast& fa, const GenArgs& a, const GenStageCarve& sc, char* ws, long long tot) {
+    memset(&fa, 0, sizeof(fa));
+    for (int k = 0; k < 3; ++k) {
+        fa.dp[k] = (const float*)(ws + sc.t[k]); fa.dl[k] = (const float*)(ws + sc.t[3 + k]);
+        fa.ap[k] = (const float*)(ws + sc.t[6 + k]); fa.al[k] = (const float*)(ws + sc.t[9 + k]);
+    }
+    fa.list = (int*)(ws + sc.list); fa.count = (unsigned*)(ws + sc.count); fa.cap = (unsigned)tot; fa.ncol = a.Ca[0] + a.Ca[1] + a.Ca[2];
+}
+int launch_gen_head_pass(const GenArgs& a, GenFast fa, const t2n_generic_desc* desc, const GenStageCarve& sc, char* ws, long long row0,
+                         unsigned rows, hipStream_t s) {
+    if (!sc.x0 || rows == 0 || rows > sc.rows_cap || (rows & 63u)) { set_error("general-shape head pass: bad pass of %u rows", rows); return T2N_ERR_INVALID; }
+    int rc;
+    if ((rc = gen_head_attrs())) return rc;
+    fa.x0 = (float*)(ws + sc.x0); fa.ldx = sc.ldx; fa.rows_cap = rows; fa.plan = (HeadPlanDev*)(ws + sc.plan); fa.row0 = (unsigned)row0;
+    fa.hbc = (4 * a.app_dim + 15) / 16 * 16;
+    const size_t lds_rows = gen_head_lds(desc, true);
+    float* h0 = (float*)(ws + sc.h0); float* h1 = (float*)(ws + sc.h1);
+    const unsigned long long pt = ((unsigned long long)rows + 63) / 64;
+    if (a.app_dim <= 32) hipLaunchKernelGGL((k_gen_head_rows<32>), dim3((unsigned)(pt < 2048 ? pt : 2048)), dim3(256), lds_rows, s, a, fa);
+    else hipLaunchKernelGGL((k_gen_head_rows<64>), dim3((unsigned)(pt < 2048 ? pt : 2048)), dim3(256), lds_rows, s, a, fa);
+    if ((rc = launch_dense_rows(fa.x0, sc.ldx, a.w0, a.in0, a.fC, a.b0, 1, rows, h0, sc.ldh, s, fa.plan, row0))) return rc;
+    if ((rc = launch_dense_rows(h0, sc.ldh, a.w1, a.fC, a.fC, a.b1, 1, rows, h1, sc.ldh, s, fa.plan, row0))) return rc;
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
 }  // namespace t2n
 
 using namespace t2n;
@@ -975,7 +918,7 @@ extern "C" size_t t2n_generic_workspace_bytes(int64_t n_rays, int n_samples) {
     return gen_carve(n_rays, n_samples, true).total;
 }
 
-static int gen_bind(GenArgs& a, const float* rays, int64_t n_rays, int ray_stride, int n_samples, uint32_t flags, const float* jitter,
+int t2n::gen_bind(GenArgs& a, const float* rays, int64_t n_rays, int ray_stride, int n_samples, uint32_t flags, const float* jitter,
                     float* weights, float* z_vals, void* workspace, size_t workspace_bytes, const char* who) {
     if (!rays || !workspace || n_rays <= 0 || ray_stride < 6 || n_samples < 1) { set_error("%s: bad argument", who); return T2N_ERR_INVALID; }
     if ((flags & (T2N_FLAG_TRAIN | T2N_FLAG_NDC)) && !jitter) { set_error("%s: train / NDC mode needs the jitter draws / depth table", who); return T2N_ERR_INVALID; }
@@ -1007,8 +950,7 @@ extern "C" int t2n_generic_forward(const t2n_generic_desc* desc, const t2n_field
     const long long tot = (long long)n_rays * n_samples;
     const GenStageCarve sc = gen_stage_carve(desc, n_rays, n_samples, gen_carve(n_rays, n_samples, true).total);
     const size_t lds = gen_head_lds(desc);
-    static const bool plain = getenv("T2N_GENERIC_PLAIN") && atoi(getenv("T2N_GENERIC_PLAIN")) != 0;
-    if (!plain && sc.total <= workspace_bytes && lds <= 160 * 1024) {
+    if (gen_forward_staged(desc) && sc.total <= workspace_bytes) {
         char* ws = (char*)workspace;
         GenFast fa;
         GenStageArgs sa;
@@ -1041,10 +983,7 @@ extern "C" int t2n_generic_forward(const t2n_generic_desc* desc, const t2n_field
             hipLaunchKernelGGL(k_gen_compact, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, a, fa);
         } else
             hipLaunchKernelGGL(k_gen_scan_compact, dim3((unsigned)((n_rays + 3) / 4)), dim3(256), 0, s, a, fa);
-        static bool attr_set = false;
-        if (!attr_set) { T2N_HIP(hipFuncSetAttribute((const void*)k_gen_head, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                         T2N_HIP(hipFuncSetAttribute((const void*)k_gen_head_rows<32>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                         T2N_HIP(hipFuncSetAttribute((const void*)k_gen_head_rows<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; }
+        if ((rc = gen_head_attrs())) return rc;
         const unsigned long long wt = ((unsigned long long)tot + 63) / 64;
         fa.x0 = nullptr; fa.ldx = 0; fa.row0 = 0; fa.rows_cap = 0; fa.plan = nullptr; fa.hbc = 0;
         static const bool valu_head = getenv("T2N_GENERIC_VALU_HEAD") && atoi(getenv("T2N_GENERIC_VALU_HEAD")) != 0;

@@ -266,6 +266,8 @@ int launch_gemm_nn_h(void* packbuf, int which, int K0, const float* IN, int ldin
 int launch_gemm_tn_b(const float* A, int lda, const float* B, int ldb, long long rows, int N, float* part, int ldp, int chunk_rows,
                      int ng, int chunks, bool pe, float* db, hipStream_t s, const unsigned* rows_dev = nullptr);
 // MLP part of the render backward: fp32-MFMA GEMMs, layer 2, bias sums, positional encoding (t2n_bwd_mlp.hip)
+struct TnPlan { int chunk_rows, chunks, ng, ldp; };   // row chunks / 128-column groups / partial-slab stride of a weight-gradient GEMM
+TnPlan tn_plan(int64_t rows, int N);
 size_t tn_part_bytes(int64_t rows, int k0);   // partial-sum scratch of the weight-gradient GEMMs (and of layer 2) for `rows` rows
 bool gemm_fp32_mode(const t2n_field* f);
 void launch_bwd_l2(const float4* go, const float* h1, long long rows, const float* w2, float* g1, float* dw2, float* db2, float* scratch,

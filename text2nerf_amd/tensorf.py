@@ -550,9 +550,10 @@ class TensorBase(nn.Module):
     GENERAL_DIM, GENERAL_FC, GENERAL_PE = 64, 256, 16     # limits of the general-shape path (csrc/t2n_generic.hip)
 
     def _is_general(self):
-        """Shapes BEYOND the tuned kernels' (more components per plane, a wider head): rendered and differentiated by the general-shape
-        kernels (csrc/t2n_generic.hip: loops over the counts, reference layouts read in place) — slow, but not an error. Fixed at
-        construction."""
+        """Shapes BEYOND the tuned kernels' (more components per plane, a wider head): rendered, differentiated and trained
+        (`train_step`, composed) by the general-shape kernels (csrc/t2n_generic.hip forward, csrc/t2n_generic_bwd.hip backward; the
+        plain per-ray / per-sample forms remain for heads above 512 inputs or 160 KB of LDS) — slower than the tuned path, but not an
+        error. Fixed at construction."""
         flag = self.__dict__.get("_general_flag")
         if flag is None:
             wide_head = False
@@ -578,8 +579,8 @@ class TensorBase(nn.Module):
     def _kernel_shape(self):
         """(density comps, appearance comps, app_dim, fea_pe, featureC) the native field is created with."""
         if self._is_general():
-            raise T2NError("this field's shape runs on the general-shape path (forward / backward through the render call only: no native "
-                           "field handle, hence no stage entry points, occupancy-mask operators or train_step)")
+            raise T2NError("this field's shape runs on the general-shape path (render, backward and train_step on its own kernels: no native "
+                           "field handle, hence no stage entry points and no one-call fused step)")
         if self.shadingMode == "MLP_Fea_noview":
             if self.fea_pe < 0:
                 raise T2NError(f"fea_pe {self.fea_pe}")
@@ -1381,11 +1382,93 @@ class TensorBase(nn.Module):
         d = self._general_desc()
         st = self._param_struct([p.detach() for p in ps])
         gs = self._param_struct(grads, _lib.FieldGrads)
+        plan = self._general_plan(d, R, N)
         with torch.cuda.device(dev):
-            _lib.check(lib.t2n_generic_backward(C.byref(d), C.byref(st), _lib.ptr(rays), R, rays.shape[1], N, flags, _lib.ptr(jitter),
-                                                _lib.ptr(w), _lib.ptr(z), _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w), C.byref(gs),
-                                                _lib.ptr(ws), ws.numel(), _lib.current_stream_ptr(dev)), "t2n_generic_backward")
+            if plan.kernel_form:
+                # the backward as kernels (csrc/t2n_generic_bwd.hip): scratch from the shared grow-only buffer, like the tuned backward's
+                bws = workspace(dev, int(plan.workspace_bytes))
+                _lib.check(lib.t2n_generic_backward_staged(C.byref(d), C.byref(st), _lib.ptr(rays), R, rays.shape[1], N, flags, _lib.ptr(jitter),
+                                                           _lib.ptr(w), _lib.ptr(z), _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w),
+                                                           C.byref(gs), _lib.ptr(ws), ws.numel(), _lib.ptr(bws), bws.numel(),
+                                                           self._general_pass_rows(), _lib.current_stream_ptr(dev)),
+                           "t2n_generic_backward_staged")
+            else:
+                _lib.check(lib.t2n_generic_backward(C.byref(d), C.byref(st), _lib.ptr(rays), R, rays.shape[1], N, flags, _lib.ptr(jitter),
+                                                    _lib.ptr(w), _lib.ptr(z), _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w), C.byref(gs),
+                                                    _lib.ptr(ws), ws.numel(), _lib.current_stream_ptr(dev)), "t2n_generic_backward")
         return grads
+
+    general_backward_pass_rows = None     # appearance-list entries per head pass of the general-shape backward (None: 262 144)
+
+    def _general_pass_rows(self):
+        v = self.general_backward_pass_rows
+        if v is None:
+            return 0
+        v = int(v)
+        if v < 1 or v > 0x7fffffc0:
+            raise T2NError(f"general_backward_pass_rows {v}: a positive row count (it is rounded up to a multiple of 64)")
+        return (v + 63) // 64 * 64
+
+    def _general_plan(self, d, R, N):
+        plan = _lib.GenericBwdPlan()
+        _lib.check(_lib.load().t2n_generic_backward_plan(C.byref(d), int(R), int(N), self._general_pass_rows(), C.byref(plan)),
+                   "t2n_generic_backward_plan")
+        return plan
+
+    def general_backward_plan(self, R, N):
+        """How the general-shape backward of an R-ray, N-sample call runs (t2n_generic_backward_plan; host only): kernel_form 1 = the
+        kernels of csrc/t2n_generic_bwd.hip, 0 = the plain form; pass_rows / max_passes: the head's passes over the appearance list
+        (bounded by `general_backward_pass_rows`); workspace_bytes: the backward's scratch."""
+        if not self._is_general():
+            raise T2NError("general_backward_plan: this field runs on the tuned path")
+        plan = self._general_plan(self._general_desc(), R, N)
+        return {"kernel_form": int(plan.kernel_form), "pass_rows": int(plan.pass_rows), "max_passes": int(plan.max_passes),
+                "workspace_bytes": int(plan.workspace_bytes)}
+
+    def _general_train_step(self, rays, rgb_target, depth_target, optimizer, N_samples, white_bg, w_depth, w_trans, delta, tv, all_reduce,
+                            kind, depth_std):
+        """train_step on a general-shape field, composed: _general_forward (train mode) -> t2n_train_loss[_ex] -> _general_backward ->
+        .grad in the reference layouts -> all_reduce -> optimizer.step. The field's AlphaGridMask is honoured (the general kernels test
+        it themselves)."""
+        lib = _lib.load()
+        params = self._real_params()
+        dev = self.basis_mat.weight.device
+        R = rays.shape[0]
+        N = int(N_samples) if N_samples > 0 else self.nSamples
+        rays, jitter, rgb_t, dep_t = to_device_async_many([rays, torch.rand(R, 1), rgb_target, depth_target], dev)
+        if rays.dtype != torch.float32 or not rays.is_contiguous():
+            rays = rays.contiguous().float()
+        jitter = jitter.reshape(-1).contiguous()
+        flags = FLAG_TRAIN | (FLAG_ADD_BG if (white_bg or bool(torch.rand((1,)) < 0.5)) else 0)
+        rgb_t = rgb_t.contiguous().float()
+        dep_t = dep_t.contiguous().float()
+        with torch.no_grad():
+            rgb, depth, z, w, ws = self._general_forward(rays, N, flags, jitter)
+            d_rgb, d_depth, d_w = torch.empty_like(rgb), torch.empty_like(depth), torch.empty_like(w)
+            losses = torch.empty(4, device=dev)
+            st = _lib.current_stream_ptr(dev)
+            if kind == 0:
+                lws = torch.empty(int(lib.t2n_train_loss_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.t2n_train_loss(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
+                                                  float(w_depth), float(w_trans), float(delta), _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w),
+                                                  _lib.ptr(losses), _lib.ptr(lws), lws.numel(), st), "t2n_train_loss")
+            else:
+                lws = torch.empty(int(lib.t2n_train_loss_ex_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+                aux = torch.empty(4, dtype=torch.float64, device=dev)
+                with torch.cuda.device(dev):
+                    _lib.check(lib.t2n_train_loss_ex(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
+                                                     float(w_depth), float(w_trans), float(delta), kind, float(depth_std), _lib.ptr(d_rgb),
+                                                     _lib.ptr(d_depth), _lib.ptr(d_w), _lib.ptr(losses), _lib.ptr(aux), _lib.ptr(lws), lws.numel(),
+                                                     st), "t2n_train_loss_ex")
+                self.__dict__["last_depth_aux"] = aux
+            grads = self._general_backward(rays, jitter, N, flags, ws, w, z, d_rgb, d_depth, d_w)
+            for p, g in zip(params, grads):
+                p.grad = g
+            if all_reduce is not None:
+                all_reduce()
+            optimizer.step(tv=tv) if tv else optimizer.step()
+        return losses
 
     def train_step(self, rays, rgb_target, depth_target, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
                    tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None, depth_loss="mse",
@@ -1415,7 +1498,11 @@ class TensorBase(nn.Module):
         (compute_depth_loss_scale_invariant) or "ssi" (scale_shift_invariant_loss) — t2n_train_loss_ex. The returned tensor keeps its
         layout [mse, depth term, transmittance loss, mse + w_depth * term + w_trans * transmittance]; `self.last_depth_aux` is the
         call's device float64 tensor of the term's coupling scalars (gnll: K, signed mean NLL; si_log: alpha; ssi: s, t; None for
-        "mse"). The one-call step has the mse term folded in: any other kind takes the composed route, and `fused=True` with it raises."""
+        "mse"). The one-call step has the mse term folded in: any other kind takes the composed route, and `fused=True` with it raises.
+        A general-shape field (`_is_general`) takes the composed route on its own kernels — t2n_generic_forward, the loss kernel,
+        t2n_generic_backward[_staged], the gradients installed as `.grad` in the reference layouts — with optim.TVAdam WITHOUT `field=`
+        (or any torch.optim optimiser when `tv` is empty); its AlphaGridMask is honoured; `fused=True` raises, `speculative` and `graph`
+        have no effect."""
         lib = _lib.load()
         params = self._autograd_params()
         kind = _depth_kind(depth_loss)
@@ -1424,6 +1511,9 @@ class TensorBase(nn.Module):
         if fuse is not None:
             fs, N, flags, use_graph = fuse
             return fs.step(rays, rgb_target, depth_target, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce)
+        if self._is_general():     # (speculative / graph: forms of the tuned backward and of the one-call step, no effect here)
+            return self._general_train_step(rays, rgb_target, depth_target, optimizer, N_samples, white_bg, w_depth, w_trans, delta, tv,
+                                            all_reduce, kind, depth_std)
         if any(not p.is_leaf for p in params):
             raise T2NError("train_step needs the kernels' own field shape (the parameters ARE the kernel tensors); embedded shapes, "
                            "TensorVM and TensorCP train through the autograd form (OctreeRender_trilinear_fast + loss.backward())")
