@@ -68,6 +68,9 @@ enum {
                                * t2n_train_step) */
     T2N_FLAG_GATHER_BATCH = 128u, /* t2n_train_step only: the batch is gathered from the field's training source by row index
                                * (t2n_field_set_train_source): rays / rgb_target / depth_target of the call are DESTINATIONS */
+    T2N_FLAG_REG_L1 = 256u,    /* t2n_train_step only: hyper[21] / hyper[22] hold this step's L1 weights (density planes / density lines) */
+    T2N_FLAG_REG_ORTHO = 512u, /* t2n_train_step only: hyper[23] / hyper[24] hold this step's ortho weights (density / appearance lines); the
+                               * call then issues the two ortho launches behind its seed */
     T2N_FLAG_COHERENT = 8u    /* hint (eval): rays are a row-major image whose width was given by t2n_field_set_frame_width:
                                  march 8x8-pixel tiles whose rays share one texel x line-row dot-product table per step
                                  (f32 matrix cores). Same samples; the density feature is summed in table order and the
@@ -614,6 +617,39 @@ int t2n_field_tv_adam_step(t2n_field* f, const t2n_field_params* params, float* 
  * depends on nothing but the parameters: it may run on another stream beside the forward; the backward must be ordered behind it.
  * Replaces (reference): the autograd of TV_loss_density / TV_loss_app (models/tensoRF.py:193-203, text2nerf_main.py:577-586). */
 int t2n_field_tv_seed(t2n_field* f, float tv_weight_density, float tv_weight_app, t2n_stream stream);
+
+/* ---- TensoRF's other two parameter regularisers (models/tensoRF.py:173-191; csrc/t2n_reg.hip).
+ * L1 (density_L1 = sum_k mean|density_plane[k]| + mean|density_line[k]|), one contiguous tensor of n floats at a time:
+ *   t2n_l1_value     sums[0 .. T2N_REG_SLOTS) = partial sums of |param| / n (float64, WRITTEN; the caller adds them: that is mean|param|)
+ *   t2n_l1_grad_add  grad += float32(weight / n) * sign(param), sign(+-0) = 0
+ *   t2n_l1_grad_set  grad  = float32(weight / n) [* *upstream, a device scalar, when non-NULL] * sign(param)
+ * Ortho (vector_comp_diffs), one reference-layout line tensor [1,C,n,1] read as M [C,n], C >= 2 (T2N_ERR_INVALID below):
+ *   D = M M^T in float64 in a fixed order (kept in `workspace`: t2n_ortho_workspace_bytes(C) = C * C * 8 bytes, 8-byte aligned)
+ *   t2n_ortho_value     *value = sum_{i != j} |D_ij| / (C (C - 1))  (one device double, written)
+ *   t2n_ortho_grad_add  grad += weight * 2 / (C (C - 1)) * S M, S_ij = sign(D_ij) off the diagonal, 0 on it (float32 sum over j in order)
+ *   t2n_ortho_grad_set  the same WRITTEN, times *upstream when non-NULL
+ * No atomics anywhere: two calls on the same input give the same bits. */
+#define T2N_REG_SLOTS 64
+int t2n_l1_value(const float* param, int64_t n, double* sums, t2n_stream stream);
+int t2n_l1_grad_add(const float* param, float* grad, int64_t n, float weight, t2n_stream stream);
+int t2n_l1_grad_set(const float* param, float* grad, int64_t n, float weight, const float* upstream, t2n_stream stream);
+size_t t2n_ortho_workspace_bytes(int C);
+int t2n_ortho_value(const float* param, int C, int64_t n, double* value, void* workspace, size_t workspace_bytes, t2n_stream stream);
+int t2n_ortho_grad_add(const float* param, float* grad, int C, int64_t n, float weight, void* workspace, size_t workspace_bytes,
+                       t2n_stream stream);
+int t2n_ortho_grad_set(const float* param, float* grad, int C, int64_t n, float weight, const float* upstream, void* workspace,
+                       size_t workspace_bytes, t2n_stream stream);
+/* t2n_field_tv_seed / t2n_field_tv_adam_step with the two terms on the field's channel-last copies: L1 on the density planes
+ * (l1_weight_plane) and density lines (l1_weight_line) inside the seed / TV launch — the planes are read and written once, the lines
+ * are written with their L1 gradient instead of zero; ortho on the three density lines and the three appearance lines as two more
+ * launches for all six (Gram, gradient) behind it on the same stream. Per element the arithmetic of the reference-layout calls above, in
+ * the order TV, L1, ortho (bit-identical). With the four new weights 0 these ARE the tv calls. */
+int t2n_field_reg_seed(t2n_field* f, float tv_weight_density, float tv_weight_app, float l1_weight_plane, float l1_weight_line,
+                       float ortho_weight_density, float ortho_weight_app, t2n_stream stream);
+int t2n_field_reg_adam_step(t2n_field* f, const t2n_field_params* params, float* const* exp_avg, float* const* exp_avg_sq,
+                            const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
+                            float tv_weight_density, float tv_weight_app, float l1_weight_plane, float l1_weight_line,
+                            float ortho_weight_density, float ortho_weight_app, t2n_stream stream);
 /* re-pack basis_mat / renderModule only (the factor copies of an uploaded field are left as they are) */
 int t2n_field_upload_head(t2n_field* f, const t2n_field_params* p, t2n_stream stream);
 

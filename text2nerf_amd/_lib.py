@@ -19,6 +19,8 @@ FLAG_TRAIN, FLAG_ADD_BG, FLAG_KEEP_CTX, FLAG_COHERENT, FLAG_NDC = 1, 2, 4, 8, 16
 FLAG_DEVICE_ROWS = 32
 FLAG_PIPELINE = 64
 FLAG_GATHER_BATCH = 128
+FLAG_REG_L1, FLAG_REG_ORTHO = 256, 512
+REG_SLOTS = 64
 SHADE_IDS = {"MLP_Fea_noview": 0, "SH": 1, "RGB": 2, "MLP_Fea": 3, "MLP_PE": 4, "MLP": 5}   # MLP_PE: rejected in tensorf.py (broken upstream)
 ACT_IDS = {"softplus": 0, "relu": 1}
 DEPTH_KINDS = {"mse": 0, "gnll": 1, "si_log": 2, "ssi": 3}   # depth_kind of t2n_train_loss_ex / t2n_depth_loss
@@ -217,6 +219,17 @@ SIGNATURES = {
     "t2n_field_tv_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                          C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "t2n_field_tv_seed": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_void_p]),
+    "t2n_l1_value": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "t2n_l1_grad_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "t2n_l1_grad_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p]),
+    "t2n_ortho_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "t2n_ortho_value": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_ortho_grad_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_ortho_grad_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
+    "t2n_field_reg_seed": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "t2n_field_reg_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                          C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "t2n_field_upload_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "t2n_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_int64, C.c_void_p]),

@@ -436,6 +436,7 @@ extern "C" int t2n_field_destroy(t2n_field* f) {
     if (f->gbuf_all && !f->gbuf_external) (void)hipFree(f->gbuf_all);
     if (f->buf_mlp) (void)hipFree(f->buf_mlp);
     if (f->staging_counts) (void)hipFree(f->staging_counts);
+    if (f->reg_ws) (void)hipFree(f->reg_ws);
     if (f->buf_mlp_h) (void)hipFree(f->buf_mlp_h);
     if (f->buf_ss) (void)hipFree(f->buf_ss);
     if (f->ss_event) (void)hipEventDestroy((hipEvent_t)f->ss_event);
@@ -482,6 +483,11 @@ extern "C" int t2n_field_upload(t2n_field* f, const t2n_field_params* p, t2n_str
     if (!rc) rc = launch_pack_mlp(f, p, s);
     timing_end(f, T2N_K_UPLOAD, s);
     if (rc) return rc;
+    if (f->reg_ws_bytes < reg_ws_bytes(f)) {   // the ortho regulariser's Gram matrices (t2n_reg.hip): here, so that no training step allocates
+        if (f->reg_ws) { T2N_HIP(hipDeviceSynchronize()); (void)hipFree(f->reg_ws); f->reg_ws = nullptr; f->reg_ws_bytes = 0; }
+        T2N_HIP(hipMalloc(&f->reg_ws, reg_ws_bytes(f)));
+        f->reg_ws_bytes = reg_ws_bytes(f);
+    }
     f->params_ref = *p;
     f->ss_dirty = true;
     f->train_packed = false;

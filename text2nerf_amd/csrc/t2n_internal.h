@@ -143,6 +143,7 @@ struct t2n_field {
     t2n_train_source train_src = {}; bool train_src_set = false;   // T2N_FLAG_GATHER_BATCH: where the device-resident training set is
     bool train_src_fresh = false;    // its pointers / n_rows changed since the last gathering step (that step's early part goes behind the caller's stream)
     unsigned list_hint = 0;          // appearance entries per ray of the last budgeted launch (0: unknown)
+    void* reg_ws = nullptr; size_t reg_ws_bytes = 0;   // ortho regulariser: the six lines' float64 Gram matrices (t2n_reg.hip), allocated by the first upload
     unsigned long long list_retries = 0;
 };
 
@@ -292,7 +293,10 @@ int launch_mlp_bwd_ss(t2n_field* f, void* packbuf, const float4* go, float* h1, 
 int mlp_bwd_ss_pack(t2n_field* f, void* packbuf, hipStream_t s, bool zeroed, bool one_launch = false, bool absmax_done = false);   // one_launch: the pack kernel finds the matrices' largest magnitudes itself
 void* mlp_bwd_ss_absmax_words(void* packbuf);
 // the fused training step's optimiser launches (t2n_optim.hip): scalars / TV weights / verdict from device memory
-int launch_tv_seed_dev(t2n_field* f, const float* tvw_dev, hipStream_t s, int world = 1, int rank = 0);
+int launch_tv_seed_dev(t2n_field* f, const float* tvw_dev, hipStream_t s, int world = 1, int rank = 0, bool l1_dev = false);   // l1_dev: tvw_dev[2..3] hold the step's L1 weights (density planes, density lines)
+// ortho regulariser of the six line tensors, added to the gradient buffer (t2n_reg.hip): weights by value, or both from device memory (w_dev)
+int launch_ortho_lines(t2n_field* f, float w_den, float w_app, const float* w_dev, hipStream_t s);
+size_t reg_ws_bytes(const t2n_field* f);     // the Gram buffer those launches use: allocated by the field's first upload
 int launch_factor_adam_dev(t2n_field* f, const t2n_field_params* params, float* const* m, float* const* v, float beta1, float beta2, float eps,
                            const TrainScalars* st, int first, int count, hipStream_t s, int world = 1, int rank = 0, bool relayout_only = false);
 void shard_partition(const t2n_field* f, int world, int rank, unsigned lo[12], unsigned hi[12], unsigned body[12]);

@@ -115,9 +115,16 @@ __global__ __launch_bounds__(256) void k_adam_multi(const AdamMulti a) {
 // thing where the data already is: TV stencil on the channel-last parameters (neighbours at +-C and +-W*C), then one pass
 // that reads g / m / v / p channel-last, writes p / m / v channel-last and the new values into the caller's reference-layout
 // tensor through an LDS tile transpose. Same arithmetic per element as k_tv_grad + k_adam (bit-identical results).
+// the L1 term of t2n_reg.hip on a channel-last float4: s with the sign of each element, 0 for +-0 (on the bits: denormals count)
+__device__ __forceinline__ float l1_one(float v, float s) {
+    const unsigned u = __float_as_uint(v);
+    return (u << 1) == 0u ? 0.f : __uint_as_float(__float_as_uint(s) ^ (u & 0x80000000u));
+}
+// l1 (weight / numel, 0 = none): the L1 gradient of t2n_reg.hip added behind the TV term, in the order of the reference-layout calls
+// (t2n_tv_grad_add / _set, then t2n_l1_grad_add); a line tensor (W = 1, sh = sw = 0) carries the L1 term alone
 template <bool SET>
 __device__ __forceinline__ void tv_grad_cl_body(const float* __restrict__ x, float* __restrict__ g, long long t, int C4, int H, int W, float sh,
-                                                float sw) {
+                                                float sw, float l1 = 0.f) {
     const long long n = (long long)H * W * C4;   // t: one float4 of 4 channels
     if (t >= n) return;
     const long long pos = t / C4;
@@ -134,13 +141,14 @@ __device__ __forceinline__ void tv_grad_cl_body(const float* __restrict__ x, flo
     if (SET) { G[t] = acc; return; }   // the gradient buffer STARTS as the TV gradient (t2n_field_tv_seed)
     float4 gv = G[t];
     gv.x += acc.x; gv.y += acc.y; gv.z += acc.z; gv.w += acc.w;
+    if (l1 != 0.f) { gv.x += l1_one(v.x, l1); gv.y += l1_one(v.y, l1); gv.z += l1_one(v.z, l1); gv.w += l1_one(v.w, l1); }
     G[t] = gv;
 }
 
 // the same stencil with 32-bit index arithmetic (a factor tensor has < 2^31 float4 elements; checked by the launcher): the 64-bit
 // divisions of the form above are ~150 of the seed kernel's instructions per thread, on a kernel that moves 32 bytes per thread
 __device__ __forceinline__ void tv_seed_cl_body32(const float* __restrict__ x, float* __restrict__ g, unsigned t, unsigned C4, unsigned H, unsigned W, float sh,
-                                                  float sw) {
+                                                  float sw, float l1) {
     const unsigned n = H * W * C4;
     if (t >= n) return;
     const unsigned pos = C4 == 4u ? (t >> 2) : (C4 == 12u ? t / 12u : t / C4);
@@ -153,6 +161,7 @@ __device__ __forceinline__ void tv_seed_cl_body32(const float* __restrict__ x, f
     if (h < H - 1) { const float4 d = X[t + row]; acc.x -= sh * (2.f * (d.x - v.x)); acc.y -= sh * (2.f * (d.y - v.y)); acc.z -= sh * (2.f * (d.z - v.z)); acc.w -= sh * (2.f * (d.w - v.w)); }
     if (w > 0) { const float4 l = X[t - C4]; acc.x += sw * (2.f * (v.x - l.x)); acc.y += sw * (2.f * (v.y - l.y)); acc.z += sw * (2.f * (v.z - l.z)); acc.w += sw * (2.f * (v.w - l.w)); }
     if (w < W - 1) { const float4 r = X[t + C4]; acc.x -= sw * (2.f * (r.x - v.x)); acc.y -= sw * (2.f * (r.y - v.y)); acc.z -= sw * (2.f * (r.z - v.z)); acc.w -= sw * (2.f * (r.w - v.w)); }
+    if (l1 != 0.f) { acc.x += l1_one(v.x, l1); acc.y += l1_one(v.y, l1); acc.z += l1_one(v.z, l1); acc.w += l1_one(v.w, l1); }
     reinterpret_cast<float4*>(g)[t] = acc;
 }
 
@@ -208,7 +217,9 @@ struct FactorStep {
     long long npos[12];
     int C[12], H[12], W[12];
     float sh[12], sw[12], lr_over_bc1[12], inv_bc2_sqrt[12];
-    unsigned ablock0[13], tblock0[13];   // first workgroup of tensor t in the Adam / TV launch (TV: zero-width for lines and weight 0)
+    float l1[12];        // L1 weight / numel per tensor (0: none; the launches then take the paths they took without the term)
+    int l1_dev;          // fused training step: tvw_dev[2], tvw_dev[3] are this step's L1 weights of the density planes / density lines
+    unsigned ablock0[13], tblock0[13];   // first workgroup of tensor t in the Adam / TV launch (TV: zero-width for a tensor with neither a TV nor an L1 weight)
     float beta1, beta2, eps;
     // fused training step (NULL: by value): Adam scalars + verdict; the two TV weights (x 1e-2) of this step in device memory
     const TrainScalars* st; const float* tvw_dev;
@@ -224,7 +235,7 @@ __global__ __launch_bounds__(256) void k_tv_grad_cl_multi(const FactorStep a) {
 #pragma unroll 1
     for (int q = 1; q < 12; ++q) t += (a.tblock0[q] <= blockIdx.x) ? 1 : 0;
     const long long i = (long long)(blockIdx.x - a.tblock0[t]) * 256 + threadIdx.x;
-    tv_grad_cl_body<false>(a.p[t], a.g[t], i, a.C[t] / 4, a.H[t], a.W[t], a.sh[t], a.sw[t]);
+    tv_grad_cl_body<false>(a.p[t], a.g[t], i, a.C[t] / 4, a.H[t], a.W[t], a.sh[t], a.sw[t], a.l1[t]);
 }
 // every factor gradient tensor initialised: the TV gradient where a tensor has a TV weight, zero elsewhere (tblock0 spans all 12)
 __global__ __launch_bounds__(256) void k_tv_seed_cl_multi(const FactorStep a) {
@@ -250,7 +261,18 @@ __global__ __launch_bounds__(256) void k_tv_seed_cl_multi(const FactorStep a) {
             else { sh = 0.f; sw = 0.f; }
         }
     }
-    if (sh != 0.f || sw != 0.f) tv_seed_cl_body32(a.p[t], a.g[t], i32, (unsigned)a.C[t] / 4u, (unsigned)a.H[t], (unsigned)a.W[t], sh, sw);
+    float l1 = a.l1[t];
+    if (a.l1_dev) {    // the host's expression (factor_step_l1), on this step's weights; density tensors only
+        const float w = t < 3 ? a.tvw_dev[2] : (t < 6 ? a.tvw_dev[3] : 0.f);
+        l1 = w != 0.f ? (float)((double)w / ((double)a.npos[t] * (double)a.C[t])) : 0.f;
+    }
+    if (sh != 0.f || sw != 0.f) tv_seed_cl_body32(a.p[t], a.g[t], i32, (unsigned)a.C[t] / 4u, (unsigned)a.H[t], (unsigned)a.W[t], sh, sw, l1);
+    else if (l1 != 0.f) {   // no TV on this tensor (a line, or a plane without a TV weight): the buffer starts as the L1 gradient
+        if (i < a.npos[t] * (a.C[t] / 4)) {
+            const float4 v = reinterpret_cast<const float4*>(a.p[t])[i];
+            reinterpret_cast<float4*>(a.g[t])[i] = make_float4(l1_one(v.x, l1), l1_one(v.y, l1), l1_one(v.z, l1), l1_one(v.w, l1));
+        }
+    }
     else if (i < a.npos[t] * (a.C[t] / 4)) reinterpret_cast<float4*>(a.g[t])[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 __global__ __launch_bounds__(256) void k_adam_cl_multi(const FactorStep a) {
@@ -276,15 +298,22 @@ __global__ __launch_bounds__(256) void k_adam_cl_multi(const FactorStep a) {
 
 using namespace t2n;
 
-extern "C" int t2n_field_tv_adam_step(t2n_field* f, const t2n_field_params* params, float* const* exp_avg, float* const* exp_avg_sq,
-                                      const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
-                                      float tv_weight_density, float tv_weight_app, t2n_stream stream) {
-    if (!f || !params || !exp_avg || !exp_avg_sq || !lrs || !steps) { set_error("t2n_field_tv_adam_step: NULL argument"); return T2N_ERR_INVALID; }
+// L1 weight / numel of factor tensor idx (order: density planes, density lines, appearance planes, appearance lines): density tensors only
+static float factor_step_l1(int idx, long long numel, float l1_plane, float l1_line) {
+    const float w = idx < 3 ? l1_plane : (idx < 6 ? l1_line : 0.f);
+    return w != 0.f ? (float)((double)w / (double)numel) : 0.f;
+}
+
+// t2n_field_tv_adam_step / t2n_field_reg_adam_step (`who`): the L1 increment rides in the TV launch, the ortho term takes two launches of its own
+static int field_adam_step(const char* who, t2n_field* f, const t2n_field_params* params, float* const* exp_avg, float* const* exp_avg_sq,
+                           const float* lrs, const int64_t* steps, float beta1, float beta2, float eps, float tv_weight_density,
+                           float tv_weight_app, float l1_plane, float l1_line, float ortho_den, float ortho_app, t2n_stream stream) {
+    if (!f || !params || !exp_avg || !exp_avg_sq || !lrs || !steps) { set_error("%s: NULL argument", who); return T2N_ERR_INVALID; }
     if (!f->uploaded || !f->gbuf_den_plane[0]) {
-        set_error("t2n_field_tv_adam_step: needs an uploaded field and the gradients of a t2n_render_backward call");
+        set_error("%s: needs an uploaded field and the gradients of a t2n_render_backward call", who);
         return T2N_ERR_INVALID;
     }
-    if (f->factor_bf16) { set_error("t2n_field_tv_adam_step: bf16 factor storage keeps no fp32 master copy on the device"); return T2N_ERR_UNSUPPORTED; }
+    if (f->factor_bf16) { set_error("%s: bf16 factor storage keeps no fp32 master copy on the device", who); return T2N_ERR_UNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
     const int* gr = f->desc.grid;
     FactorStep A;
@@ -303,16 +332,17 @@ extern "C" int t2n_field_tv_adam_step(t2n_field* f, const t2n_field_params* para
             const int C = q < 2 ? 16 : 48;
             const bool plane = (q & 1) == 0;
             const float tvw = q == 0 ? tv_weight_density : (q == 2 ? tv_weight_app : 0.f);
-            if (!pref[q] || !exp_avg[idx] || !exp_avg_sq[idx] || steps[idx] < 1) { set_error("t2n_field_tv_adam_step: bad tensor %d", idx); return T2N_ERR_INVALID; }
+            if (!pref[q] || !exp_avg[idx] || !exp_avg_sq[idx] || steps[idx] < 1) { set_error("%s: bad tensor %d", who, idx); return T2N_ERR_INVALID; }
             A.p[idx] = pcl[q]; A.g[idx] = gcl[q]; A.m[idx] = exp_avg[idx]; A.v[idx] = exp_avg_sq[idx]; A.ref[idx] = pref[q];
             A.npos[idx] = plane ? HW : L; A.C[idx] = C; A.H[idx] = plane ? H : (int)L; A.W[idx] = plane ? W : 1;
             A.tblock0[idx] = tb;
+            A.l1[idx] = factor_step_l1(idx, A.npos[idx] * C, l1_plane, l1_line);
             if (tvw != 0.f) {
-                if (H < 2 || W < 2) { set_error("t2n_field_tv_adam_step: TV needs planes of at least 2x2"); return T2N_ERR_INVALID; }
+                if (H < 2 || W < 2) { set_error("%s: TV needs planes of at least 2x2", who); return T2N_ERR_INVALID; }
                 A.sh[idx] = tvw * 2.f / ((float)C * (float)(H - 1) * (float)W);
                 A.sw[idx] = tvw * 2.f / ((float)C * (float)H * (float)(W - 1));
-                tb += (unsigned)((HW * (C / 4) + 255) / 256);
             }
+            if (tvw != 0.f || A.l1[idx] != 0.f) tb += (unsigned)((A.npos[idx] * (C / 4) + 255) / 256);
             const double bc1 = 1.0 - pow((double)beta1, (double)steps[idx]), bc2 = 1.0 - pow((double)beta2, (double)steps[idx]);
             A.lr_over_bc1[idx] = (float)((double)lrs[idx] / bc1);
             A.inv_bc2_sqrt[idx] = (float)(1.0 / sqrt(bc2));
@@ -321,19 +351,35 @@ extern "C" int t2n_field_tv_adam_step(t2n_field* f, const t2n_field_params* para
         }
     A.tblock0[12] = tb; A.ablock0[12] = ab;
     if (tb) hipLaunchKernelGGL(k_tv_grad_cl_multi, dim3(tb), dim3(256), 0, s, A);
+    if (ortho_den != 0.f || ortho_app != 0.f) { const int rc = launch_ortho_lines(f, ortho_den, ortho_app, nullptr, s); if (rc) return rc; }
     hipLaunchKernelGGL(k_adam_cl_multi, dim3(ab), dim3(256), 0, s, A);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
+}
+
+extern "C" int t2n_field_tv_adam_step(t2n_field* f, const t2n_field_params* params, float* const* exp_avg, float* const* exp_avg_sq,
+                                      const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
+                                      float tv_weight_density, float tv_weight_app, t2n_stream stream) {
+    return field_adam_step("t2n_field_tv_adam_step", f, params, exp_avg, exp_avg_sq, lrs, steps, beta1, beta2, eps, tv_weight_density, tv_weight_app,
+                           0.f, 0.f, 0.f, 0.f, stream);
+}
+extern "C" int t2n_field_reg_adam_step(t2n_field* f, const t2n_field_params* params, float* const* exp_avg, float* const* exp_avg_sq,
+                                       const float* lrs, const int64_t* steps, float beta1, float beta2, float eps,
+                                       float tv_weight_density, float tv_weight_app, float l1_weight_plane, float l1_weight_line,
+                                       float ortho_weight_density, float ortho_weight_app, t2n_stream stream) {
+    return field_adam_step("t2n_field_reg_adam_step", f, params, exp_avg, exp_avg_sq, lrs, steps, beta1, beta2, eps, tv_weight_density, tv_weight_app,
+                           l1_weight_plane, l1_weight_line, ortho_weight_density, ortho_weight_app, stream);
 }
 
 // The factor gradient buffer of the next backward call initialised to the TV gradient of the CURRENT device copies (zero for the
 // lines and for a zero weight) instead of being zero-filled and TV-incremented after the backward: one pass that only writes the
 // buffer, and one that may run on another stream beside the forward (it reads the parameters the forward reads and nothing else).
 // Same per-element arithmetic as the TV pass of t2n_field_tv_adam_step; the scatter kernels then accumulate on top.
-extern "C" int t2n_field_tv_seed(t2n_field* f, float tv_weight_density, float tv_weight_app, t2n_stream stream) {
-    if (!f) { set_error("t2n_field_tv_seed: NULL field"); return T2N_ERR_INVALID; }
-    if (!f->uploaded || !f->gbuf_den_plane[0]) { set_error("t2n_field_tv_seed: needs an uploaded field with a gradient buffer"); return T2N_ERR_INVALID; }
-    if (f->factor_bf16) { set_error("t2n_field_tv_seed: bf16 factor storage keeps no fp32 master copy on the device"); return T2N_ERR_UNSUPPORTED; }
+static int field_seed(const char* who, t2n_field* f, float tv_weight_density, float tv_weight_app, float l1_plane, float l1_line, float ortho_den,
+                      float ortho_app, t2n_stream stream) {
+    if (!f) { set_error("%s: NULL field", who); return T2N_ERR_INVALID; }
+    if (!f->uploaded || !f->gbuf_den_plane[0]) { set_error("%s: needs an uploaded field with a gradient buffer", who); return T2N_ERR_INVALID; }
+    if (f->factor_bf16) { set_error("%s: bf16 factor storage keeps no fp32 master copy on the device", who); return T2N_ERR_UNSUPPORTED; }
     const int* gr = f->desc.grid;
     FactorStep A;
     memset(&A, 0, sizeof(A));
@@ -351,17 +397,27 @@ extern "C" int t2n_field_tv_seed(t2n_field* f, float tv_weight_density, float tv
             A.p[idx] = pcl[q]; A.g[idx] = gcl[q];
             A.npos[idx] = plane ? HW : L; A.C[idx] = C; A.H[idx] = plane ? H : (int)L; A.W[idx] = plane ? W : 1;
             if (tvw != 0.f) {
-                if (H < 2 || W < 2) { set_error("t2n_field_tv_seed: TV needs planes of at least 2x2"); return T2N_ERR_INVALID; }
+                if (H < 2 || W < 2) { set_error("%s: TV needs planes of at least 2x2", who); return T2N_ERR_INVALID; }
                 A.sh[idx] = tvw * 2.f / ((float)C * (float)(H - 1) * (float)W);
                 A.sw[idx] = tvw * 2.f / ((float)C * (float)H * (float)(W - 1));
             }
+            A.l1[idx] = factor_step_l1(idx, A.npos[idx] * C, l1_plane, l1_line);
             A.tblock0[idx] = tb;
             tb += (unsigned)((A.npos[idx] * (C / 4) + 255) / 256);
         }
     A.tblock0[12] = tb;
     hipLaunchKernelGGL(k_tv_seed_cl_multi, dim3(tb), dim3(256), 0, (hipStream_t)stream, A);
+    if (ortho_den != 0.f || ortho_app != 0.f) { const int rc = launch_ortho_lines(f, ortho_den, ortho_app, nullptr, (hipStream_t)stream); if (rc) return rc; }
     T2N_HIP(hipGetLastError());
     return T2N_OK;
+}
+extern "C" int t2n_field_tv_seed(t2n_field* f, float tv_weight_density, float tv_weight_app, t2n_stream stream) {
+    return field_seed("t2n_field_tv_seed", f, tv_weight_density, tv_weight_app, 0.f, 0.f, 0.f, 0.f, stream);
+}
+extern "C" int t2n_field_reg_seed(t2n_field* f, float tv_weight_density, float tv_weight_app, float l1_weight_plane, float l1_weight_line,
+                                  float ortho_weight_density, float ortho_weight_app, t2n_stream stream) {
+    return field_seed("t2n_field_reg_seed", f, tv_weight_density, tv_weight_app, l1_weight_plane, l1_weight_line, ortho_weight_density, ortho_weight_app,
+                      stream);
 }
 
 
@@ -415,14 +471,14 @@ static void factor_step_shard(const t2n_field* f, FactorStep& A, int world, int 
     }
     A.ablock0[12] = ab;
 }
-int launch_tv_seed_dev(t2n_field* f, const float* tvw_dev, hipStream_t s, int world, int rank) {
+int launch_tv_seed_dev(t2n_field* f, const float* tvw_dev, hipStream_t s, int world, int rank, bool l1_dev) {
     if (f->desc.grid[0] < 2 || f->desc.grid[1] < 2 || f->desc.grid[2] < 2) { set_error("t2n_train_step: TV needs planes of at least 2x2"); return T2N_ERR_INVALID; }
     FactorStep A;
     memset(&A, 0, sizeof(A));
     unsigned ab, tb;
     factor_step_geometry(f, A, ab, tb);
     factor_step_shard(f, A, world, rank, false, ab);
-    A.tvw_dev = tvw_dev;
+    A.tvw_dev = tvw_dev; A.l1_dev = l1_dev ? 1 : 0;
     hipLaunchKernelGGL(k_tv_seed_cl_multi, dim3(tb), dim3(256), 0, s, A);
     T2N_HIP(hipGetLastError());
     return T2N_OK;

@@ -4,7 +4,7 @@
 // beside it, and nothing about a step is decided on the host. Two side streams, the process-wide pair (ensure_side_streams):
 //   s  (caller)  [setup -> march] -> shade (kept rows) -> composite -> bwd_march (with the loss) -> mlp_bwd_ss -> tile_accum -> Adam (appearance factors)
 //   sa (side)    plan (rows, tile prefix, verdict, Adam scalars, host record) -> appearance binning (needs the forward's lists only) -> TV seed of the
-//                gradient buffer (behind the march) -> density scatter (behind bwd_march) -> Adam (density factors)
+//                gradient buffer (behind the march; + the L1 term, + the lines' ortho launches in a step that carries them) -> density scatter (behind bwd_march) -> Adam (density factors)
 //   sg (gemm)    [early form: density scan] -> layer-2 gradients (behind bwd_march) -> weight-gradient GEMMs (behind mlp_bwd_ss) -> reduce + losses
 //                -> Adam (head) -> operand re-packs
 // [setup -> march]: on sa in the pipelined form (beside the previous step's tail), behind the engine copy of the host batch.
@@ -218,6 +218,13 @@ extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_st
         set_error("t2n_train_step: shard_rank %d of %d, or a sharded step as one call (the gradient exchange lies between phases 1 and 2)", A->shard_rank, A->shard_world);
         return T2N_ERR_INVALID;
     }
+    // the L1 / ortho regularisers (hyper[21..24]; the flags say which the caller set): single rank only — the sharded seed scales the TV term
+    // per owner and knows nothing of these; refused rather than dropped
+    const bool reg_l1 = (A->flags & T2N_FLAG_REG_L1) != 0, reg_ortho = (A->flags & T2N_FLAG_REG_ORTHO) != 0;
+    if (sworld > 1 && (reg_l1 || reg_ortho)) {
+        set_error("t2n_train_step: the L1 / ortho regularisers (T2N_FLAG_REG_L1 / T2N_FLAG_REG_ORTHO) are not implemented for the sharded optimiser (shard_world %d)", sworld);
+        return T2N_ERR_UNSUPPORTED;
+    }
     if (A->phases == 4u) {   // sharded optimiser: the gathered body blocks of the other ranks -> the caller's reference-layout tensors
         if (!f->uploaded || !train_supported(f)) { set_error("t2n_train_step: phases = 4 needs an uploaded field of the fused step's shape"); return T2N_ERR_STATE; }
         if (sworld < 2) return T2N_OK;
@@ -271,6 +278,10 @@ extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_st
     bool den_early = den_env >= 0 ? den_env != 0 : A->n_rays <= 4096;
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cap_status);
+    if (cap_status != hipStreamCaptureStatusNone && (reg_l1 || reg_ortho)) {
+        set_error("t2n_train_step: the L1 / ortho regularisers (T2N_FLAG_REG_L1 / T2N_FLAG_REG_ORTHO) are not part of the captured step");
+        return T2N_ERR_UNSUPPORTED;
+    }
     if (cap_status != hipStreamCaptureStatusNone) den_early = false;   // (the captured step keeps the one DAG its replay was tested with: the early form's extra fork crashed hipStreamEndCapture on ROCm 7.2)
     const bool pipe = (A->flags & T2N_FLAG_PIPELINE) && A->host_batch && do_grad && do_opt && A->workspace_bytes >= 2 * T.total && cap_status == hipStreamCaptureStatusNone;
     const bool chain_prev = f->train_chain;               // the previous call was a full step of this form and left its density-Adam event
@@ -377,8 +388,10 @@ extern "C" int t2n_train_step(t2n_field* f, const t2n_train_step_args* A, t2n_st
         T2N_HIP(hipStreamWaitEvent(sa, ev[0], 0));     // (behind the previous step's Adam: it read this buffer and wrote the factors)
         T2N_HIP(hipStreamWaitEvent(sa, ev[2], 0));
         timing_begin(f, T2N_K_TV_SEED, sa);
-        if ((rc = launch_tv_seed_dev(f, A->hyper + 19, sa, sworld, srank))) return rc;
+        if ((rc = launch_tv_seed_dev(f, A->hyper + 19, sa, sworld, srank, reg_l1))) return rc;
         timing_end(f, T2N_K_TV_SEED, sa);
+        // the ortho term of the six lines, added directly behind the seed (Gram, gradient: two launches, only in a step that carries the term)
+        if (reg_ortho && (rc = launch_ortho_lines(f, 0.f, 0.f, A->hyper + 23, sa))) return rc;
         T2N_HIP(hipEventRecord(ev[1], sa));
         // ---- backward: per-ray pass
         float* x144 = (float*)(fw + kr.x144); float* feat32 = (float*)(fw + kr.feat32); float* h0 = (float*)(fw + kr.h0); float* h1 = (float*)(fw + kr.h1);
@@ -477,6 +490,10 @@ struct t2n_train_graph { hipGraph_t graph; hipGraphExec_t exec; int nodes; t2n_f
 extern "C" int t2n_train_graph_capture(t2n_field* f, const t2n_train_step_args* a, t2n_stream stream, t2n_train_graph** out) {
     if (!f || !a || !out) { set_error("t2n_train_graph_capture: NULL argument"); return T2N_ERR_INVALID; }
     if (!f->train_dev || !f->train_packed) { set_error("t2n_train_graph_capture: run t2n_train_step eagerly once first (lazy state cannot be captured)"); return T2N_ERR_STATE; }
+    if (a->flags & (T2N_FLAG_REG_L1 | T2N_FLAG_REG_ORTHO)) {
+        set_error("t2n_train_graph_capture: the L1 / ortho regularisers (T2N_FLAG_REG_L1 / T2N_FLAG_REG_ORTHO) are not part of the captured step: run it eagerly");
+        return T2N_ERR_UNSUPPORTED;
+    }
     // captured on a stream of its own: the caller's may be the legacy default stream, which cannot capture (hipErrorStreamCaptureUnsupported);
     // the instantiated graph is launched on whatever stream the caller passes to t2n_train_graph_launch
     (void)stream;

@@ -76,6 +76,105 @@ def tv_planes(reg, planes, scale):
     return _TVPlaneSum.apply(float(w) * float(scale), *planes)
 
 
+class _L1Sum(torch.autograd.Function):
+    """scale * sum_t mean|t| over contiguous fp32 device tensors (models/tensoRF.py:187-191) as one HIP kernel per tensor each way:
+    t2n_l1_value (float64 partial sums, fixed order), t2n_l1_grad_set (scale / numel * sign(t), sign(+-0) = 0, times the device
+    upstream scalar)."""
+
+    @staticmethod
+    def forward(ctx, scale, *tensors):
+        lib = _lib.load()
+        dev = tensors[0].device
+        sums = torch.empty(len(tensors), _lib.REG_SLOTS, device=dev, dtype=torch.float64)
+        ctx.scale = float(scale)
+        ctx.save_for_backward(*tensors)
+        with torch.cuda.device(dev):
+            st = _lib.current_stream_ptr(dev)
+            for i, t in enumerate(tensors):
+                _lib.check(lib.t2n_l1_value(_lib.ptr(t.detach()), t.numel(), _lib.ptr(sums[i]), st), "t2n_l1_value")
+        return (sums.sum() * ctx.scale).to(torch.float32)      # (the kernel's partial sums are already divided by numel)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        tensors = ctx.saved_tensors
+        dev = tensors[0].device
+        up = grad_out.detach().to(torch.float32).reshape(1).contiguous()
+        grads = []
+        with torch.cuda.device(dev):
+            st = _lib.current_stream_ptr(dev)
+            for t in tensors:
+                g = torch.empty_like(t)
+                _lib.check(lib.t2n_l1_grad_set(_lib.ptr(t.detach()), _lib.ptr(g), t.numel(), ctx.scale, _lib.ptr(up), st), "t2n_l1_grad_set")
+                grads.append(g)
+        return (None, *grads)
+
+
+class _OrthoSum(torch.autograd.Function):
+    """scale * sum_lines mean_{i != j} |(M M^T)_ij| over line tensors [1,C,n,1] / [C,n,1] (vectorDiffs, models/tensoRF.py:173-182):
+    t2n_ortho_value / t2n_ortho_grad_set, the Gram matrix in float64 in a fixed order (see csrc/t2n_reg.hip for why)."""
+
+    @staticmethod
+    def forward(ctx, scale, *lines):
+        lib = _lib.load()
+        dev = lines[0].device
+        vals = torch.empty(len(lines), device=dev, dtype=torch.float64)
+        ctx.scale = float(scale)
+        ctx.save_for_backward(*lines)
+        with torch.cuda.device(dev):
+            st = _lib.current_stream_ptr(dev)
+            for i, t in enumerate(lines):
+                c, n = int(t.shape[-3]), int(t.shape[-2])
+                ws = torch.empty(c * c, device=dev, dtype=torch.float64)
+                _lib.check(lib.t2n_ortho_value(_lib.ptr(t.detach()), c, n, _lib.ptr(vals[i:]), _lib.ptr(ws), ws.numel() * 8, st),
+                           "t2n_ortho_value")
+        return (vals.sum() * ctx.scale).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        lines = ctx.saved_tensors
+        dev = lines[0].device
+        up = grad_out.detach().to(torch.float32).reshape(1).contiguous()
+        grads = []
+        with torch.cuda.device(dev):
+            st = _lib.current_stream_ptr(dev)
+            for t in lines:
+                c, n = int(t.shape[-3]), int(t.shape[-2])
+                g = torch.empty_like(t)
+                ws = torch.empty(c * c, device=dev, dtype=torch.float64)
+                _lib.check(lib.t2n_ortho_grad_set(_lib.ptr(t.detach()), _lib.ptr(g), c, n, ctx.scale, _lib.ptr(up), _lib.ptr(ws),
+                                                  ws.numel() * 8, st), "t2n_ortho_grad_set")
+                grads.append(g)
+        return (None, *grads)
+
+
+def _kernel_tensor(t):
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() > 0
+
+
+def l1_terms(tensors, scale=1.0):
+    """scale * sum_t mean|t| (density_L1's sum, models/tensoRF.py:187-191) as a float32 device scalar through the HIP kernels; None
+    when they do not apply (CPU, non-float32 or non-contiguous tensors: the caller then evaluates the eager expression)."""
+    tensors = list(tensors)
+    if not tensors or not all(_kernel_tensor(t) for t in tensors):
+        return None
+    return _L1Sum.apply(float(scale), *tensors)
+
+
+def ortho_terms(lines, scale=1.0):
+    """scale * sum_lines vectorDiffs(line) (models/tensoRF.py:173-185) for line tensors [1,C,n,1] (or a stacked tensor's [C,n,1]
+    slices) as a float32 device scalar through the HIP kernels; None when they do not apply (CPU, non-float32, non-contiguous, or
+    C < 2, where the reference takes the mean of an empty tensor)."""
+    lines = list(lines)
+    if not lines:
+        return None
+    for t in lines:
+        if not (_kernel_tensor(t) and t.dim() in (3, 4) and t.shape[-1] == 1 and (t.dim() == 3 or t.shape[0] == 1) and t.shape[-3] >= 2):
+            return None
+    return _OrthoSum.apply(float(scale), *lines)
+
+
 class TVLoss(nn.Module):
     """Total-variation regulariser on a [B,C,H,W] plane (utils.py:488-504)."""
 

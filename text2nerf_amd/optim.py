@@ -44,10 +44,12 @@ class TVAdam(torch.optim.Optimizer):
             self.field = field
             field.defer_factor_grads = True
 
-    def _step_factors_on_device(self, tv, betas, eps):
-        """TV + Adam of the field's 12 factor tensors from the device-side gradients; returns the ids of the tensors handled."""
+    def _step_factors_on_device(self, tv, betas, eps, l1=(), ortho=()):
+        """TV (+ L1, ortho) + Adam of the field's 12 factor tensors from the device-side gradients; returns the ids of the tensors
+        handled."""
         import ctypes as C
         f = self.field
+        reg = f._reg_weights(l1, ortho)     # (entries other than the field's own parameter lists: T2NError, as for tv)
         ps = f._all_params()
         fac = ps[:12]
         if getattr(f, "_deferred_grad_key", None) is None or f._deferred_grad_key != f._uploaded_key:
@@ -95,9 +97,14 @@ class TVAdam(torch.optim.Optimizer):
             step_arr[i] = int(self.state[p]["step"])
         with torch.cuda.device(dev):
             pst = f._param_struct([p.detach() for p in ps])
-            _lib.check(_lib.load().t2n_field_tv_adam_step(f._handle, C.byref(pst), ms_arr, vs_arr, lr_arr, step_arr, float(betas[0]),
-                                                          float(betas[1]), eps, tv_d, tv_a, _lib.current_stream_ptr(dev)),
-                       "t2n_field_tv_adam_step")
+            if any(reg):
+                _lib.check(_lib.load().t2n_field_reg_adam_step(f._handle, C.byref(pst), ms_arr, vs_arr, lr_arr, step_arr, float(betas[0]),
+                                                               float(betas[1]), eps, tv_d, tv_a, *reg, _lib.current_stream_ptr(dev)),
+                           "t2n_field_reg_adam_step")
+            else:
+                _lib.check(_lib.load().t2n_field_tv_adam_step(f._handle, C.byref(pst), ms_arr, vs_arr, lr_arr, step_arr, float(betas[0]),
+                                                              float(betas[1]), eps, tv_d, tv_a, _lib.current_stream_ptr(dev)),
+                           "t2n_field_tv_adam_step")
         for p in fac:
             _bump_version(p)
         f._device_factor_key = tuple((p.data_ptr(), p._version) for p in fac)   # the device copies are these values
@@ -110,13 +117,17 @@ class TVAdam(torch.optim.Optimizer):
             self.field.zero_factor_grads()
 
     @torch.no_grad()
-    def step(self, tv=()):
+    def step(self, tv=(), l1=(), ortho=()):
+        """`tv`: [(planes, TV weight)]. `l1`: [(tensors, weight)] — weight * sum_t mean|t| over the listed [1,C,H,W] tensors (density_L1,
+        models/tensoRF.py:187-191). `ortho`: [(lines, weight)] — weight * sum vectorDiffs(line) over the listed [1,C,n,1] lines of at least
+        two components (vector_comp_diffs, :173-185). With `field=` the entries must be the field's own density_plane / density_line (l1)
+        and density_line / app_line (ortho)."""
         lib = _lib.load()
         done = set()
         if self.field is not None and self.field.defer_factor_grads:
             g0 = self.param_groups[0]
-            done = self._step_factors_on_device(tv, tuple(g0["betas"]), float(g0["eps"]))
-            tv = ()
+            done = self._step_factors_on_device(tv, tuple(g0["betas"]), float(g0["eps"]), l1, ortho)
+            tv = l1 = ortho = ()
         # 1. TV gradient of the listed plane groups: TV_loss_* = sum_planes 1e-2 * TVLoss(plane) (models/tensoRF.py:193-203)
         for planes, weight in tv:
             if weight == 0:
@@ -128,6 +139,33 @@ class TVAdam(torch.optim.Optimizer):
                 with torch.cuda.device(p.device):
                     _lib.check(lib.t2n_tv_grad_add(_lib.ptr(p), _lib.ptr(p.grad), C, H, W, float(weight) * 1e-2,
                                                    _lib.current_stream_ptr(p.device)), "t2n_tv_grad_add")
+        # 1b. the L1 and ortho gradients of the listed tensors, reference layout (csrc/t2n_reg.hip), in that order behind the TV term
+        for tensors, weight in l1:
+            if weight == 0:
+                continue
+            for p in tensors:
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p)
+                if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
+                    raise _lib.T2NError("TVAdam(l1=...): needs contiguous float32 tensors and gradients on the GPU")
+                with torch.cuda.device(p.device):
+                    _lib.check(lib.t2n_l1_grad_add(_lib.ptr(p), _lib.ptr(p.grad), p.numel(), float(weight), _lib.current_stream_ptr(p.device)),
+                               "t2n_l1_grad_add")
+        for lines, weight in ortho:
+            if weight == 0:
+                continue
+            for p in lines:
+                if p.dim() != 4 or p.shape[0] != 1 or p.shape[3] != 1 or p.shape[1] < 2:
+                    raise _lib.T2NError(f"TVAdam(ortho=...): needs [1,C,n,1] line tensors of at least two components, got {tuple(p.shape)}")
+                if p.grad is None:
+                    p.grad = torch.zeros_like(p)
+                if p.device.type != "cuda" or p.dtype != torch.float32 or not p.is_contiguous() or not p.grad.is_contiguous():
+                    raise _lib.T2NError("TVAdam(ortho=...): needs contiguous float32 lines and gradients on the GPU")
+                c, n = int(p.shape[1]), int(p.shape[2])
+                ws = torch.empty(c * c, device=p.device, dtype=torch.float64)
+                with torch.cuda.device(p.device):
+                    _lib.check(lib.t2n_ortho_grad_add(_lib.ptr(p), _lib.ptr(p.grad), c, n, float(weight), _lib.ptr(ws), ws.numel() * 8,
+                                                      _lib.current_stream_ptr(p.device)), "t2n_ortho_grad_add")
         # 2. Adam: every parameter tensor in one launch (same betas / eps across groups, per-tensor lr and step)
         import ctypes as C
         ps, lrs, steps = [], [], []

@@ -40,6 +40,31 @@ def _depth_kind(name) -> int:
     return kind
 
 
+def _live_terms(terms):
+    """The (parameter list, weight) entries of an `l1` / `ortho` argument whose weight is not zero."""
+    return [(g, w) for g, w in terms if float(w) != 0.0] if terms else ()
+
+
+def _check_reg_route(optimizer, graph, all_reduce):
+    """train_step with a non-zero L1 / ortho weight: the routes that do not carry the terms refuse them."""
+    from .optim import TVAdam
+    if not isinstance(optimizer, TVAdam):
+        raise T2NError("train_step(l1=..., ortho=...): the terms are applied by optim.TVAdam; another optimiser would drop them")
+    if graph:
+        raise T2NError("train_step(l1=..., ortho=..., graph=True): the captured step does not carry the L1 / ortho terms; run it eagerly")
+    if all_reduce is not None and hasattr(all_reduce, "gather") and int(getattr(all_reduce, "world", 1)) > 1:
+        raise T2NError("train_step(l1=..., ortho=...): the sharded optimiser (parallel.ShardedExchange) does not carry the L1 / ortho terms")
+
+
+def _step_with_terms(optimizer, tv, l1, ortho):
+    if l1 or ortho:
+        optimizer.step(tv=tv, l1=l1, ortho=ortho)
+    elif tv:
+        optimizer.step(tv=tv)
+    else:
+        optimizer.step()
+
+
 def _ws_key(device):
     device = torch.device(device)
     if device.type != "cuda":
@@ -751,21 +776,44 @@ class TensorBase(nn.Module):
                 raise T2NError("train_step: tv entries must be tensorf.density_plane / tensorf.app_plane")
         return tv_d, tv_a
 
+    def _reg_weights(self, l1, ortho):
+        """(L1 weight of the density planes, of the density lines, ortho weight of the density lines, of the appearance lines) of the
+        `l1` / `ortho` lists of train_step / TVAdam(field=...).step."""
+        l1_p = l1_l = o_d = o_a = 0.0
+        for group, weight in l1:
+            if group is self.density_plane:
+                l1_p = float(weight)
+            elif group is self.density_line:
+                l1_l = float(weight)
+            else:
+                raise T2NError("l1 entries must be tensorf.density_plane / tensorf.density_line")
+        for group, weight in ortho:
+            if group is self.density_line:
+                o_d = float(weight)
+            elif group is self.app_line:
+                o_a = float(weight)
+            else:
+                raise T2NError("ortho entries must be tensorf.density_line / tensorf.app_line")
+        return l1_p, l1_l, o_d, o_a
+
     def _factor_key(self):
         return tuple((p.data_ptr(), p._version) for p in self._all_params()[:12])
 
-    def seed_factor_grads_with_tv(self, tv, ahead=False):
+    def seed_factor_grads_with_tv(self, tv, ahead=False, l1=(), ortho=()):
         """Initialise the factor gradient buffer to the TV gradient of the current parameters (t2n_field_tv_seed) on a side stream, beside
         whatever the current stream does next: returns the event the backward has to wait for. `tv`: [(tensorf.density_plane, weight),
         (tensorf.app_plane, weight)] as for TVAdam.step. `ahead` (train_step, right behind its optimiser step): the seed of the NEXT
         step, written while the iteration's tail of small launches runs instead of beside the next forward's march (which it slows by a
         quarter); to everybody but a train_step with the same terms on unchanged parameters the buffer then counts as consumed
-        (zero-filled before use)."""
+        (zero-filled before use). `l1` / `ortho`: the L1 and ortho terms as for train_step (t2n_field_reg_seed: L1 inside the seed launch,
+        the six lines' ortho gradient in two launches behind it); their four weights are part of the key a seed written ahead is taken by."""
         lib = _lib.load()
         tv_d, tv_a = self._tv_weights(tv)
+        reg = self._reg_weights(l1, ortho)
         dev = self.basis_mat.weight.device
         pre = self.__dict__.get("_gbuf_preseed")
-        if not ahead and pre is not None and getattr(self, "_gbuf_stale", False) and pre[:2] == (tv_d, tv_a) and pre[2] == self._factor_key():
+        if not ahead and pre is not None and getattr(self, "_gbuf_stale", False) and pre[:2] == (tv_d, tv_a) and pre[2] == self._factor_key() \
+                and pre[4] == reg:
             self.__dict__["_gbuf_preseed"] = None          # written ahead by the previous step: take it
             self._gbuf_stale = False
             self._gbuf_dirty = True
@@ -779,13 +827,16 @@ class TensorBase(nn.Module):
             side = self.__dict__["_seed_stream"] = torch.cuda.Stream(device=dev)
         side.wait_stream(cur)            # the previous step's Adam has read the buffer and written the parameters
         with torch.cuda.device(dev):
-            _lib.check(lib.t2n_field_tv_seed(h, tv_d, tv_a, side.cuda_stream), "t2n_field_tv_seed")
+            if any(reg):
+                _lib.check(lib.t2n_field_reg_seed(h, tv_d, tv_a, *reg, side.cuda_stream), "t2n_field_reg_seed")
+            else:
+                _lib.check(lib.t2n_field_tv_seed(h, tv_d, tv_a, side.cuda_stream), "t2n_field_tv_seed")
         ev = side.record_event()
         self._gbuf_dirty = True
         self._gbuf_reduced = False
         if ahead:
             self._gbuf_stale = True
-            self.__dict__["_gbuf_preseed"] = (tv_d, tv_a, self._factor_key(), ev)
+            self.__dict__["_gbuf_preseed"] = (tv_d, tv_a, self._factor_key(), ev, reg)
         else:
             self._gbuf_stale = False
             self.__dict__["_gbuf_preseed"] = None
@@ -1426,7 +1477,7 @@ class TensorBase(nn.Module):
                 "workspace_bytes": int(plan.workspace_bytes)}
 
     def _general_train_step(self, rays, rgb_target, depth_target, optimizer, N_samples, white_bg, w_depth, w_trans, delta, tv, all_reduce,
-                            kind, depth_std):
+                            kind, depth_std, l1=(), ortho=()):
         """train_step on a general-shape field, composed: _general_forward (train mode) -> t2n_train_loss[_ex] -> _general_backward ->
         .grad in the reference layouts -> all_reduce -> optimizer.step. The field's AlphaGridMask is honoured (the general kernels test
         it themselves)."""
@@ -1467,12 +1518,12 @@ class TensorBase(nn.Module):
                 p.grad = g
             if all_reduce is not None:
                 all_reduce()
-            optimizer.step(tv=tv) if tv else optimizer.step()
+            _step_with_terms(optimizer, tv, l1, ortho)
         return losses
 
     def train_step(self, rays, rgb_target, depth_target, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
                    tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None, depth_loss="mse",
-                   depth_std=0.1):
+                   depth_std=0.1, l1=(), ortho=()):
         """One optimisation step of text2nerf_main.py:547-590 without the autograd graph: render (train mode, CPU-generator jitter
         like models/tensorBase.py:313-317) -> the driver's loss as ONE kernel that emits d_rgb / d_depth / d_weights
         (t2n_train_loss) -> t2n_render_backward -> optimizer.step(). `optimizer`: optim.TVAdam(field=self) (TV terms via `tv`, as
@@ -1502,18 +1553,30 @@ class TensorBase(nn.Module):
         A general-shape field (`_is_general`) takes the composed route on its own kernels — t2n_generic_forward, the loss kernel,
         t2n_generic_backward[_staged], the gradients installed as `.grad` in the reference layouts — with optim.TVAdam WITHOUT `field=`
         (or any torch.optim optimiser when `tv` is empty); its AlphaGridMask is honoured; `fused=True` raises, `speculative` and `graph`
-        have no effect."""
+        have no effect.
+        `l1` / `ortho`: TensoRF's other two parameter regularisers (models/tensoRF.py:173-191), as lists of (parameter list, weight) like
+        `tv` — `l1`: tensorf.density_plane / tensorf.density_line under the weight of density_L1() (--L1_weight_inital / --L1_weight_rest),
+        `ortho`: tensorf.density_line / tensorf.app_line under the weight of vector_comp_diffs() (--Ortho_weight); tensorf.reg_terms(l1,
+        ortho) builds both for the reference's two scalars. Applied on every route (the one-call step: inside its seed launch plus two
+        launches for the six lines; the composed step: t2n_field_reg_seed / t2n_field_reg_adam_step; general shapes: the reference-layout
+        kernels of optim.TVAdam). Like TV they are not part of the returned `total`; weights may change from step to step. With a
+        non-zero weight, `graph=True`, a sharded exchange and an optimiser other than optim.TVAdam raise T2NError."""
         lib = _lib.load()
         params = self._autograd_params()
         kind = _depth_kind(depth_loss)
         self.__dict__["last_depth_aux"] = None
+        l1, ortho = _live_terms(l1), _live_terms(ortho)
+        if l1 or ortho:
+            _check_reg_route(optimizer, graph, all_reduce)
+            if getattr(optimizer, "field", None) is self:
+                self._reg_weights(l1, ortho)       # (entries other than the field's own lists: refused before anything is drawn or queued)
         fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, kind)
         if fuse is not None:
             fs, N, flags, use_graph = fuse
-            return fs.step(rays, rgb_target, depth_target, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce)
+            return fs.step(rays, rgb_target, depth_target, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce, l1=l1, ortho=ortho)
         if self._is_general():     # (speculative / graph: forms of the tuned backward and of the one-call step, no effect here)
             return self._general_train_step(rays, rgb_target, depth_target, optimizer, N_samples, white_bg, w_depth, w_trans, delta, tv,
-                                            all_reduce, kind, depth_std)
+                                            all_reduce, kind, depth_std, l1, ortho)
         if any(not p.is_leaf for p in params):
             raise T2NError("train_step needs the kernels' own field shape (the parameters ARE the kernel tensors); embedded shapes, "
                            "TensorVM and TensorCP train through the autograd form (OctreeRender_trilinear_fast + loss.backward())")
@@ -1531,10 +1594,10 @@ class TensorBase(nn.Module):
         # TV terms: the gradient buffer starts as the TV gradient (one write-only pass on a side stream beside the forward) instead of
         # being zero-filled, accumulated into and TV-incremented after the backward
         seed_ev = seed_terms = None
-        if tv and R >= _SEED_MIN_RAYS and getattr(optimizer, "field", None) is self and getattr(self, "defer_factor_grads", False) \
+        if (tv or l1 or ortho) and R >= _SEED_MIN_RAYS and getattr(optimizer, "field", None) is self and getattr(self, "defer_factor_grads", False) \
                 and self.supports_deferred_factor_grads() and (all_reduce is None or all_reduce_averages):
-            seed_ev = self.seed_factor_grads_with_tv(tv)
-            seed_terms, tv = list(tv), ()
+            seed_ev = self.seed_factor_grads_with_tv(tv, l1=l1, ortho=ortho)
+            seed_terms, tv, l1, ortho = (list(tv), list(l1), list(ortho)), (), (), ()
         device_rows = False
         if speculative:
             device_rows = self._poll_device_rows() and bool(self.keep_activation_rows) and int(getattr(self, "_ctx_rows_hint", 0)) > 0 \
@@ -1585,9 +1648,9 @@ class TensorBase(nn.Module):
                 p.grad = g
             if all_reduce is not None:
                 all_reduce()
-            optimizer.step(tv=tv) if tv else optimizer.step()
+            _step_with_terms(optimizer, tv, l1, ortho)
             if seed_terms is not None:
-                self.seed_factor_grads_with_tv(seed_terms, ahead=True)
+                self.seed_factor_grads_with_tv(seed_terms[0], ahead=True, l1=seed_terms[1], ortho=seed_terms[2])
             if speculative:
                 # nothing in the step waits for the GPU any more: the host is held to two steps of run-ahead (a queue that grows
                 # without bound stalls in the HIP runtime for milliseconds at a time: 7-ms pauses every ~11 steps measured)
@@ -1601,7 +1664,7 @@ class TensorBase(nn.Module):
 
     def train_step_indexed(self, source, ids, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
                            tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None, depth_loss="mse",
-                           depth_std=0.1):
+                           depth_std=0.1, l1=(), ortho=()):
         """`train_step` on rows `ids` of a `dataset.DeviceTrainSet` (rays, colours and depths kept on the device): same keyword
         arguments, same arithmetic, same draws from the CPU generator in the same order. `ids`: an int64 (as SimpleSampler returns it) or
         int32 tensor. On the host its range is checked before anything is drawn or queued — an id outside [0, len(source)) or a
@@ -1612,15 +1675,20 @@ class TensorBase(nn.Module):
         from .dataset import check_ids
         ids = check_ids(ids, len(source))
         self.__dict__["last_depth_aux"] = None
+        l1, ortho = _live_terms(l1), _live_terms(ortho)
+        if l1 or ortho:
+            _check_reg_route(optimizer, graph, all_reduce)
+            if getattr(optimizer, "field", None) is self:
+                self._reg_weights(l1, ortho)       # (entries other than the field's own lists: refused before anything is drawn or queued)
         fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph,
                                     _depth_kind(depth_loss))
         if fuse is not None:
             fs, N, flags, use_graph = fuse
-            return fs.step_indexed(source, ids, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce)
+            return fs.step_indexed(source, ids, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce, l1=l1, ortho=ortho)
         rays, rgb_t, dep_t = source.rows(ids)
         return self.train_step(rays, rgb_t, dep_t, optimizer, N_samples=N_samples, white_bg=white_bg, w_depth=w_depth, w_trans=w_trans,
                                delta=delta, tv=tv, all_reduce=all_reduce, all_reduce_averages=all_reduce_averages, speculative=speculative,
-                               fused=False if fused is None else fused, graph=graph, depth_loss=depth_loss, depth_std=depth_std)
+                               fused=False if fused is None else fused, graph=graph, depth_loss=depth_loss, depth_std=depth_std, l1=l1, ortho=ortho)
 
     def _fused_step_for(self, optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, depth_kind=0):
         """The fuse decision of train_step / train_step_indexed: None (the composed step), or (the field's FusedStep for this optimiser,
@@ -1756,10 +1824,22 @@ class TensorVMSplit(TensorBase):
         return total
 
     def density_L1(self):
+        """models/tensoRF.py:187-191. Device tensors run as one HIP kernel per tensor each way (losses.l1_terms)."""
+        from .losses import l1_terms
+        fused = l1_terms([t for pair in zip(self.density_plane, self.density_line) for t in pair])
+        if fused is not None:
+            return fused
         total = 0
         for p, l in zip(self.density_plane, self.density_line):
             total = total + torch.mean(torch.abs(p)) + torch.mean(torch.abs(l))
         return total
+
+    def reg_terms(self, l1=0.0, ortho=0.0):
+        """The `l1` / `ortho` arguments of train_step and TVAdam.step for the reference's two scalar weights (--L1_weight_inital or
+        --L1_weight_rest on density_L1(), --Ortho_weight on vector_comp_diffs()): returns (l1 list, ortho list)."""
+        l1_list = [(self.density_plane, l1), (self.density_line, l1)] if l1 else []
+        ortho_list = [(self.density_line, ortho), (self.app_line, ortho)] if ortho else []
+        return l1_list, ortho_list
 
     def vectorDiffs(self, vector_comps):
         total = 0
@@ -1771,6 +1851,11 @@ class TensorVMSplit(TensorBase):
         return total
 
     def vector_comp_diffs(self):
+        """models/tensoRF.py:184-185. Device lines of at least two components run through the HIP kernels (losses.ortho_terms)."""
+        from .losses import ortho_terms
+        fused = ortho_terms(list(self.density_line) + list(self.app_line))
+        if fused is not None:
+            return fused
         return self.vectorDiffs(self.density_line) + self.vectorDiffs(self.app_line)
 
     def compute_densityfeature(self, xyz_sampled):
@@ -1913,6 +1998,10 @@ class TensorVM(TensorVMSplit):
 
     def vector_comp_diffs(self):
         a, d = self.app_n_comp[0], self.density_n_comp[0]
+        from .losses import ortho_terms
+        fused = ortho_terms([self.line_coef[k, -d:] for k in range(3)] + [self.line_coef[k, :a] for k in range(3)])
+        if fused is not None:
+            return fused
         return self.vectorDiffs(self.line_coef[:, -d:]) + self.vectorDiffs(self.line_coef[:, :a])
 
     def vectorDiffs(self, vector_comps):
@@ -2039,6 +2128,10 @@ class TensorCP(TensorVMSplit):
         return super().state_dict(*a, **k)
 
     def density_L1(self):
+        from .losses import l1_terms
+        fused = l1_terms(list(self.density_line))
+        if fused is not None:
+            return fused
         return sum(torch.mean(torch.abs(l)) for l in self.density_line)
 
     def TV_loss_density(self, reg):

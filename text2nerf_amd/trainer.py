@@ -120,8 +120,10 @@ class FusedStep:
         self._arg_cache = {}
         return ps, ms, vs, steps[0]
 
-    def _hyper(self, tv):
-        """The step's scalars as a list of TRAIN_HYPER_FLOATS floats (19 learning rates, the two TV weights x 1e-2), betas, eps."""
+    def _hyper(self, tv, l1=(), ortho=()):
+        """The step's scalars as a list of TRAIN_HYPER_FLOATS floats (19 learning rates, the two TV weights x 1e-2, [21..22] the L1
+        weights of the density planes / lines, [23..24] the ortho weights of the density / appearance lines), betas, eps, and the
+        T2N_FLAG_REG_* bits that tell the C call which of the new terms this step carries."""
         f, opt = self.field, self.opt
         groups = opt.param_groups
         gi = self._group_of
@@ -134,7 +136,9 @@ class FusedStep:
         lrs = [float(g["lr"]) for g in groups]
         h = [lrs[k] for k in gi[0]]
         tv_d, tv_a = f._tv_weights(tv)
-        h += [tv_d, tv_a] + [0.0] * (_lib.TRAIN_HYPER_FLOATS - 21)
+        reg = f._reg_weights(l1, ortho) if (l1 or ortho) else (0.0, 0.0, 0.0, 0.0)     # (the keyword-free step pays nothing for them)
+        h += [tv_d, tv_a] + list(reg) + [0.0] * (_lib.TRAIN_HYPER_FLOATS - 25)
+        self._reg_flags = (_lib.FLAG_REG_L1 if (reg[0] or reg[1]) else 0) | (_lib.FLAG_REG_ORTHO if (reg[2] or reg[3]) else 0)
         g0 = groups[0]
         b0, e0 = g0["betas"], g0["eps"]
         for g in groups:
@@ -476,10 +480,11 @@ class FusedStep:
             self.events.pop(0).synchronize()
         return self.losses
 
-    def step(self, rays, rgb_t, dep_t, N, flags, w_depth, w_trans, delta, tv, graph, all_reduce=None):
+    def step(self, rays, rgb_t, dep_t, N, flags, w_depth, w_trans, delta, tv, graph, all_reduce=None, l1=(), ortho=()):
         R, stride = int(rays.shape[0]), int(rays.shape[1])
         i, untouched = self._begin(R)
-        hyper, betas, eps = self._hyper(tv)
+        hyper, betas, eps = self._hyper(tv, l1, ortho)
+        flags |= self._reg_flags
         n_in = R * stride + R + 3 * R + R + _lib.TRAIN_HYPER_FLOATS
         for j in range(_RING):          # (all four slots at once: a pinned allocation inside somebody's timed loop costs a millisecond)
             self._ensure_inbuf(j, n_in)
@@ -515,7 +520,7 @@ class FusedStep:
         self._submit(i, meta, graph, all_reduce)
         return self._end(i)
 
-    def step_indexed(self, source, ids, N, flags, w_depth, w_trans, delta, tv, graph, all_reduce=None):
+    def step_indexed(self, source, ids, N, flags, w_depth, w_trans, delta, tv, graph, all_reduce=None, l1=(), ortho=()):
         """`step` on rows `ids` (validated: dataset.check_ids) of a dataset.DeviceTrainSet on this device: the host stages
         ids (int32) | jitter | hyper — 2 R + 32 words instead of 11 R + 32 — and the C call gathers the rows into the slot's buffer as
         its first device work (T2N_FLAG_GATHER_BATCH). The jitter is drawn where `step` draws it; everything behind the gather is `step`."""
@@ -523,7 +528,8 @@ class FusedStep:
             raise T2NError(f"fused train step: the training set is on {source.rays.device}, the field on {self.dev}")
         R, stride = int(ids.numel()), 6
         i, untouched = self._begin(R)
-        hyper, betas, eps = self._hyper(tv)
+        hyper, betas, eps = self._hyper(tv, l1, ortho)
+        flags |= self._reg_flags
         lay = self._layout(R, stride, True)
         n_in, n_host = lay["n"], lay["host"]
         for j in range(_RING):
