@@ -183,6 +183,23 @@ int t2n_field_set_early_termination(t2n_field* f, float eps);
  * created. A diagnostic: it waits for the whole device (hipDeviceSynchronize), so it must not be called inside a stream capture. */
 int t2n_field_set_feature_staging(t2n_field* f, int on);
 int t2n_field_feature_staging_counts(const t2n_field* f, uint64_t out[2]);
+/* Cached summed density table of the tile marcher (T2N_FLAG_COHERENT eval frames). The marcher's per-step-pair table
+ * S[z][y][x] = (D0 + D1) + D2, D_k = P_k L_k^T, is a function of the density factors alone; with the cache on (default of a new
+ * handle) the second consecutive tile-marcher frame that finds the factors unchanged builds S for the whole grid once
+ * ((grid + 1)^3 floats in a buffer the field owns, built on that frame's stream), and frames read their entries there until the
+ * factors change (t2n_field_upload, the field Adam steps, t2n_train_step, a t2n_field_factor_buffer view). Frames are the same bit
+ * for bit with and without it. Not cached: grids whose cells x 4 B exceed the cap (t2n_field_set_density_cache_cap; 0 = the default,
+ * 1/64 of the device's memory), a failed allocation, cache switched off.
+ * t2n_field_release_density_cache frees the buffer (waits for the device); the next two frames build it again.
+ * t2n_field_density_cache_counts: out[0] / out[1] = tile-marcher launches served from the cache / without it, out[2] = builds,
+ * out[3] = bytes the buffer holds now (host-side counters: no device wait).
+ * DIAGNOSTIC t2n_field_density_sum_table: the builder alone — S of the whole grid into `out` ((grid[0] + 1) (grid[1] + 1) (grid[2] + 1)
+ * floats, x fastest), computed in 4 x 4 x 4 boxes anchored at 4 b - shift[axis] (shift in [0, 3]): every shift gives the same bits. */
+int t2n_field_set_density_cache(t2n_field* f, int on);
+int t2n_field_set_density_cache_cap(t2n_field* f, uint64_t bytes);
+int t2n_field_release_density_cache(t2n_field* f);
+int t2n_field_density_cache_counts(const t2n_field* f, uint64_t out[4]);
+int t2n_field_density_sum_table(const t2n_field* f, const int* shift, float* out, t2n_stream stream);
 /* DIAGNOSTIC, for tests of the feature stage's tile queue only (like the staging counters above, not part of the rendering API): the
  * shape of the feature stage's launch. At most `workgroups` workgroups of eight waves (0 = the default, 512), and `defer_cap` tiles
  * (1 .. 64; 0 = the default, 16) that a wave sets aside for its gathered loop before it drains them. Small values make one wave see

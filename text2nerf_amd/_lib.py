@@ -103,6 +103,11 @@ SIGNATURES = {
     "t2n_field_set_feature_staging": (C.c_int, [C.c_void_p, C.c_int]),
     "t2n_field_feature_staging_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "t2n_field_set_feature_stage_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "t2n_field_set_density_cache": (C.c_int, [C.c_void_p, C.c_int]),
+    "t2n_field_set_density_cache_cap": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "t2n_field_release_density_cache": (C.c_int, [C.c_void_p]),
+    "t2n_field_density_cache_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "t2n_field_density_sum_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "t2n_sample_ray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "t2n_field_set_frame_width": (C.c_int, [C.c_void_p, C.c_int]),

@@ -122,6 +122,7 @@ int launch_relayout(t2n_field* f, const t2n_field_params* p, hipStream_t s) {
         f->dev.app.plane_h[k] = hf ? f->hbuf_app_plane[k] : nullptr; f->dev.app.line_h[k] = hf ? f->hbuf_app_line[k] : nullptr;
     }
     m.block0[m.count] = blocks;
+    ++f->den_version;   // the density factors change: the cached summed table (density_cache_prepare) is stale
     if (blocks) hipLaunchKernelGGL(k_relayout, dim3(blocks), dim3(256), 0, s, m);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
@@ -436,6 +437,8 @@ extern "C" int t2n_field_destroy(t2n_field* f) {
     if (f->gbuf_all && !f->gbuf_external) (void)hipFree(f->gbuf_all);
     if (f->buf_mlp) (void)hipFree(f->buf_mlp);
     if (f->staging_counts) (void)hipFree(f->staging_counts);
+    if (f->dcache) (void)hipFree(f->dcache);
+    if (f->dcache_ev) (void)hipEventDestroy((hipEvent_t)f->dcache_ev);
     if (f->reg_ws) (void)hipFree(f->reg_ws);
     if (f->buf_mlp_h) (void)hipFree(f->buf_mlp_h);
     if (f->buf_ss) (void)hipFree(f->buf_ss);
@@ -750,6 +753,7 @@ extern "C" int t2n_render_forward(t2n_field* f, const float* rays, int64_t n_ray
             if (per <= 0) { set_error("t2n_render_forward: workspace too small for one 8-row band"); return T2N_ERR_WORKSPACE; }
         }
     }
+    if (tiles) { const int rc = density_cache_prepare(f, s); if (rc) return rc; }   // once per frame, whatever its sub-launches
     char* ws = (char*)workspace;
     for (int64_t off = 0; off < n_rays; off += per) {
         const int64_t cnt = (n_rays - off) < per ? (n_rays - off) : per;
@@ -924,6 +928,34 @@ extern "C" int t2n_field_set_feature_staging(t2n_field* f, int on) {
     if (!f) { set_error("t2n_field_set_feature_staging: NULL field"); return T2N_ERR_INVALID; }
     f->feature_staging = on ? 1 : 0;
     return T2N_OK;
+}
+
+// ---- cached summed density table of the tile marcher (t2n_march_tiles.hip) ---------------------------------------------------------
+extern "C" int t2n_field_set_density_cache(t2n_field* f, int on) {
+    if (!f) { set_error("t2n_field_set_density_cache: NULL field"); return T2N_ERR_INVALID; }
+    f->dcache_on = on ? 1 : 0;
+    return T2N_OK;
+}
+extern "C" int t2n_field_set_density_cache_cap(t2n_field* f, uint64_t bytes) {
+    if (!f) { set_error("t2n_field_set_density_cache_cap: NULL field"); return T2N_ERR_INVALID; }
+    f->dcache_cap = (size_t)bytes;
+    f->dcache_alloc_failed = false;
+    return T2N_OK;
+}
+extern "C" int t2n_field_release_density_cache(t2n_field* f) {
+    if (!f) { set_error("t2n_field_release_density_cache: NULL field"); return T2N_ERR_INVALID; }
+    density_cache_release(f);
+    return T2N_OK;
+}
+extern "C" int t2n_field_density_cache_counts(const t2n_field* f, uint64_t out[4]) {
+    if (!f || !out) { set_error("t2n_field_density_cache_counts: NULL argument"); return T2N_ERR_INVALID; }
+    out[0] = f->dcache_counts[0]; out[1] = f->dcache_counts[1]; out[2] = f->dcache_counts[2]; out[3] = (uint64_t)f->dcache_bytes;
+    return T2N_OK;
+}
+extern "C" int t2n_field_density_sum_table(const t2n_field* f, const int* shift, float* out, t2n_stream stream) {
+    if (!f || !shift || !out) { set_error("t2n_field_density_sum_table: NULL argument"); return T2N_ERR_INVALID; }
+    if (!f->uploaded) { set_error("t2n_field_density_sum_table: the field has no uploaded factors"); return T2N_ERR_STATE; }
+    return launch_density_sum_table(f, out, shift, (hipStream_t)stream);
 }
 
 extern "C" int t2n_field_set_feature_stage_shape(t2n_field* f, int workgroups, int defer_cap) {

@@ -52,6 +52,10 @@ struct FieldDev {
     // transmittance fell below term_eps evaluates no further sample. The reference never terminates (models/tensorBase.py:19-26,
     // 494-505: every in-box sample is evaluated); what the rest of a ray could add is bounded by T: acc < eps, rgb < eps, depth < eps z_max.
     float term_eps;
+    // cached summed density table of the whole grid (tile marcher, t2n_march_tiles.hip): S[z][y][x] over (grid + 1)^3 entries, the last
+    // entry of every axis a copy of the clamped one; NULL = the marcher builds its 4 x 4 x 4 piece per step pair. Set per call by
+    // t2n_render_forward (density_cache_prepare); ds_row / ds_slice: BYTES between y and z neighbours.
+    const float* dsum; unsigned ds_row, ds_slice;
 };
 
 // Device-side state of the fused training step (t2n_train_step): one 256-B block per field. k_train_plan advances it once per step;
@@ -145,6 +149,14 @@ struct t2n_field {
     unsigned list_hint = 0;          // appearance entries per ray of the last budgeted launch (0: unknown)
     void* reg_ws = nullptr; size_t reg_ws_bytes = 0;   // ortho regulariser: the six lines' float64 Gram matrices (t2n_reg.hip), allocated by the first upload
     unsigned long long list_retries = 0;
+    // cached summed density table (t2n_field_set_density_cache): a function of the density factors alone, built by the second consecutive
+    // tile-marcher frame that finds den_version unchanged; every launcher that writes the device density factors bumps den_version
+    float* dcache = nullptr; size_t dcache_bytes = 0;
+    unsigned long long den_version = 1, dcache_version = 0, dcache_seen = 0;   // factors now / the cache's / the last tile frame's
+    int dcache_on = 1; size_t dcache_cap = 0;        // cap in bytes on grid cells x 4 B (0 = 1/64 of the device's memory)
+    bool dcache_alloc_failed = false;
+    void* dcache_ev = nullptr; void* dcache_stream = nullptr;   // the build's stream + an event behind it: a frame on another stream waits for it
+    unsigned long long dcache_counts[3] = {0, 0, 0};   // tile-marcher frames served from the cache / without it, builds
 };
 
 namespace t2n {
@@ -182,6 +194,13 @@ int launch_ray_stats(const RenderLaunch& L, hipStream_t s);
 int launch_filter_bbox(const FieldDev& F, const float* rays, long long n_rays, int ray_stride, uint8_t* mask, hipStream_t s);
 int launch_filter_alpha(const FieldDev& F, const float* rays, long long n_rays, int ray_stride, int n_samples, uint8_t* mask, hipStream_t s);
 // spill: [n_rays][n_samples] scratch rows (used only when L.weights is NULL); scratch: [n_rays][n_samples / 4] staging entries
+// the cached summed density table (t2n_march_tiles.hip). density_cache_prepare: called once per tile-marcher frame; sets f->dev.dsum
+// (NULL = uncached frame), builds on the second frame of a factor version. launch_density_sum_table: S of the whole grid into `out`
+// ((grid + 1)^3 floats), boxes anchored at 4 b - shift per axis
+size_t density_cache_bytes(const t2n_field* f);
+int density_cache_prepare(t2n_field* f, hipStream_t s);
+void density_cache_release(t2n_field* f);
+int launch_density_sum_table(const t2n_field* f, float* out, const int shift[3], hipStream_t s);
 int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h, float* spill, float4* scratch, hipStream_t s);
 constexpr int kLists = 8;   // appearance sub-lists per sub-launch
 constexpr int kCounterStride = 64;   // unsigned words between sub-list counters: one 256-B line each (same-line atomics serialise)

@@ -21,6 +21,9 @@
 // the appearance list (in-kernel compaction, see TileArgs); with weights requested (DENSE) also the weights of the wave's sampled
 // window (k_dense_fill writes the z_vals rows and the zeros of the weights rows beforehand).
 // Steps whose rectangles do not fit the table (incoherent rays, huge field of view) fall back to direct gathers.
+// S is a function of the density factors alone: a field rendered more than once keeps S of its WHOLE grid in a per-field buffer
+// (k_density_sum_table, density_cache_prepare) and the CACHED instantiations read a cell's eight entries there — the same bits,
+// without the per-step-pair loads, MFMAs, LDS table and fences (C2 frame: 0.51 -> 0.38 ms; profiles/march_density_cache_ab.txt).
 // Replaces the same reference lines as k_march (see t2n_march.hip).
 #include "t2n_device.h"
 
@@ -182,6 +185,36 @@ __device__ __forceinline__ float table_read3(const Axes3& A, int org, const floa
     return fmaf(v1, az.w1, v0 * az.w0);
 }
 
+// The same feature from the CACHED table of the whole grid (FieldDev::dsum, k_density_sum_table): the eight entries of a cell are four
+// 8-byte loads (x and x + 1 are adjacent; rows are only 4-B aligned) off one scalar base and a 32-bit byte offset per lane; the
+// weight products and multiply-adds are table_read3's, in its order, on entries that are the same bits (tests/test_density_cache.py).
+struct __attribute__((aligned(4))) F2U { float a, b; };
+struct CellTaps { F2U d00, d01, d10, d11; };   // (z, y), (z, y + 1), (z + 1, y), (z + 1, y + 1); .a = x, .b = x + 1
+__device__ __forceinline__ unsigned cached_offset(const FieldDev& F, const Axes3& A) {
+    // (24-bit multiplies: full rate; density_cache_prepare refuses grids whose row count or row bytes leave 24 bits)
+    return umad24(umad24((unsigned)A.a[2].i0, (unsigned)F.den.H[0] + 1u, (unsigned)A.a[1].i0), F.ds_row, (unsigned)A.a[0].i0 << 2);
+}
+__device__ __forceinline__ CellTaps cached_load(const FieldDev& F, unsigned off) {
+    const char* __restrict__ B = reinterpret_cast<const char*>(F.dsum);
+    CellTaps t;
+    t.d00 = *reinterpret_cast<const F2U*>(B + off);
+    t.d01 = *reinterpret_cast<const F2U*>(B + (off + F.ds_row));
+    t.d10 = *reinterpret_cast<const F2U*>(B + (off + F.ds_slice));
+    t.d11 = *reinterpret_cast<const F2U*>(B + (off + F.ds_slice + F.ds_row));
+    return t;
+}
+__device__ __forceinline__ float cached_read3(const Axes3& A, const CellTaps& t) {
+    const Axis& ax = A.a[0];
+    const Axis& ay = A.a[1];
+    const Axis& az = A.a[2];
+    const float wnw = ay.w0 * ax.w0, wne = ay.w0 * ax.w1, wsw = ay.w1 * ax.w0, wse = ay.w1 * ax.w1;
+    float v0 = t.d00.a * wnw, v1 = t.d10.a * wnw;
+    v0 = fmaf(t.d00.b, wne, v0); v1 = fmaf(t.d10.b, wne, v1);
+    v0 = fmaf(t.d01.a, wsw, v0); v1 = fmaf(t.d11.a, wsw, v1);
+    v0 = fmaf(t.d01.b, wse, v0); v1 = fmaf(t.d11.b, wse, v1);
+    return fmaf(v1, az.w1, v0 * az.w0);
+}
+
 template <int K>
 __device__ __forceinline__ float pair_dot_global(const FactorSet& S, const Axes3& A, float part) {
     const Axis& ax = A.a[mat0(K)];
@@ -231,6 +264,16 @@ struct __attribute__((aligned(4))) F4U { float x, y, z, w; };   // row segments 
 #ifndef T2N_MTD_WAVES
 #define T2N_MTD_WAVES 4
 #endif
+// the instantiations that read the cached table (CACHED): no operand loads, no MFMA results and no LDS table are live in the step loop.
+// C2 frame, the marcher's own time: 5 waves (91 VGPRs, no scratch, no LDS) 0.376 / 0.377 / 0.380 ms, 6 waves (80 VGPRs, 48 B of scratch
+// per lane) 0.381 / 0.384 / 0.387, 4 waves (104 VGPRs) the same frame time as 5; the weights-writing variant (112 VGPRs, the 20-KB
+// transpose tile its only LDS) stays at 4 (profiles/march_density_cache_ab.txt).
+#ifndef T2N_MTC_WAVES
+#define T2N_MTC_WAVES 5
+#endif
+#ifndef T2N_MTCD_WAVES
+#define T2N_MTCD_WAVES 4
+#endif
 // -DMT_PROF (timing-only build): s_memtime at the region boundaries of a step pair, summed per wave. With five waves per SIMD a
 // region's cycles include what the SIMD gave to the other four meanwhile: the sums say where a wave's time goes, not what the
 // instructions cost alone.
@@ -242,15 +285,22 @@ struct __attribute__((aligned(4))) F4U { float x, y, z, w; };   // row segments 
 // ALPHA: the field carries an AlphaGridMask; RELU: fea2denseAct = relu. Compile-time, like the absent NDC depth table (the host never
 // sends NDC renders here): the step loop of the driver's configuration (no mask, softplus) carries neither the mask's eight-tap
 // gather with its 64-bit address arithmetic nor a run-time test per sample and option.
-template <bool DENSE, bool ALPHA = false, bool RELU = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DENSE ? T2N_MTD_WAVES : T2N_MT_WAVES, DENSE ? T2N_MTD_WAVES : T2N_MT_WAVES))) void k_march_tiles(const TileArgs a) {
+// CACHED: the field carries the summed table of its whole grid (FieldDev::dsum): a step pair inside the table's reach reads its entries
+// there instead of building its 4 x 4 x 4 piece (same bits, see cached_read3). Which step pairs take the table form and which the direct
+// gathers is decided exactly as without the cache (the two forms round differently, and the frame is the same bit for bit either way),
+// so the tap bit set stays; the operand loads, the MFMAs, the LDS table, its sum pass and the three fences go.
+constexpr int mt_waves(bool dense, bool cached) { return cached ? (dense ? T2N_MTCD_WAVES : T2N_MTC_WAVES) : (dense ? T2N_MTD_WAVES : T2N_MT_WAVES); }
+template <bool DENSE, bool ALPHA = false, bool RELU = false, bool CACHED = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DENSE, CACHED), mt_waves(DENSE, CACHED)))) void k_march_tiles(const TileArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int l15 = lane & 15, lq = lane >> 4;
-    float* __restrict__ stD = smem + (size_t)wid * kStageFloats;
-    for (int i = lane; i < kStageFloats; i += 64) stD[i] = 0.f;   // the padding behind S stays zero (table_read3 may touch it with weight 0)
-    lds_fence_w();
-    float* __restrict__ wt = smem + 4 * kStageFloats + (size_t)wid * kDenseFloats;   // DENSE only
+    float* __restrict__ stD = smem + (size_t)wid * kStageFloats;   // (CACHED: no table area)
+    if constexpr (!CACHED) {
+        for (int i = lane; i < kStageFloats; i += 64) stD[i] = 0.f;   // the padding behind S stays zero (table_read3 may touch it with weight 0)
+        lds_fence_w();
+    }
+    float* __restrict__ wt = smem + (CACHED ? 0 : 4 * kStageFloats) + (size_t)wid * kDenseFloats;   // DENSE only
     const FieldDev& F = a.F;
     const int tiles_x = (a.img_w + 7) >> 3;
     const long long tile = (long long)blockIdx.x * 4 + wid;
@@ -358,7 +408,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DENSE ? T2N
                                  32 - __builtin_clz(f2) - __builtin_ctz(f2)) + 1;
             const bool ranged = !(bits & 0x40000000u);
             MT_T(p_axes);
-            if (ranged && span <= 4) {
+            if (CACHED && ranged && span <= 4) {
+                // both samples' eight loads in flight together; a lane without a sample reads the table's first cell
+                unsigned off[kSteps];
+                CellTaps ct[kSteps];
+#pragma unroll
+                for (int q = 0; q < kSteps; ++q) off[q] = ok[q] ? cached_offset(F, A[q]) : 0u;
+#pragma unroll
+                for (int q = 0; q < kSteps; ++q) ct[q] = cached_load(F, off[q]);
+                MT_T(p_build);
+#pragma unroll
+                for (int q = 0; q < kSteps; ++q)
+                    if (ok[q]) part[q] = cached_read3(A[q], ct[q]);
+                MT_T(p_read);
+            } else if (ranged && span <= 4) {
                 table_build<2>(F.den, amn, stD, l15, lq);
                 lds_fence_w();
                 {
@@ -604,6 +667,108 @@ __global__ __launch_bounds__(256) void k_dense_fill(const FieldDev F, const floa
     }
 }
 
+// ---- the cached summed table of a whole grid ------------------------------------------------------------------------------------
+// S[z][y][x] for 0 <= x <= grid[0], 0 <= y <= grid[1], 0 <= z <= grid[2] (one entry past the last texel per axis: the clamped texel
+// again, what table_build puts into a slot beyond the grid — a cell at the grid's last texel reads it with weight 0), each entry by
+// the marcher's own table_build<2> + table_sum<2> on a synthetic box origin: one wave per 4 x 4 x 4 box anchored at 4 b - shift per
+// axis (cut at 0). An entry is three 16-term dot products on v_mfma_f32_16x16x4_f32 — every output element of the instruction runs the
+// same four k-steps over the same operand values wherever it sits in the 16 x 16 block — and a fixed-order sum: its bits do not depend
+// on the box it was computed in (tests/test_density_cache.py builds with every shift and compares).
+struct SumTableArgs { FactorSet den; float* out; int n[3]; int nb[3]; int shift[3]; long long boxes; };
+__global__ __launch_bounds__(256) void k_density_sum_table(const SumTableArgs a) {
+    __shared__ __attribute__((aligned(16))) float smem[4 * kStageFloats];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const long long box = (long long)blockIdx.x * 4 + wid;
+    if (box >= a.boxes) return;
+    float* __restrict__ stD = smem + (size_t)wid * kStageFloats;
+    const int bx = (int)(box % a.nb[0]), by = (int)((box / a.nb[0]) % a.nb[1]), bz = (int)(box / ((long long)a.nb[0] * a.nb[1]));
+    const int o[3] = {4 * bx - a.shift[0], 4 * by - a.shift[1], 4 * bz - a.shift[2]};
+    const int amn[3] = {max(o[0], 0), max(o[1], 0), max(o[2], 0)};
+    table_build<2>(a.den, amn, stD, lane & 15, lane >> 4);
+    lds_fence_w();
+    table_sum<2>(stD, lane);
+    lds_fence_w();
+    const int x = amn[0] + (lane & 3), y = amn[1] + ((lane >> 2) & 3), z = amn[2] + (lane >> 4);
+    // the box's own cells (a box cut at 0 holds further cells of its neighbour: left to that one), inside the padded grid
+    if (x < o[0] + 4 && y < o[1] + 4 && z < o[2] + 4 && x <= a.n[0] && y <= a.n[1] && z <= a.n[2])
+        a.out[((size_t)z * (a.n[1] + 1) + y) * (a.n[0] + 1) + x] = stD[lane];
+}
+
+size_t density_cache_bytes(const t2n_field* f) {
+    const int* g = f->desc.grid;
+    return (size_t)(g[0] + 1) * (g[1] + 1) * (g[2] + 1) * sizeof(float);
+}
+
+int launch_density_sum_table(const t2n_field* f, float* out, const int shift[3], hipStream_t s) {
+    SumTableArgs a;
+    a.den = f->dev.den; a.out = out;
+    a.boxes = 1;
+    for (int k = 0; k < 3; ++k) {
+        if (shift[k] < 0 || shift[k] > 3) { set_error("density sum table: shift[%d]=%d outside [0, 3]", k, shift[k]); return T2N_ERR_INVALID; }
+        a.n[k] = f->desc.grid[k]; a.shift[k] = shift[k];
+        a.nb[k] = (a.n[k] + shift[k]) / 4 + 1;    // boxes b with 4 b - shift <= n
+        a.boxes *= a.nb[k];
+    }
+    hipLaunchKernelGGL(k_density_sum_table, dim3((unsigned)((a.boxes + 3) / 4)), dim3(256), 0, s, a);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
+void density_cache_release(t2n_field* f) {
+    if (f->dcache) { (void)hipDeviceSynchronize(); (void)hipFree(f->dcache); }
+    f->dcache = nullptr; f->dcache_bytes = 0; f->dcache_version = 0; f->dcache_seen = 0; f->dcache_alloc_failed = false;
+    f->dev.dsum = nullptr;
+}
+
+// Once per tile-marcher frame (t2n_render_forward), before its launches: f->dev.dsum = the cached table when it is current, else NULL.
+// The table is built by the SECOND consecutive frame that finds the density factors unchanged (a loop that alternates optimiser steps
+// and single frames never builds), on that frame's stream in front of its marcher; frames on other streams wait for the event behind
+// the build. A rebuild overwrites the buffer in place: every frame that read the old table was queued before the factors changed, and
+// whatever changed them was ordered behind those frames by the caller, as for the factor copies themselves.
+int density_cache_prepare(t2n_field* f, hipStream_t s) {
+    f->dev.dsum = nullptr;
+    const bool second = f->dcache_seen == f->den_version;   // an earlier tile-marcher frame saw these factors (cached or not)
+    f->dcache_seen = f->den_version;
+    if (!f->dcache_on) return T2N_OK;
+    const int* g = f->desc.grid;
+    const size_t bytes = density_cache_bytes(f);
+    size_t cap = f->dcache_cap;
+    if (!cap) {
+        static size_t dev_total = 0;
+        if (!dev_total) { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess) dev_total = tot; else (void)hipGetLastError(); }
+        cap = dev_total / 64;
+    }
+    // (cached_offset: 24-bit row counts and row bytes, 32-bit byte offsets)
+    const bool addressable = (size_t)(g[1] + 1) * (g[2] + 1) < (1u << 24) && bytes < (1ull << 32);
+    if ((size_t)g[0] * g[1] * g[2] * sizeof(float) > cap || !addressable) return T2N_OK;
+    if (f->dcache && f->dcache_version == f->den_version) {
+        if (f->dcache_stream != (void*)s) T2N_HIP(hipStreamWaitEvent(s, (hipEvent_t)f->dcache_ev, 0));
+    } else {
+        if (!second) return T2N_OK;   // first frame of this version
+        if (!f->dcache) {
+            if (f->dcache_alloc_failed) return T2N_OK;
+            if (hipMalloc((void**)&f->dcache, bytes + 16) != hipSuccess) {   // no room: the frames stay uncached
+                (void)hipGetLastError();
+                f->dcache = nullptr; f->dcache_alloc_failed = true;
+                return T2N_OK;
+            }
+            f->dcache_bytes = bytes + 16;
+        }
+        if (!f->dcache_ev) T2N_HIP(hipEventCreateWithFlags((hipEvent_t*)&f->dcache_ev, hipEventDisableTiming));
+        const int shift[3] = {0, 0, 0};
+        const int rc = launch_density_sum_table(f, f->dcache, shift, s);
+        if (rc) return rc;
+        T2N_HIP(hipEventRecord((hipEvent_t)f->dcache_ev, s));
+        f->dcache_stream = (void*)s;
+        f->dcache_version = f->den_version;
+        ++f->dcache_counts[2];
+    }
+    f->dev.dsum = f->dcache;
+    f->dev.ds_row = (unsigned)(g[0] + 1) * 4u;
+    f->dev.ds_slice = f->dev.ds_row * (unsigned)(g[1] + 1);
+    return T2N_OK;
+}
+
 int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h, float* spill, float4* scratch, hipStream_t s) {
     const int cap = L.n_samples / 4 > 0 ? L.n_samples / 4 : 1;
     unsigned* ovf_count = (unsigned*)((char*)scratch + (size_t)L.n_rays * cap * 16);
@@ -633,9 +798,12 @@ int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h
     if (L.weights || L.z_vals)
         hipLaunchKernelGGL(k_dense_fill, dim3((unsigned)((L.n_rays + 3) / 4)), dim3(256), 0, s, f->dev, L.rays, (long long)L.n_rays, L.ray_stride,
                            L.n_samples, L.weights, L.z_vals);
-    const size_t lds = (size_t)4 * (kStageFloats + (dense ? kDenseFloats : 0)) * sizeof(float);
+    const bool cached = f->dev.dsum != nullptr;
+    const size_t lds = (size_t)4 * ((cached ? 0 : kStageFloats) + (dense ? kDenseFloats : 0)) * sizeof(float);
     const bool mask = f->dev.alpha != nullptr, relu = f->dev.act == T2N_ACT_RELU;
-#define T2N_MT_LAUNCH(D, A, R) hipLaunchKernelGGL((k_march_tiles<D, A, R>), grid, dim3(256), lds, s, a)
+    ++f->dcache_counts[cached ? 0 : 1];
+#define T2N_MT_LAUNCH(D, A, R) do { if (cached) hipLaunchKernelGGL((k_march_tiles<D, A, R, true>), grid, dim3(256), lds, s, a); \
+                                    else hipLaunchKernelGGL((k_march_tiles<D, A, R, false>), grid, dim3(256), lds, s, a); } while (0)
     if (dense) { if (mask) { if (relu) T2N_MT_LAUNCH(true, true, true); else T2N_MT_LAUNCH(true, true, false); }
                  else { if (relu) T2N_MT_LAUNCH(true, false, true); else T2N_MT_LAUNCH(true, false, false); } }
     else { if (mask) { if (relu) T2N_MT_LAUNCH(false, true, true); else T2N_MT_LAUNCH(false, true, false); }

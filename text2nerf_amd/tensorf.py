@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import weakref
 import time
 from typing import Optional
 
@@ -113,11 +114,21 @@ def _ladder(n: int, step: float = 1.25, floor: int = 1024) -> int:
     return v
 
 
+_FIELDS = weakref.WeakSet()     # live fields: release_workspaces frees their cached density tables
+
+
 def release_workspaces(device=None, keep_current=True) -> int:
     """Drop the scratch buffers of `device` (all devices when None) — all of them, or all but the current stream's. Returns the bytes
     released to torch's caching allocator. For long runs that drove a field from many streams; a pipelined evaluation keeps its
-    side streams (renderer._FramePipe) and needs no call."""
+    side streams (renderer._FramePipe) and needs no call. The cached summed density tables of the live fields (TensorBase.density_cache)
+    are freed as well, whatever `keep_current` says (device allocations of the native field, not torch's: not part of the returned
+    count; see density_cache_counts()['bytes']): a field builds its table again on the second frame it renders."""
     freed = 0
+    for fld in list(_FIELDS):
+        h = getattr(fld, "_handle", None)
+        if h is None or (device is not None and str(fld._all_params()[0].device) != str(torch.device(device))):
+            continue
+        _lib.check(_lib.load().t2n_field_release_density_cache(h), "t2n_field_release_density_cache")
     for key in list(_WORKSPACE):
         d, st = key
         if device is not None and d != str(torch.device(device)):
@@ -403,6 +414,11 @@ class TensorBase(nn.Module):
         # 'fp32' (default) or 'bf16' (BASELINE configs[4]): the forward gathers read bf16 copies of the 12 factor tensors;
         # the render equals the fp32 render of the bf16-rounded tensors bit for bit, the parameters stay fp32 masters
         self.factor_storage = "fp32"
+        # Tile-marcher frames read the summed density table S = (D0 + D1) + D2 of the whole grid from a per-field cache, built by the
+        # second consecutive frame that finds the density factors unchanged (same frames bit for bit; False = every step pair builds its
+        # own piece). density_cache_cap_bytes: grids whose cells x 4 B exceed it are not cached (0 = 1/64 of the device's memory).
+        self.density_cache = True
+        self.density_cache_cap_bytes = 0
         # Early ray termination of eval renders that return neither weights nor z_vals (evaluation(), render_views, ...): OPT-IN. The
         # reference never terminates (models/tensorBase.py:19-26,494-505: every in-box sample is evaluated), so the default 0.0 is its
         # sample-for-sample arithmetic (exact evaluated-sample counts). A threshold eps > 0 stops a ray whose transmittance fell below it:
@@ -416,6 +432,8 @@ class TensorBase(nn.Module):
         self._gbuf_dirty = False
         self._gbuf_stale = False
         self.last_stats = None
+        self._dcache_base = [0, 0, 0]     # density-cache counters of the native fields this object has dropped (grid changes)
+        _FIELDS.add(self)
 
         if shadingMode not in _lib.SHADE_IDS:
             raise T2NError(f"shadingMode {shadingMode!r} is not implemented by the HIP renderer "
@@ -863,6 +881,7 @@ class TensorBase(nn.Module):
             self._storage_set = None
             self._frame_w_set = None
             self._staging_set = None
+            self._dcache_set = (True, 0)
             self._stage_shape_set = (0, 0)
             self._head_rows_set = 32
             self._alpha_key = "unset"
@@ -901,6 +920,11 @@ class TensorBase(nn.Module):
             _lib.check(lib.t2n_field_set_feature_staging(self._handle, 1 if self.feature_staging else 0),
                        "t2n_field_set_feature_staging")
             self._staging_set = bool(self.feature_staging)
+        dc = (bool(getattr(self, "density_cache", True)), int(getattr(self, "density_cache_cap_bytes", 0)))
+        if getattr(self, "_dcache_set", (True, 0)) != dc:
+            _lib.check(lib.t2n_field_set_density_cache(self._handle, 1 if dc[0] else 0), "t2n_field_set_density_cache")
+            _lib.check(lib.t2n_field_set_density_cache_cap(self._handle, dc[1]), "t2n_field_set_density_cache_cap")
+            self._dcache_set = dc
         shape = tuple(int(v) for v in self.feature_stage_shape)
         if getattr(self, "_stage_shape_set", (0, 0)) != shape:
             _lib.check(lib.t2n_field_set_feature_stage_shape(self._handle, shape[0], shape[1]), "t2n_field_set_feature_stage_shape")
@@ -1083,6 +1107,8 @@ class TensorBase(nn.Module):
         if self.__dict__.get("_gbuf_preseed") is not None:
             self._drop_preseed()      # a seed kernel in flight reads the old field and writes the old buffer
         if self._handle is not None:
+            c = self.density_cache_counts()
+            self._dcache_base = [c["cached"], c["uncached"], c["builds"]]
             _lib.load().t2n_field_destroy(self._handle)
             self._handle = None
             self._device_rows_ovf_seen = self._device_rows_issued = 0
@@ -1766,6 +1792,27 @@ class TensorBase(nn.Module):
         out = (C.c_uint64 * 2)()
         _lib.check(_lib.load().t2n_field_feature_staging_counts(self._handle, out), "t2n_field_feature_staging_counts")
         return (int(out[0]), int(out[1]))
+
+    def density_cache_counts(self):
+        """Tile-marcher launches served from the cached summed density table ('cached') and without it ('uncached'), table builds
+        ('builds') since this object was created, and the bytes the table holds now ('bytes'). Host-side counters: no device wait."""
+        base = self.__dict__.get("_dcache_base", [0, 0, 0])
+        out = (C.c_uint64 * 4)()
+        if self._handle is not None:
+            _lib.check(_lib.load().t2n_field_density_cache_counts(self._handle, out), "t2n_field_density_cache_counts")
+        return {"cached": base[0] + int(out[0]), "uncached": base[1] + int(out[1]), "builds": base[2] + int(out[2]), "bytes": int(out[3])}
+
+    def density_sum_table(self, shift=(0, 0, 0)):
+        """Diagnostic: the summed density table of the whole grid as the cache's builder computes it with its 4 x 4 x 4 boxes anchored at
+        4 b - shift per axis: a [grid z + 1, grid y + 1, grid x + 1] tensor (the last index of every axis repeats the clamped texel)."""
+        h = self.sync_params()
+        g = [int(v) for v in self.gridSize]
+        dev = self._all_params()[0].device
+        out = torch.empty((g[2] + 1, g[1] + 1, g[0] + 1), dtype=torch.float32, device=dev)
+        sh = (C.c_int * 3)(*[int(v) for v in shift])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().t2n_field_density_sum_table(h, sh, _lib.ptr(out), _lib.current_stream_ptr(dev)), "t2n_field_density_sum_table")
+        return out
 
 
 class TensorVMSplit(TensorBase):
