@@ -594,6 +594,34 @@ int t2n_depth_loss(int kind, const float* depth, const float* weights, const flo
                    int n_samples, float target_std, float* loss, double* aux, float* d_depth, float* d_weights, void* workspace,
                    size_t workspace_bytes, t2n_stream stream);
 
+/* The distortion regulariser of mip-NeRF 360 (eq. 15) on the weights along a ray (the reference has no such term). For one ray with
+ * ascending sample depths z_0 <= ... <= z_{N-1} (the renderer's z_vals), weights w_n and rho = inv_range = 1 / z_range:
+ *   intervals   delta_n = (z_{n+1} - z_n) rho for n < N-1, delta_{N-1} = 0 (the renderer's dists, the last one 0);
+ *   midpoints   m_n = ((z_n - z_0) + (z_{n+1} - z_n) / 2) rho, m_{N-1} = (z_{N-1} - z_0) rho (the term is translation-invariant);
+ *   loss        L_r = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 delta_i;
+ *   gradient    dL_r/dw_i = 2 sum_j w_j |m_i - m_j| + (2/3) w_i delta_i;
+ *   batch term  D = mean_r L_r; the gradient goes to the weights only (z_vals carry none).
+ * Evaluated in O(N) per ray by prefix sums of (w, w m) in sample order (which is why z_vals must ascend). float32 inputs, float64 from
+ * the first operation, sums in a fixed order without atomics (two calls give the same bits); the stored gradient and the reported
+ * loss are rounded to float32 once.
+ * t2n_distortion_loss: the term alone: loss[0] = D (device float) and, unless NULL, d_weights [R,N] = (1/R) dL_r/dw (upstream
+ * gradient 1; exact zeros on a ray without weight). workspace: t2n_distortion_loss_workspace_bytes(n_rays), 8-byte aligned. Python:
+ * losses.distortion_loss.
+ * t2n_train_loss_dist: t2n_train_loss_ex (every depth_kind 0..3) with w_dist D added: losses[4] keeps its layout, total additionally
+ * contains w_dist D; dist[0] = D, unweighted (device double); d_weights is still written once: float32(t2n_train_loss_ex's value +
+ * (w_dist / R) dL_r/dw); everything else is t2n_train_loss_ex's, bit for bit. With w_dist == 0 every output of t2n_train_loss_ex is
+ * bit-equal to that call's (dist[0] is still D). workspace: t2n_train_loss_dist_workspace_bytes(n_rays), 8-byte aligned.
+ * T2N_ERR_INVALID (before any launch): NULL / non-positive argument, inv_range not finite or <= 0, w_dist negative or not finite,
+ * t2n_train_loss_ex's own cases, misaligned workspace; T2N_ERR_WORKSPACE: workspace too small. */
+size_t t2n_distortion_loss_workspace_bytes(int64_t n_rays);
+int t2n_distortion_loss(const float* weights, const float* z_vals, int64_t n_rays, int n_samples, float inv_range, float* loss,
+                        float* d_weights, void* workspace, size_t workspace_bytes, t2n_stream stream);
+size_t t2n_train_loss_dist_workspace_bytes(int64_t n_rays);
+int t2n_train_loss_dist(const float* rgb, const float* depth, const float* weights, const float* z_vals, const float* rgb_t,
+                        const float* depth_t, int64_t n_rays, int n_samples, float w_depth, float w_trans, float delta, int depth_kind,
+                        float target_std, float w_dist, float inv_range, float* d_rgb, float* d_depth, float* d_weights, float* losses,
+                        double* aux, double* dist, void* workspace, size_t workspace_bytes, t2n_stream stream);
+
 /* ---- SURVEY.md 8(f-1), optional: the dense tail of the training step as streaming kernels.
  * t2n_tv_grad_add: grad += d/dparam [ weight * TVLoss(param) ] for one reference-layout plane [1,C,H,W]
  *   (utils.py:488-504; the driver's term is TV_loss_*(tvreg) * TV_weight with TV_loss_* = sum_planes 1e-2 * TVLoss,

@@ -173,6 +173,13 @@ SIGNATURES = {
     "t2n_depth_loss_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "t2n_depth_loss": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_distortion_loss_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "t2n_distortion_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                      C.c_void_p]),
+    "t2n_train_loss_dist_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "t2n_train_loss_dist": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float,
+                                      C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "t2n_field_set_factor_storage": (C.c_int, [C.c_void_p, C.c_int]),
     "t2n_frame_postprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float,
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

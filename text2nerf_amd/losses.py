@@ -298,3 +298,49 @@ def scale_shift_invariant_loss(z_vals, weights, target_depth):
     _device_rays("scale_shift_invariant_loss", z_vals=z_vals, weights=weights, target_depth=target_depth)
     loss, aux = _DepthLoss.apply(3, 0.0, None, weights, z_vals, target_depth)
     return loss, aux[0], aux[1]
+
+
+# ---- the distortion regulariser of mip-NeRF 360 on a ray's weights: one HIP call (t2n_distortion_loss) ----------------------------------
+class _DistortionLoss(torch.autograd.Function):
+    """D of include/t2n.h (t2n_distortion_loss) on the model of _DepthLoss: the forward call also writes d_weights for upstream
+    gradient 1 and keeps it; the backward multiplies it by grad_output. z_vals gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, inv_range, weights, z_vals):
+        lib = _lib.load()
+        dev = weights.device
+        w, z = (t.detach().to(torch.float32).contiguous() for t in (weights, z_vals))
+        R, N = int(w.shape[0]), int(w.shape[1])
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        d_w = torch.empty(R, N, device=dev, dtype=torch.float32) if ctx.needs_input_grad[1] else None
+        ws = torch.empty(int(lib.t2n_distortion_loss_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.t2n_distortion_loss(_lib.ptr(w), _lib.ptr(z), R, N, float(inv_range), _lib.ptr(loss), _lib.ptr(d_w), _lib.ptr(ws),
+                                               ws.numel(), _lib.current_stream_ptr(dev)), "t2n_distortion_loss")
+        ctx.d_w = d_w
+        ctx.like = (tuple(weights.shape), weights.dtype)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        g_w = None
+        if ctx.needs_input_grad[1]:
+            g_w = (ctx.d_w * grad_loss.detach().to(torch.float32)).reshape(ctx.like[0]).to(ctx.like[1])
+        return None, g_w, None
+
+
+def distortion_loss(weights, z_vals, z_range):
+    """The distortion regulariser of mip-NeRF 360 (eq. 15) on device tensors: mean over the rays of sum_ij w_i w_j |m_i - m_j| +
+    1/3 sum_i w_i^2 delta_i, with the sample midpoints m and intervals delta of `z_vals` ([R, N], ascending along a ray, as the
+    renderer returns them) divided by `z_range` (> 0; near_far[1] - near_far[0] of the field), the last interval 0 — the definition in
+    include/t2n.h. Returns a 0-d float32 loss; the gradient goes to `weights` alone. Device tensors only (no CPU fallback). Composes with
+    OctreeRender_trilinear_fast(..., is_train=True), which returns weights and z_vals, in an autograd loop;
+    TensorVMSplit.train_step(distortion=w) is the form without autograd."""
+    from ._lib import T2NError
+    _device_rays("distortion_loss", weights=weights, z_vals=z_vals)
+    if weights.dim() != 2 or tuple(weights.shape) != tuple(z_vals.shape) or weights.shape[1] == 0:
+        raise T2NError(f"distortion_loss: weights {tuple(weights.shape)} and z_vals {tuple(z_vals.shape)} must both be [R, N]")
+    z_range = float(z_range)
+    if not (z_range > 0.0 and z_range != float("inf")):
+        raise T2NError(f"distortion_loss: z_range must be finite and > 0, got {z_range}")
+    return _DistortionLoss.apply(1.0 / z_range, weights, z_vals)

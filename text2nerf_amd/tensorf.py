@@ -33,6 +33,14 @@ _SEED_MIN_RAYS = 8192
 _WORKSPACE = {}
 
 
+def _distortion_weight(w) -> float:
+    """train_step's `distortion` keyword as a float: finite and >= 0."""
+    w = float(w)
+    if not (0.0 <= w < float("inf")):
+        raise T2NError(f"distortion={w!r}: the weight of the distortion term must be finite and >= 0")
+    return w
+
+
 def _depth_kind(name) -> int:
     """depth_kind of t2n_train_loss_ex for train_step's `depth_loss` keyword."""
     kind = _lib.DEPTH_KINDS.get(name)
@@ -1502,8 +1510,27 @@ class TensorBase(nn.Module):
         return {"kernel_form": int(plan.kernel_form), "pass_rows": int(plan.pass_rows), "max_passes": int(plan.max_passes),
                 "workspace_bytes": int(plan.workspace_bytes)}
 
+    def _train_loss_dist(self, rgb, depth, w, z, rgb_t, dep_t, R, N, w_depth, w_trans, delta, kind, depth_std, distortion, d_rgb, d_depth, d_w,
+                         losses):
+        """The loss stage of a composed step with the distortion term (t2n_train_loss_dist, distortion > 0): sets `last_distortion` (D,
+        0-d float64, device) and, for a depth kind other than "mse", `last_depth_aux`."""
+        lib = _lib.load()
+        dev = rgb.device
+        inv_range = 1.0 / (float(self.near_far[1]) - float(self.near_far[0]))
+        lws = torch.empty(int(lib.t2n_train_loss_dist_workspace_bytes(R)), dtype=torch.uint8, device=dev)
+        aux = torch.empty(4, dtype=torch.float64, device=dev)
+        dist = torch.empty(1, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.t2n_train_loss_dist(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
+                                               float(w_depth), float(w_trans), float(delta), kind, float(depth_std), float(distortion),
+                                               inv_range, _lib.ptr(d_rgb), _lib.ptr(d_depth), _lib.ptr(d_w), _lib.ptr(losses), _lib.ptr(aux),
+                                               _lib.ptr(dist), _lib.ptr(lws), lws.numel(), _lib.current_stream_ptr(dev)), "t2n_train_loss_dist")
+        if kind != 0:
+            self.__dict__["last_depth_aux"] = aux
+        self.__dict__["last_distortion"] = dist.reshape(())
+
     def _general_train_step(self, rays, rgb_target, depth_target, optimizer, N_samples, white_bg, w_depth, w_trans, delta, tv, all_reduce,
-                            kind, depth_std, l1=(), ortho=()):
+                            kind, depth_std, l1=(), ortho=(), distortion=0.0):
         """train_step on a general-shape field, composed: _general_forward (train mode) -> t2n_train_loss[_ex] -> _general_backward ->
         .grad in the reference layouts -> all_reduce -> optimizer.step. The field's AlphaGridMask is honoured (the general kernels test
         it themselves)."""
@@ -1524,7 +1551,10 @@ class TensorBase(nn.Module):
             d_rgb, d_depth, d_w = torch.empty_like(rgb), torch.empty_like(depth), torch.empty_like(w)
             losses = torch.empty(4, device=dev)
             st = _lib.current_stream_ptr(dev)
-            if kind == 0:
+            if distortion > 0:
+                self._train_loss_dist(rgb, depth, w, z, rgb_t, dep_t, R, N, w_depth, w_trans, delta, kind, depth_std, distortion, d_rgb, d_depth,
+                                      d_w, losses)
+            elif kind == 0:
                 lws = torch.empty(int(lib.t2n_train_loss_workspace_bytes(R)), dtype=torch.uint8, device=dev)
                 with torch.cuda.device(dev):
                     _lib.check(lib.t2n_train_loss(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
@@ -1549,7 +1579,7 @@ class TensorBase(nn.Module):
 
     def train_step(self, rays, rgb_target, depth_target, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
                    tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None, depth_loss="mse",
-                   depth_std=0.1, l1=(), ortho=()):
+                   depth_std=0.1, l1=(), ortho=(), distortion=0.0):
         """One optimisation step of text2nerf_main.py:547-590 without the autograd graph: render (train mode, CPU-generator jitter
         like models/tensorBase.py:313-317) -> the driver's loss as ONE kernel that emits d_rgb / d_depth / d_weights
         (t2n_train_loss) -> t2n_render_backward -> optimizer.step(). `optimizer`: optim.TVAdam(field=self) (TV terms via `tv`, as
@@ -1586,23 +1616,31 @@ class TensorBase(nn.Module):
         ortho) builds both for the reference's two scalars. Applied on every route (the one-call step: inside its seed launch plus two
         launches for the six lines; the composed step: t2n_field_reg_seed / t2n_field_reg_adam_step; general shapes: the reference-layout
         kernels of optim.TVAdam). Like TV they are not part of the returned `total`; weights may change from step to step. With a
-        non-zero weight, `graph=True`, a sharded exchange and an optimiser other than optim.TVAdam raise T2NError."""
+        non-zero weight, `graph=True`, a sharded exchange and an optimiser other than optim.TVAdam raise T2NError.
+        `distortion`: weight of the distortion regulariser of mip-NeRF 360 on the rays' weights (losses.distortion_loss; the definition is
+        in include/t2n.h), with z_range = near_far[1] - near_far[0] of the field. With a weight > 0 the loss stage is t2n_train_loss_dist
+        (every `depth_loss`, both composed routes, `speculative` included): `total` additionally contains distortion * D and
+        `self.last_distortion` is D of the batch, unweighted, as a 0-d device float64 tensor (None otherwise). The one-call step has
+        its loss folded into the backward: `fused=None` takes the composed route, `fused=True` and `graph=True` raise T2NError. With
+        the keyword omitted or 0 the step makes exactly the calls it makes without it."""
         lib = _lib.load()
         params = self._autograd_params()
         kind = _depth_kind(depth_loss)
+        distortion = _distortion_weight(distortion)
         self.__dict__["last_depth_aux"] = None
+        self.__dict__["last_distortion"] = None
         l1, ortho = _live_terms(l1), _live_terms(ortho)
         if l1 or ortho:
             _check_reg_route(optimizer, graph, all_reduce)
             if getattr(optimizer, "field", None) is self:
                 self._reg_weights(l1, ortho)       # (entries other than the field's own lists: refused before anything is drawn or queued)
-        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, kind)
+        fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, kind, distortion)
         if fuse is not None:
             fs, N, flags, use_graph = fuse
             return fs.step(rays, rgb_target, depth_target, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce, l1=l1, ortho=ortho)
         if self._is_general():     # (speculative / graph: forms of the tuned backward and of the one-call step, no effect here)
             return self._general_train_step(rays, rgb_target, depth_target, optimizer, N_samples, white_bg, w_depth, w_trans, delta, tv,
-                                            all_reduce, kind, depth_std, l1, ortho)
+                                            all_reduce, kind, depth_std, l1, ortho, distortion)
         if any(not p.is_leaf for p in params):
             raise T2NError("train_step needs the kernels' own field shape (the parameters ARE the kernel tensors); embedded shapes, "
                            "TensorVM and TensorCP train through the autograd form (OctreeRender_trilinear_fast + loss.backward())")
@@ -1635,7 +1673,10 @@ class TensorBase(nn.Module):
             rgb, depth, z, w, ws = self._render_raw(rays, N, flags, jitter, True, keep_ctx=True, reuse_ctx=True)
             d_rgb, d_depth, d_w = torch.empty_like(rgb), torch.empty_like(depth), torch.empty_like(w)
             losses = torch.empty(4, device=dev)
-            if kind == 0:
+            if distortion > 0:
+                self._train_loss_dist(rgb, depth, w, z, rgb_t, dep_t, R, N, w_depth, w_trans, delta, kind, depth_std, distortion, d_rgb, d_depth,
+                                      d_w, losses)
+            elif kind == 0:
                 lws = torch.empty(int(lib.t2n_train_loss_workspace_bytes(R)), dtype=torch.uint8, device=dev)
                 with torch.cuda.device(dev):
                     _lib.check(lib.t2n_train_loss(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(w), _lib.ptr(z), _lib.ptr(rgb_t), _lib.ptr(dep_t), R, N,
@@ -1690,7 +1731,7 @@ class TensorBase(nn.Module):
 
     def train_step_indexed(self, source, ids, optimizer, N_samples=-1, white_bg=True, w_depth=0.005, w_trans=1e3, delta=0.1,
                            tv=(), all_reduce=None, all_reduce_averages=True, speculative=False, fused=None, graph=None, depth_loss="mse",
-                           depth_std=0.1, l1=(), ortho=()):
+                           depth_std=0.1, l1=(), ortho=(), distortion=0.0):
         """`train_step` on rows `ids` of a `dataset.DeviceTrainSet` (rays, colours and depths kept on the device): same keyword
         arguments, same arithmetic, same draws from the CPU generator in the same order. `ids`: an int64 (as SimpleSampler returns it) or
         int32 tensor. On the host its range is checked before anything is drawn or queued — an id outside [0, len(source)) or a
@@ -1700,23 +1741,27 @@ class TensorBase(nn.Module):
         the fused step does not apply this is `train_step(*source.rows(ids), ...)`."""
         from .dataset import check_ids
         ids = check_ids(ids, len(source))
+        distortion = _distortion_weight(distortion)
         self.__dict__["last_depth_aux"] = None
+        self.__dict__["last_distortion"] = None
         l1, ortho = _live_terms(l1), _live_terms(ortho)
         if l1 or ortho:
             _check_reg_route(optimizer, graph, all_reduce)
             if getattr(optimizer, "field", None) is self:
                 self._reg_weights(l1, ortho)       # (entries other than the field's own lists: refused before anything is drawn or queued)
         fuse = self._fused_step_for(optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph,
-                                    _depth_kind(depth_loss))
+                                    _depth_kind(depth_loss), distortion)
         if fuse is not None:
             fs, N, flags, use_graph = fuse
             return fs.step_indexed(source, ids, N, flags, w_depth, w_trans, delta, tv, use_graph, all_reduce, l1=l1, ortho=ortho)
         rays, rgb_t, dep_t = source.rows(ids)
         return self.train_step(rays, rgb_t, dep_t, optimizer, N_samples=N_samples, white_bg=white_bg, w_depth=w_depth, w_trans=w_trans,
                                delta=delta, tv=tv, all_reduce=all_reduce, all_reduce_averages=all_reduce_averages, speculative=speculative,
-                               fused=False if fused is None else fused, graph=graph, depth_loss=depth_loss, depth_std=depth_std, l1=l1, ortho=ortho)
+                               fused=False if fused is None else fused, graph=graph, depth_loss=depth_loss, depth_std=depth_std, l1=l1, ortho=ortho,
+                               distortion=distortion)
 
-    def _fused_step_for(self, optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, depth_kind=0):
+    def _fused_step_for(self, optimizer, N_samples, white_bg, all_reduce, all_reduce_averages, speculative, fused, graph, depth_kind=0,
+                        distortion=0.0):
         """The fuse decision of train_step / train_step_indexed: None (the composed step), or (the field's FusedStep for this optimiser,
         N, flags, use_graph) with the background coin drawn — the first draw of a fused step from the CPU generator. A depth term other
         than "mse" (depth_kind != 0) cannot fuse: the one-call step's loss is folded into its backward."""
@@ -1724,6 +1769,12 @@ class TensorBase(nn.Module):
             if fused:
                 raise T2NError("train_step(fused=True): the one-call step computes the \"mse\" depth term only; depth_loss=gnll / si_log / ssi "
                                "runs on the composed route (fused=None or False)")
+            return None
+        if distortion > 0:
+            if fused or graph:
+                raise T2NError(f"train_step({'fused' if fused else 'graph'}=True): the one-call step and its graph form have their loss folded "
+                               "into the backward and carry no distortion term; distortion > 0 runs on the composed route (fused=None or "
+                               "False, graph=None or False)")
             return None
         can_fuse = self._can_fuse_train_step(optimizer) and (all_reduce is None or all_reduce_averages) and not speculative
         if fused and not can_fuse:
