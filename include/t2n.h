@@ -200,6 +200,43 @@ int t2n_field_set_density_cache_cap(t2n_field* f, uint64_t bytes);
 int t2n_field_release_density_cache(t2n_field* f);
 int t2n_field_density_cache_counts(const t2n_field* f, uint64_t out[4]);
 int t2n_field_density_sum_table(const t2n_field* f, const int* shift, float* out, t2n_stream stream);
+/* Cached appearance feature volume of the tile-marcher frames (T2N_FLAG_COHERENT eval frames, fused MLP_Fea_noview head on split
+ * products). The 27 appearance features of a sample are the trilinear interpolation of a per-corner volume
+ * F_j(corner) = sum_k sum_c basis_mat[j, 48 k + c] P_k[corner][c] L_k[corner][c], a function of the appearance factors and basis_mat
+ * alone. With the volume on (default of a new handle) the min_frames-th CONSECUTIVE tile-marcher frame that finds those tensors
+ * unchanged builds F for the whole grid ((grid + 1)^3 corners x 32 floats in a buffer the field owns, on that frame's stream), and the
+ * feature stage of the frames after it reads eight corners per sample there until the tensors change (t2n_field_upload[_head], the field
+ * Adam steps, t2n_train_step and its graph replay, a t2n_field_factor_buffer view of an appearance tensor). Frames of one version before
+ * and after the build differ by rounding only (the interpolation's eight extra multiply-adds per feature); depth, acc, lists and counters
+ * are the same bits. The training forward, explicit points and per-ray-marcher launches always run the direct form, as do tiles past
+ * the feature-row capacity; the rays the budgeted lists leave to the finisher read the volume like the rest of their frame.
+ * Where a frame can hold rows of both forms (they differ by rounding, ~1e-7 in rgb): (a) a volume frame with more appearance tiles than
+ * its feature rows hold (32 rows per ray + 1024 with worst-case lists, half the budget per ray + 1024 with budgeted ones) — the
+ * surplus tiles take the one-kernel direct path, so a budgeted and a worst-case volume frame of such a scene need not be equal bit for
+ * bit; (b) an image that the caller splits over several t2n_render_forward calls: every call counts as a frame, and the min_frames-th
+ * call may fall inside the image. Callers that need bit-stable frames switch the volume off or set min_frames = 1.
+ * Footprint: the buffer (3.49 GB at 300^3) is a device allocation of the field outside any caller's allocator; it stays allocated,
+ * unread, while the tensors change (training steps between evaluations) and is rebuilt in place by the next run of min_frames frames;
+ * t2n_field_release_appearance_volume gives it back.
+ * min_frames = 0 restores the default
+ * (T2N_APP_VOLUME_MIN_FRAMES = build time / per-frame saving, measured at C2); a loop that alternates optimiser steps and single frames
+ * never builds. Not built: grids whose cells x 128 B exceed the cap (t2n_field_set_appearance_volume_cap; 0 = the default, 1/64 of the
+ * device's memory) or leave 32-bit byte offsets, a failed allocation, volume switched off, other heads.
+ * t2n_field_release_appearance_volume frees the buffer (waits for the device).
+ * t2n_field_appearance_volume_counts: out[0] = bytes the buffer holds now, out[1] = builds, out[2] / out[3] = tile-marcher frames that
+ * read the volume / ran the direct form (host-side counters: no device wait). */
+#define T2N_APP_VOLUME_MIN_FRAMES 33   /* 4.9 ms build / 0.149 ms saved per C2 frame (profiles/appearance_volume_ab.txt) */
+int t2n_field_set_appearance_volume(t2n_field* f, int on, int min_frames);
+int t2n_field_set_appearance_volume_cap(t2n_field* f, uint64_t bytes);
+int t2n_field_release_appearance_volume(t2n_field* f);
+int t2n_field_appearance_volume_counts(const t2n_field* f, uint64_t out[4]);
+/* DIAGNOSTIC, for tests of the feature stage: the stage alone on caller-made appearance lists. app_pos: device [8][list_cap] entries
+ * (x, y, z normalised to [-1, 1], compositing weight); counters: device block of 8 x 64 words, word 64 l = entries of sub-list l (word 32
+ * is the stage's f16-range flag: zero it); feat: device [feat_rows][32] rows, row 32 t + s = entry s of tile t, tiles numbered through
+ * the sub-lists in order (a sub-list's last tile is padded with zero-weight rows); feat_rows a multiple of 32 that covers the tiles.
+ * volume = 0: the direct form; 1: the rows from the cached feature volume, built here if it is not current. */
+int t2n_field_feature_rows(t2n_field* f, const float* app_pos, const uint32_t* counters, uint32_t list_cap, int volume, float* feat,
+                           uint32_t feat_rows, t2n_stream stream);
 /* DIAGNOSTIC, for tests of the feature stage's tile queue only (like the staging counters above, not part of the rendering API): the
  * shape of the feature stage's launch. At most `workgroups` workgroups of eight waves (0 = the default, 512), and `defer_cap` tiles
  * (1 .. 64; 0 = the default, 16) that a wave sets aside for its gathered loop before it drains them. Small values make one wave see

@@ -123,6 +123,7 @@ int launch_relayout(t2n_field* f, const t2n_field_params* p, hipStream_t s) {
     }
     m.block0[m.count] = blocks;
     ++f->den_version;   // the density factors change: the cached summed table (density_cache_prepare) is stale
+    ++f->app_version;   // ... and the appearance factors: the cached feature volume (appearance_volume_prepare)
     if (blocks) hipLaunchKernelGGL(k_relayout, dim3(blocks), dim3(256), 0, s, m);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
@@ -439,6 +440,8 @@ extern "C" int t2n_field_destroy(t2n_field* f) {
     if (f->staging_counts) (void)hipFree(f->staging_counts);
     if (f->dcache) (void)hipFree(f->dcache);
     if (f->dcache_ev) (void)hipEventDestroy((hipEvent_t)f->dcache_ev);
+    if (f->avol) (void)hipFree(f->avol);
+    if (f->avol_ev) (void)hipEventDestroy((hipEvent_t)f->avol_ev);
     if (f->reg_ws) (void)hipFree(f->reg_ws);
     if (f->buf_mlp_h) (void)hipFree(f->buf_mlp_h);
     if (f->buf_ss) (void)hipFree(f->buf_ss);
@@ -754,6 +757,10 @@ extern "C" int t2n_render_forward(t2n_field* f, const float* rays, int64_t n_ray
         }
     }
     if (tiles) { const int rc = density_cache_prepare(f, s); if (rc) return rc; }   // once per frame, whatever its sub-launches
+    // the feature stage's form for this frame: the cached volume (tile-marcher frames of an unchanged field) or the direct gather; every
+    // other call — training forward, per-ray marcher — keeps the direct form
+    AvolScope avol_scope{f};
+    if (tiles) { const int rc = appearance_volume_prepare(f, s); if (rc) return rc; }
     char* ws = (char*)workspace;
     for (int64_t off = 0; off < n_rays; off += per) {
         const int64_t cnt = (n_rays - off) < per ? (n_rays - off) : per;
@@ -951,6 +958,47 @@ extern "C" int t2n_field_density_cache_counts(const t2n_field* f, uint64_t out[4
     if (!f || !out) { set_error("t2n_field_density_cache_counts: NULL argument"); return T2N_ERR_INVALID; }
     out[0] = f->dcache_counts[0]; out[1] = f->dcache_counts[1]; out[2] = f->dcache_counts[2]; out[3] = (uint64_t)f->dcache_bytes;
     return T2N_OK;
+}
+// ---- cached appearance feature volume of the tile-marcher frames (t2n_app_volume.hip) ----------------------------------------------
+extern "C" int t2n_field_set_appearance_volume(t2n_field* f, int on, int min_frames) {
+    if (!f || min_frames < 0) { set_error("t2n_field_set_appearance_volume: NULL field or min_frames < 0"); return T2N_ERR_INVALID; }
+    f->avol_on = on ? 1 : 0;
+    f->avol_min_frames = min_frames ? min_frames : T2N_APP_VOLUME_MIN_FRAMES;
+    return T2N_OK;
+}
+extern "C" int t2n_field_set_appearance_volume_cap(t2n_field* f, uint64_t bytes) {
+    if (!f) { set_error("t2n_field_set_appearance_volume_cap: NULL field"); return T2N_ERR_INVALID; }
+    f->avol_cap = (size_t)bytes;
+    f->avol_alloc_failed = false;
+    return T2N_OK;
+}
+extern "C" int t2n_field_release_appearance_volume(t2n_field* f) {
+    if (!f) { set_error("t2n_field_release_appearance_volume: NULL field"); return T2N_ERR_INVALID; }
+    appearance_volume_release(f);
+    return T2N_OK;
+}
+extern "C" int t2n_field_appearance_volume_counts(const t2n_field* f, uint64_t out[4]) {
+    if (!f || !out) { set_error("t2n_field_appearance_volume_counts: NULL argument"); return T2N_ERR_INVALID; }
+    out[0] = (uint64_t)f->avol_bytes; out[1] = f->avol_counts[2]; out[2] = f->avol_counts[0]; out[3] = f->avol_counts[1];
+    return T2N_OK;
+}
+extern "C" int t2n_field_feature_rows(t2n_field* f, const float* app_pos, const uint32_t* counters, uint32_t list_cap, int volume, float* feat,
+                                      uint32_t feat_rows, t2n_stream stream) {
+    if (!f || !app_pos || !counters || !feat || feat_rows % 32u) { set_error("t2n_field_feature_rows: bad argument"); return T2N_ERR_INVALID; }
+    if (!f->uploaded) { set_error("t2n_field_feature_rows: the field has no uploaded parameters"); return T2N_ERR_STATE; }
+    if (f->desc.shading != T2N_SHADE_MLP_FEA_NOVIEW || !f->mlp_split) { set_error("t2n_field_feature_rows: needs the fused MLP_Fea_noview head on split products"); return T2N_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    AvolScope avol_scope{f};
+    f->dev.avol = nullptr;
+    if (volume) {   // the volume current whatever the frame count (built here when it is stale)
+        const int on = f->avol_on, mf = f->avol_min_frames;
+        f->avol_on = 1; f->avol_min_frames = 1;
+        const int rc = appearance_volume_prepare(f, s);
+        f->avol_on = on; f->avol_min_frames = mf;
+        if (rc) return rc;
+        if (!f->dev.avol) { set_error("t2n_field_feature_rows: this field gets no feature volume (cap, addressing, allocation)"); return T2N_ERR_UNSUPPORTED; }
+    }
+    return launch_feature_rows(f, (const float4*)app_pos, counters, list_cap, feat, feat_rows, s);
 }
 extern "C" int t2n_field_density_sum_table(const t2n_field* f, const int* shift, float* out, t2n_stream stream) {
     if (!f || !shift || !out) { set_error("t2n_field_density_sum_table: NULL argument"); return T2N_ERR_INVALID; }

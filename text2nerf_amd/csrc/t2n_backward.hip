@@ -1810,6 +1810,7 @@ extern "C" int t2n_field_factor_buffer(const t2n_field* f, int t, void** ptr) {
     if (!f->uploaded || f->factor_bf16) { set_error("t2n_field_factor_buffer: needs an uploaded field with fp32 factor storage"); return T2N_ERR_STATE; }
     float* const* tab[4] = {f->buf_den_plane, f->buf_den_line, f->buf_app_plane, f->buf_app_line};
     if (t < 6) ++const_cast<t2n_field*>(f)->den_version;   // a writable view of a density tensor leaves the library: whatever was cached from it is stale
+    if (t >= 6) ++const_cast<t2n_field*>(f)->app_version;   // (an appearance tensor: the cached feature volume)
     *ptr = (void*)tab[t / 3][t % 3];
     return T2N_OK;
 }

@@ -56,6 +56,10 @@ struct FieldDev {
     // entry of every axis a copy of the clamped one; NULL = the marcher builds its 4 x 4 x 4 piece per step pair. Set per call by
     // t2n_render_forward (density_cache_prepare); ds_row / ds_slice: BYTES between y and z neighbours.
     const float* dsum; unsigned ds_row, ds_slice;
+    // cached appearance feature volume (t2n_app_volume.hip): [gz + 1][gy + 1][gx + 1][32] floats, the 27 features of every grid corner;
+    // NULL = the feature stage runs its direct form. Set per call by t2n_render_forward (appearance_volume_prepare); av_row / av_slice:
+    // BYTES between y and z neighbours.
+    const float* avol; unsigned av_row, av_slice;
 };
 
 // Device-side state of the fused training step (t2n_train_step): one 256-B block per field. k_train_plan advances it once per step;
@@ -157,6 +161,15 @@ struct t2n_field {
     bool dcache_alloc_failed = false;
     void* dcache_ev = nullptr; void* dcache_stream = nullptr;   // the build's stream + an event behind it: a frame on another stream waits for it
     unsigned long long dcache_counts[3] = {0, 0, 0};   // tile-marcher frames served from the cache / without it, builds
+    // cached appearance feature volume (t2n_field_set_appearance_volume, t2n_app_volume.hip): a function of the appearance factors and
+    // basis_mat alone, built by the avol_min_frames-th consecutive tile-marcher frame that finds app_version unchanged; every launcher
+    // that writes the device copies of those tensors bumps app_version
+    float* avol = nullptr; size_t avol_bytes = 0;
+    unsigned long long app_version = 1, avol_version = 0, avol_seen = 0, avol_run = 0;   // tensors now / the volume's / the last tile frame's / consecutive tile frames of avol_seen
+    int avol_on = 1, avol_min_frames = T2N_APP_VOLUME_MIN_FRAMES; size_t avol_cap = 0;   // cap in bytes on grid cells x 128 B (0 = 1/64 of the device's memory)
+    bool avol_alloc_failed = false;
+    void* avol_ev = nullptr; void* avol_stream = nullptr;
+    unsigned long long avol_counts[3] = {0, 0, 0};     // tile-marcher frames that read the volume / ran the direct form, builds
 };
 
 namespace t2n {
@@ -201,6 +214,28 @@ size_t density_cache_bytes(const t2n_field* f);
 int density_cache_prepare(t2n_field* f, hipStream_t s);
 void density_cache_release(t2n_field* f);
 int launch_density_sum_table(const t2n_field* f, float* out, const int shift[3], hipStream_t s);
+// the cached appearance feature volume (t2n_app_volume.hip). appearance_volume_prepare: called once per tile-marcher frame; sets f->dev.avol
+// (NULL = direct frame). launch_app_features_vol: the feature stage's second form, rows of tiles [0, tile_hi) from the volume
+// layout of the volume, shared by its builder, the read kernel (t2n_app_volume.hip) and k_finish_rays (t2n_shade.hip): kAvStride floats
+// per corner, channel quads of 16 B, channels past the 27 features zero. 32 = one 128-B line per corner; 28 (112 B, a corner straddling
+// two lines three times out of four) ran the C2 frame's rows 2 % slower, 0.277 against 0.272 ms (profiles/appearance_volume_ab.txt)
+#ifndef T2N_AVOL_STRIDE
+#define T2N_AVOL_STRIDE 32
+#endif
+constexpr int kAvStride = T2N_AVOL_STRIDE;
+constexpr int kAvFeatures = 27;
+constexpr unsigned kAvCornerBytes = kAvStride * sizeof(float);
+static_assert(kAvStride % 4 == 0 && kAvStride >= 28 && kAvStride <= 32, "corner stride: whole quads that hold the 27 features");
+// t2n_render_forward / t2n_field_feature_rows: the volume is offered to the launches of ONE call
+struct AvolScope { t2n_field* f; ~AvolScope() { f->dev.avol = nullptr; } };
+size_t appearance_volume_bytes(const t2n_field* f);
+int appearance_volume_prepare(t2n_field* f, hipStream_t s);
+void appearance_volume_release(t2n_field* f);
+int launch_app_volume_build(const t2n_field* f, float* out, hipStream_t s);
+int launch_app_features_vol(t2n_field* f, const float4* app_pos, const unsigned* counters_dev, unsigned list_cap, unsigned tile_hi, float* feat,
+                            hipStream_t s);
+int launch_feature_rows(t2n_field* f, const float4* app_pos, const unsigned* counters_dev, unsigned list_cap, float* feat, unsigned feat_rows,
+                        hipStream_t s);   // (t2n_shade.hip) the feature stage alone on caller-made lists, in the form f->dev.avol selects
 int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h, float* spill, float4* scratch, hipStream_t s);
 constexpr int kLists = 8;   // appearance sub-lists per sub-launch
 constexpr int kCounterStride = 64;   // unsigned words between sub-list counters: one 256-B line each (same-line atomics serialise)

@@ -353,6 +353,7 @@ static int field_adam_step(const char* who, t2n_field* f, const t2n_field_params
     if (tb) hipLaunchKernelGGL(k_tv_grad_cl_multi, dim3(tb), dim3(256), 0, s, A);
     if (ortho_den != 0.f || ortho_app != 0.f) { const int rc = launch_ortho_lines(f, ortho_den, ortho_app, nullptr, s); if (rc) return rc; }
     ++f->den_version;   // (the cached summed density table is stale)
+    ++f->app_version;   // (and the cached appearance feature volume)
     hipLaunchKernelGGL(k_adam_cl_multi, dim3(ab), dim3(256), 0, s, A);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
@@ -507,6 +508,7 @@ int launch_factor_adam_dev(t2n_field* f, const t2n_field_params* params, float* 
         for (int i = first + count + 1; i <= 12; ++i) A.ablock0[i] = 0xffffffffu;
     }
     if (first < 6) ++f->den_version;   // density planes / lines among the tensors: the cached summed density table is stale
+    if (first + count > 6) ++f->app_version;   // appearance planes / lines among them: the cached feature volume is stale
     if (b1 > b0) hipLaunchKernelGGL(k_adam_cl_multi, dim3(b1 - b0), dim3(256), 0, s, A);
     T2N_HIP(hipGetLastError());
     return T2N_OK;

@@ -526,6 +526,7 @@ extern "C" int t2n_train_graph_launch(t2n_train_graph* g, t2n_stream stream) {
         f->train_packed = true;
     }
     ++f->den_version;   // the replayed step's Adam kernels rewrite the density factors (no launcher runs): the cached summed density table is stale
+    ++f->app_version;   // ... and the appearance factors and basis_mat: the cached feature volume too
     T2N_HIP(hipGraphLaunch(g->exec, (hipStream_t)stream));
     return T2N_OK;
 }

@@ -137,6 +137,7 @@ def release_workspaces(device=None, keep_current=True) -> int:
         if h is None or (device is not None and str(fld._all_params()[0].device) != str(torch.device(device))):
             continue
         _lib.check(_lib.load().t2n_field_release_density_cache(h), "t2n_field_release_density_cache")
+        _lib.check(_lib.load().t2n_field_release_appearance_volume(h), "t2n_field_release_appearance_volume")
     for key in list(_WORKSPACE):
         d, st = key
         if device is not None and d != str(torch.device(device)):
@@ -427,6 +428,14 @@ class TensorBase(nn.Module):
         # own piece). density_cache_cap_bytes: grids whose cells x 4 B exceed it are not cached (0 = 1/64 of the device's memory).
         self.density_cache = True
         self.density_cache_cap_bytes = 0
+        # Tile-marcher frames of the fused MLP_Fea_noview head read their appearance feature rows from a cached per-corner feature volume
+        # (27 features per grid corner, trilinear fetch), built by the appearance_volume_min_frames-th consecutive frame that finds the
+        # appearance factors and basis_mat unchanged (0 = the library's default: build time / per-frame saving). Frames before and after
+        # the build differ by rounding only; False = every frame gathers and multiplies. appearance_volume_cap_bytes: grids whose cells
+        # x 128 B exceed it are not cached (0 = 1/64 of the device's memory). See appearance_volume_counts().
+        self.appearance_volume = True
+        self.appearance_volume_min_frames = 0
+        self.appearance_volume_cap_bytes = 0
         # Early ray termination of eval renders that return neither weights nor z_vals (evaluation(), render_views, ...): OPT-IN. The
         # reference never terminates (models/tensorBase.py:19-26,494-505: every in-box sample is evaluated), so the default 0.0 is its
         # sample-for-sample arithmetic (exact evaluated-sample counts). A threshold eps > 0 stops a ray whose transmittance fell below it:
@@ -890,6 +899,7 @@ class TensorBase(nn.Module):
             self._frame_w_set = None
             self._staging_set = None
             self._dcache_set = (True, 0)
+            self._avol_set = (True, 0, 0)
             self._stage_shape_set = (0, 0)
             self._head_rows_set = 32
             self._alpha_key = "unset"
@@ -933,6 +943,12 @@ class TensorBase(nn.Module):
             _lib.check(lib.t2n_field_set_density_cache(self._handle, 1 if dc[0] else 0), "t2n_field_set_density_cache")
             _lib.check(lib.t2n_field_set_density_cache_cap(self._handle, dc[1]), "t2n_field_set_density_cache_cap")
             self._dcache_set = dc
+        av = (bool(getattr(self, "appearance_volume", True)), int(getattr(self, "appearance_volume_min_frames", 0)),
+              int(getattr(self, "appearance_volume_cap_bytes", 0)))
+        if getattr(self, "_avol_set", (True, 0, 0)) != av:
+            _lib.check(lib.t2n_field_set_appearance_volume(self._handle, 1 if av[0] else 0, av[1]), "t2n_field_set_appearance_volume")
+            _lib.check(lib.t2n_field_set_appearance_volume_cap(self._handle, av[2]), "t2n_field_set_appearance_volume_cap")
+            self._avol_set = av
         shape = tuple(int(v) for v in self.feature_stage_shape)
         if getattr(self, "_stage_shape_set", (0, 0)) != shape:
             _lib.check(lib.t2n_field_set_feature_stage_shape(self._handle, shape[0], shape[1]), "t2n_field_set_feature_stage_shape")
@@ -1852,6 +1868,14 @@ class TensorBase(nn.Module):
         if self._handle is not None:
             _lib.check(_lib.load().t2n_field_density_cache_counts(self._handle, out), "t2n_field_density_cache_counts")
         return {"cached": base[0] + int(out[0]), "uncached": base[1] + int(out[1]), "builds": base[2] + int(out[2]), "bytes": int(out[3])}
+
+    def appearance_volume_counts(self):
+        """The cached appearance feature volume of the current native field: bytes it holds now ('bytes'), builds ('builds'), tile-marcher
+        frames that read it ('volume') and that ran the direct form ('direct'). Host-side counters: no device wait."""
+        out = (C.c_uint64 * 4)()
+        if self._handle is not None:
+            _lib.check(_lib.load().t2n_field_appearance_volume_counts(self._handle, out), "t2n_field_appearance_volume_counts")
+        return {"bytes": int(out[0]), "builds": int(out[1]), "volume": int(out[2]), "direct": int(out[3])}
 
     def density_sum_table(self, shift=(0, 0, 0)):
         """Diagnostic: the summed density table of the whole grid as the cache's builder computes it with its 4 x 4 x 4 boxes anchored at
