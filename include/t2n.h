@@ -211,7 +211,7 @@ int t2n_field_density_sum_table(const t2n_field* f, const int* shift, float* out
  * are the same bits. The training forward, explicit points and per-ray-marcher launches always run the direct form, as do tiles past
  * the feature-row capacity; the rays the budgeted lists leave to the finisher read the volume like the rest of their frame.
  * Where a frame can hold rows of both forms (they differ by rounding, ~1e-7 in rgb): (a) a volume frame with more appearance tiles than
- * its feature rows hold (32 rows per ray + 1024 with worst-case lists, half the budget per ray + 1024 with budgeted ones) — the
+ * its feature rows hold (32 rows per ray + 1024 with worst-case lists; budgeted lists hold a row per list slot and have none) — the
  * surplus tiles take the one-kernel direct path, so a budgeted and a worst-case volume frame of such a scene need not be equal bit for
  * bit; (b) an image that the caller splits over several t2n_render_forward calls: every call counts as a frame, and the min_frames-th
  * call may fall inside the image. Callers that need bit-stable frames switch the volume off or set min_frames = 1.
@@ -230,6 +230,24 @@ int t2n_field_set_appearance_volume(t2n_field* f, int on, int min_frames);
 int t2n_field_set_appearance_volume_cap(t2n_field* f, uint64_t bytes);
 int t2n_field_release_appearance_volume(t2n_field* f);
 int t2n_field_appearance_volume_counts(const t2n_field* f, uint64_t out[4]);
+/* Feature rows in the tile marcher's tail. A tile-marcher launch that reads the cached density table, holds the current feature volume
+ * and whose workspace carve holds ONE FEATURE ROW PER LIST SLOT writes the rows in the marcher itself — every wave produces the rows of the
+ * list slots it fills or voids, k_compact_list those of the rays handed to it — and runs no feature kernel; the head reads the rows by
+ * slot. The rows are the bits the feature kernel computes from the same entries, so a fused frame equals the unfused frame of the same
+ * field and volume bit for bit. A row per slot: budgeted lists always (the feature rows of a budgeted carve are sized that way: at the
+ * ~14 entries per ray a C2 frame settles on 1.15 GB of rows instead of the 0.6 GB of half a row per slot), worst-case lists only where
+ * 8 x list_cap <= 32 rows per ray + 1024 (small launches); a C2 frame's worst-case lists (42 GB of rows) stay unfused, as do launches
+ * that materialise weights, uncached frames, frames without a current volume and fields with an alpha mask (the masked marcher spills
+ * in its step loop once the tail is added). Default of a new handle: on.
+ * t2n_field_feature_fusion_counts: out[0] / out[1] = tile-marcher launches (sub-launches of a split call count one each) with the rows
+ * in the marcher's tail / with the feature stage (host-side counters: no device wait).
+ * t2n_render_list_shape: the carve of one launch of n_rays x n_samples with `entries_per_ray` budgeted lists (0 = worst case): out[0] =
+ * list_cap (slots per sub-list), out[1] = feature rows, out[2] = 1 when the rows hold a row per slot (the launch can be fused), out[3] /
+ * out[4] / out[5] = byte offsets of the entry list, the feature rows and the counter block in the workspace (tests read a launch's
+ * lists and rows there). */
+int t2n_field_set_feature_fusion(t2n_field* f, int on);
+int t2n_field_feature_fusion_counts(const t2n_field* f, uint64_t out[2]);
+int t2n_render_list_shape(int64_t n_rays, int n_samples, int entries_per_ray, uint64_t out[6]);
 /* DIAGNOSTIC, for tests of the feature stage: the stage alone on caller-made appearance lists. app_pos: device [8][list_cap] entries
  * (x, y, z normalised to [-1, 1], compositing weight); counters: device block of 8 x 64 words, word 64 l = entries of sub-list l (word 32
  * is the stage's f16-range flag: zero it); feat: device [feat_rows][32] rows, row 32 t + s = entry s of tile t, tiles numbered through
@@ -299,7 +317,8 @@ int t2n_raw2alpha(const float* sigma, const float* dist, int64_t n_rays, int n_s
  *             one; depth and every other ray are unaffected); the sub-list counters travel to pinned host memory behind an event
  *             and a LATER call (or t2n_render_workspace_bytes_hint / t2n_field_list_retries) turns them into the next budget.
  *             t2n_render_workspace_bytes_hint returns a workspace size for that mode: lists for 32 entries per ray while nothing is
- *             known, then twice what the field's last completed budgeted launch needed + 16 (~4.3 GB for the frame above).
+ *             known, then one and a half times what the field's last completed budgeted launch needed + 12 (5.0 GB for the frame above:
+ *             a budgeted carve holds a feature row per list slot, 164 B per entry, see t2n_field_set_feature_fusion).
  */
 size_t t2n_render_workspace_bytes(int64_t rays_per_launch, int n_samples);
 /* The general view-dependent heads (T2N_SHADE_MLP_FEA / _MLP_PE / _MLP; models/tensorBase.py:62-86,111-159) evaluate their unfused MLP

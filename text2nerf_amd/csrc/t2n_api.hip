@@ -382,8 +382,11 @@ Carve carve_workspace(int64_t rays, int n_samples, bool ctx, bool feat, unsigned
     c.scratch = o; if (ctx) o = align_up(o + (size_t)rays * (size_t)(n_samples / 4 > 0 ? n_samples / 4 : 1) * 16 + 256 + (size_t)rays * 4, 256);
     // appearance feature rows between the gather + basis kernel and the sample-stationary head: 32 rows per ray (the bench
     // scene needs ~7, BASELINE configs[0] ~44), never more than the worst case; appearance tiles past the capacity take the
-    // one-kernel path
-    const size_t worst_rows = cap + (size_t)kLists * 32, want_rows = (size_t)rays * (budget && budget < 64 ? (budget + 1) / 2 : 32) + 1024;
+    // one-kernel path. Budgeted lists (budget < 64: a C2 frame settles on ~14 entries per ray, 1.15 GB of rows) get ONE ROW PER LIST SLOT:
+    // a frame of the tile marcher then writes its rows in the marcher's tail, addressed by slot (fuse_rows). Worst-case lists never do
+    // (a C2 frame's would take 42 GB): 32 rows per ray, which covers every slot only where the launch is small.
+    const bool budgeted = budget && budget < 64 && budget < (unsigned)n_samples;
+    const size_t worst_rows = cap + (size_t)kLists * 32, want_rows = budgeted ? cap : (size_t)rays * 32 + 1024;
     c.feat_rows = (unsigned)(((worst_rows < want_rows ? worst_rows : want_rows) + 127) / 128 * 128);
     if (!feat) c.feat_rows = 0;
     c.feat = o; o = align_up(o + (size_t)c.feat_rows * 32 * sizeof(float), 256);
@@ -776,6 +779,9 @@ extern "C" int t2n_render_forward(t2n_field* f, const float* rays, int64_t n_ray
         L.app_pos = (float4*)(ws + c.app_pos); L.app_rgb = (float4*)(ws + c.app_rgb); L.app_ray = (int*)(ws + c.app_ray);
         L.list_cap = c.list_cap;
         L.feat = (float*)(ws + c.feat); L.feat_rows = c.feat_rows;
+        // fused launch: cached table, current feature volume (which implies the fused MLP_Fea_noview head on split products), no weights
+        // rows, a feature row per list slot; anything else keeps the feature stage
+        L.slot_rows = tiles && f->fusion_on && f->dev.dsum && f->dev.avol && !f->dev.alpha && !weights && !keep && !generic_head && fuse_rows(c.list_cap, c.feat_rows);
         L.sigma_ctx = keep ? (float*)(ws + c.sigma) : nullptr;
         L.rgb_raw = keep ? (float4*)(ws + c.rgb_raw) : nullptr;
         int rc;
@@ -842,7 +848,7 @@ extern "C" int t2n_render_forward(t2n_field* f, const float* rays, int64_t n_ray
                 ShadeCtx ctx{(float*)(ws + kr.x144), (float*)(ws + kr.feat32), (float*)(ws + kr.h0), (float*)(ws + kr.h1)};
                 if ((rc = launch_shade_list(f, L.app_pos, L.app_ray, L.rays, ray_stride, L.counters, L.list_cap, L.app_rgb, &ctx, s, false, kr.rows))) return rc;
             } else if ((rc = launch_shade_list(f, L.app_pos, L.app_ray, L.rays, ray_stride, L.counters, L.list_cap, L.app_rgb, nullptr, s, false,
-                                               0xffffffffu, keep ? nullptr : L.feat, L.feat_rows, stats))) return rc;
+                                               0xffffffffu, keep ? nullptr : L.feat, L.feat_rows, stats, 0, 0xffffffffu, L.slot_rows))) return rc;
         }
         if ((rc = tiles ? launch_composite(f, L, s, f->frame_w, (int)(cnt / f->frame_w)) : launch_composite(f, L, s))) return rc;
         // the rays that found no room in the lists (budgeted lists; with worst-case lists a ray cannot be left over, but the
@@ -853,8 +859,10 @@ extern "C" int t2n_render_forward(t2n_field* f, const float* rays, int64_t n_ray
     return T2N_OK;
 }
 
-// Workspace for one budgeted launch of a frame, from what the field's last such launch needed: twice the entries per ray it
-// used + 16, at least kBudgetMin; 32 entries per ray when nothing is known yet. Never more than the worst case.
+// Workspace for one budgeted launch of a frame, from what the field's last such launch needed: one and a half times the entries per
+// ray it used + 12, at least kBudgetMin; 32 entries per ray when nothing is known yet. Never more than the worst case. (Twice + 16 while
+// a budgeted carve held half a feature row per slot; with a row per slot — 164 B per entry instead of 100 — that slack would cost a C2
+// frame 5.8 GB. A C2 frame uses ~7 entries per ray and settles on 22: 5.0 GB.)
 extern "C" size_t t2n_render_workspace_bytes_hint(const t2n_field* f, int64_t n_rays, int n_samples) {
     if (!f || n_rays <= 0 || n_samples <= 0) return 0;
     counts_poll(const_cast<t2n_field*>(f), false);
@@ -862,7 +870,7 @@ extern "C" size_t t2n_render_workspace_bytes_hint(const t2n_field* f, int64_t n_
     if (n_rays < kBudgetMinRays) return worst;
     // nothing known yet: 32 entries per ray (the driver's scenes need ~7; a scene that needs more has its surplus rays finished on the
     // device by k_finish_rays for the frame or two until the counters of the first launches have landed)
-    unsigned b = f->list_hint ? 2u * f->list_hint + 16u : 32u;
+    unsigned b = f->list_hint ? f->list_hint + f->list_hint / 2u + 12u : 32u;
     if (b < kBudgetMin) b = kBudgetMin;
     if (b >= (unsigned)n_samples) return worst;
     const size_t want = carve_workspace(n_rays, n_samples, true, true, b).total;
@@ -980,6 +988,24 @@ extern "C" int t2n_field_release_appearance_volume(t2n_field* f) {
 extern "C" int t2n_field_appearance_volume_counts(const t2n_field* f, uint64_t out[4]) {
     if (!f || !out) { set_error("t2n_field_appearance_volume_counts: NULL argument"); return T2N_ERR_INVALID; }
     out[0] = (uint64_t)f->avol_bytes; out[1] = f->avol_counts[2]; out[2] = f->avol_counts[0]; out[3] = f->avol_counts[1];
+    return T2N_OK;
+}
+// ---- feature rows in the tile marcher's tail (t2n_march_tiles.hip) ------------------------------------------------------------------
+extern "C" int t2n_field_set_feature_fusion(t2n_field* f, int on) {
+    if (!f) { set_error("t2n_field_set_feature_fusion: NULL field"); return T2N_ERR_INVALID; }
+    f->fusion_on = on ? 1 : 0;
+    return T2N_OK;
+}
+extern "C" int t2n_field_feature_fusion_counts(const t2n_field* f, uint64_t out[2]) {
+    if (!f || !out) { set_error("t2n_field_feature_fusion_counts: NULL argument"); return T2N_ERR_INVALID; }
+    out[0] = f->fusion_counts[0]; out[1] = f->fusion_counts[1];
+    return T2N_OK;
+}
+extern "C" int t2n_render_list_shape(int64_t n_rays, int n_samples, int entries_per_ray, uint64_t out[6]) {
+    if (n_rays <= 0 || n_samples <= 0 || entries_per_ray < 0 || !out) { set_error("t2n_render_list_shape: bad argument"); return T2N_ERR_INVALID; }
+    const Carve c = carve_workspace(n_rays, n_samples, true, true, (unsigned)entries_per_ray);
+    out[0] = c.list_cap; out[1] = c.feat_rows; out[2] = fuse_rows(c.list_cap, c.feat_rows) ? 1 : 0;
+    out[3] = c.app_pos; out[4] = c.feat; out[5] = c.counters;
     return T2N_OK;
 }
 extern "C" int t2n_field_feature_rows(t2n_field* f, const float* app_pos, const uint32_t* counters, uint32_t list_cap, int volume, float* feat,

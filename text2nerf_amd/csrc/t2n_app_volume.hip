@@ -15,6 +15,7 @@
 // texel reads it with weight 0, so the eight corners of a cell are always (x, x + 1) x (y, y + 1) x (z, z + 1) without a clamp.
 #include "t2n_internal.h"
 #include "t2n_device.h"
+#include "t2n_app_rows.h"
 
 namespace t2n {
 
@@ -87,7 +88,8 @@ __global__ __launch_bounds__(256) void k_app_features_vol(const AvReadArgs a) {
     // per CU all run the C2 frame's rows in 0.27 ms: the texture addresser is busy for 0.78 - 0.87 of the kernel's cycles with the
     // 34 wave-wide 16-B loads per tile, whatever the lane mapping; the vector L1 serves four fifths of their line accesses and the
     // volume's touched part stays in L2 / Infinity Cache (counters: profiles/appearance_volume_ab.txt, section 9)
-    constexpr int LPE = 4, NQ = 8 / LPE, EPP = 64 / LPE, PASSES = 32 / EPP;   // quads per lane, entries per pass, passes per tile
+    // (the per-entry body is av_feature_row, t2n_app_rows.h: the tile marcher's tail runs it with eight lanes per entry)
+    constexpr int LPE = 4, EPP = 64 / LPE, PASSES = 32 / EPP;   // entries per pass, passes per tile
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     unsigned cnt_l = 0;
     if (lane < a.nlists) {
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256) void k_app_features_vol(const AvReadArgs a) {
     if (ntiles > a.tile_hi) ntiles = a.tile_hi;
     const unsigned wave_stride = gridDim.x * 4u;
     const int e = lane / LPE, q = lane % LPE;
-    const char* __restrict__ V = reinterpret_cast<const char*>(a.avol);
+    const AvVolume vol{a.avol, a.row, a.slice, a.ny1};
     for (unsigned tile = blockIdx.x * 4u + wid; tile < ntiles; tile += wave_stride) {
         // tile -> (first entry, live entries): k_app_features_p's locate
         const int li = (int)__popcll(__ballot((lane < a.nlists) & (incl <= tile)));
@@ -124,42 +126,7 @@ __global__ __launch_bounds__(256) void k_app_features_vol(const AvReadArgs a) {
         for (int p = 0; p < PASSES; ++p) {
             const bool live = (unsigned)(EPP * p + e) < nlive;
             const float4 mine = pos[p];
-            const Axes3 A = sample_axes_inbox(a.app, mine.x, mine.y, mine.z);
-            // (list slots a failed reservation left unwritten decode to anything: the cell stays inside the grid, as in the direct form)
-            const unsigned ix = (unsigned)min(max(A.a[0].i0, 0), a.app.W[0] - 1), iy = (unsigned)min(max(A.a[1].i0, 0), a.app.H[0] - 1);
-            const unsigned iz = (unsigned)min(max(A.a[2].i0, 0), a.app.H[1] - 1);
-            // (24-bit multiplies, as in the cached density read: appearance_volume_prepare refuses grids that leave their range)
-            const unsigned cell = umad24(umad24(iz, a.ny1, iy), a.row, ix * kAvCornerBytes);
-            const unsigned o00 = (live ? cell : 0u) + (unsigned)q * 16u;
-            const unsigned o01 = o00 + a.row, o10 = o00 + a.slice, o11 = o10 + a.row;
-            const unsigned off[4] = {o00, o01, o10, o11};   // (z, y), (z, y + 1), (z + 1, y), (z + 1, y + 1)
-            float4 c[4][2][NQ];   // [(z, y)][x, x + 1][quad]
-#pragma unroll
-            for (int zy = 0; zy < 4; ++zy)
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i)   // (scalar base + 32-bit offset + immediate)
-                        c[zy][x][i] = *reinterpret_cast<const float4*>(V + (size_t)off[zy] + ((int)kAvCornerBytes * x + 16 * LPE * i));
-            __builtin_amdgcn_sched_barrier(0);   // all of the entry's loads are on their way before the first one is used
-            const float wx0 = live ? A.a[0].w0 : 0.f, wx1 = live ? A.a[0].w1 : 0.f;
-            const float wyx[2][2] = {{A.a[1].w0 * wx0, A.a[1].w0 * wx1}, {A.a[1].w1 * wx0, A.a[1].w1 * wx1}};
-            const float wz[2] = {A.a[2].w0, A.a[2].w1};
-            float4 r[NQ];
-#pragma unroll
-            for (int zy = 0; zy < 4; ++zy)
-#pragma unroll
-                for (int x = 0; x < 2; ++x) {
-                    const float w = wyx[zy & 1][x] * wz[zy >> 1];
-#pragma unroll
-                    for (int i = 0; i < NQ; ++i) r[i] = (zy == 0 && x == 0) ? f4_mul(c[0][0][i], w) : f4_fma(c[zy][x][i], w, r[i]);
-                }
-            // quad 6 carries the entry's compositing weight in column 27, quad 7 is zeros
-            if (q == 6 % LPE) r[6 / LPE].w = live ? mine.w : 0.f;
-            if (q == 7 % LPE) r[7 / LPE] = make_float4(0.f, 0.f, 0.f, 0.f);
-            float* __restrict__ row = rb + (unsigned)((EPP * p + e) * 32 + 4 * q);
-#pragma unroll
-            for (int i = 0; i < NQ; ++i) *reinterpret_cast<float4*>(row + 4 * LPE * i) = r[i];
+            av_feature_row<LPE>(a.app, vol, mine, live, q, rb + (unsigned)((EPP * p + e) * 32 + 4 * q), true);
         }
     }
 }

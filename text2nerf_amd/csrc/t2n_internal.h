@@ -170,6 +170,10 @@ struct t2n_field {
     bool avol_alloc_failed = false;
     void* avol_ev = nullptr; void* avol_stream = nullptr;
     unsigned long long avol_counts[3] = {0, 0, 0};     // tile-marcher frames that read the volume / ran the direct form, builds
+    // feature rows in the tile marcher's tail (t2n_field_set_feature_fusion, t2n_march_tiles.hip): a launch that reads the cached table,
+    // holds the current feature volume and a row per list slot writes its rows there and runs no feature kernel
+    int fusion_on = 1;
+    unsigned long long fusion_counts[2] = {0, 0};      // tile-marcher launches with the rows in the marcher's tail / with the feature stage
 };
 
 namespace t2n {
@@ -198,6 +202,7 @@ struct RenderLaunch {
     // workspace carve (one sub-launch)
     float* acc; int4* ray_app; unsigned* counters; float4* app_pos; int* app_ray; float4* app_rgb; unsigned list_cap;
     float* feat = nullptr; unsigned feat_rows = 0;   // appearance feature rows [feat_rows][32] between the gather + basis kernel and the head
+    bool slot_rows = false;   // fused launch: the tile marcher writes the row of list slot s at feat + 32 s, the head reads it there (fuse_rows)
     float* sigma_ctx; float4* rgb_raw;   // KEEP_CTX only, else NULL
 };
 int launch_march(t2n_field* f, const RenderLaunch& L, hipStream_t s);
@@ -238,6 +243,10 @@ int launch_feature_rows(t2n_field* f, const float4* app_pos, const unsigned* cou
                         hipStream_t s);   // (t2n_shade.hip) the feature stage alone on caller-made lists, in the form f->dev.avol selects
 int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h, float* spill, float4* scratch, hipStream_t s);
 constexpr int kLists = 8;   // appearance sub-lists per sub-launch
+// A tile-marcher launch is FUSED (rows in the marcher's tail, head in slot mode) when the feature rows hold one row per list slot: true of
+// budgeted lists (carve_workspace sizes their rows that way) and of small worst-case launches, never of large worst-case lists (a C2
+// frame's would take 42 GB of rows), which keep the feature stage and its dense rows.
+inline bool fuse_rows(unsigned list_cap, unsigned feat_rows) { return feat_rows && (unsigned long long)list_cap * kLists <= feat_rows; }
 constexpr int kCounterStride = 64;   // unsigned words between sub-list counters: one 256-B line each (same-line atomics serialise)
 // list_cap(n_rays, N): worst-case entries of one sub-list = rays of the largest XCD run x samples
 inline unsigned list_capacity(long long n_rays, int n_samples) {
@@ -260,7 +269,7 @@ struct ShadeCtx { float* x144; float* feat32; float* h0; float* h1; };
 int launch_shade_list(t2n_field* f, const float4* app_pos, const int* app_ray, const float* rays, int ray_stride,
                       const unsigned* counters_dev, unsigned list_cap, float4* app_rgb, const ShadeCtx* ctx, hipStream_t s,
                       bool features_only = false, unsigned ctx_rows = 0xffffffffu, float* feat = nullptr, unsigned feat_rows = 0,
-                      uint64_t* stats = nullptr, unsigned tile_lo = 0, unsigned tile_hi = 0xffffffffu);   // tile_lo / tile_hi: the one-kernel paths cover these tiles only
+                      uint64_t* stats = nullptr, unsigned tile_lo = 0, unsigned tile_hi = 0xffffffffu, bool slot_rows = false);   // tile_lo / tile_hi: the one-kernel paths cover these tiles only
 // feat / feat_rows: scratch rows for the two-kernel default path (features -> sample-stationary head, t2n_mlp_ss.hip); tiles
 // past the capacity take the one-kernel path. Word kRangeFlagWord of the counter block is the head's f16-range flag.
 constexpr int kRangeFlagWord = 32;
@@ -273,7 +282,7 @@ constexpr int kHeadPlanWord = 40;      // general view-dependent heads: the forw
 constexpr int kFailEntriesWord = 36;   // appearance entries of the rays that fit no sub-list (finished by k_finish_rays): the next budget counts them
 constexpr unsigned kKeptMagic = 0x4b455054u;   // "KEPT"
 int launch_mlp_ss(t2n_field* f, const float* feat, const unsigned* counters_dev, unsigned list_cap, unsigned tile_hi, float4* app_rgb,
-                  unsigned* range_flag, hipStream_t s);
+                  unsigned* range_flag, hipStream_t s, bool slot_rows = false);   // slot_rows: the row of list slot s is feat + 32 s
 // features_only: gather + basis stages only (the general heads take over); ctx_rows: capacity of the ctx buffers in rows
 
 // the general (unfused) view-dependent heads (t2n_heads.hip): MLP_Fea / MLP_PE / MLP input layout and launchers

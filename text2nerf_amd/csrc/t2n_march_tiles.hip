@@ -26,6 +26,7 @@
 // without the per-step-pair loads, MFMAs, LDS table and fences (C2 frame: 0.51 -> 0.38 ms; profiles/march_density_cache_ab.txt).
 // Replaces the same reference lines as k_march (see t2n_march.hip).
 #include "t2n_device.h"
+#include "t2n_app_rows.h"
 
 namespace t2n {
 
@@ -59,6 +60,9 @@ struct TileArgs {
     // the marcher writes the weights of the 16-step blocks its wave's window touches, through a per-wave LDS transpose: 16 steps x
     // 64 rays, then 64-B row segments per store
     float* dense_w;
+    // ROWS: the feature rows of a fused frame, one [32]-float row per LIST SLOT (row of slot s at feat + 32 s); the volume they are
+    // fetched from is F.avol / F.av_row / F.av_slice
+    float* feat;
 #ifdef MT_PROF
     unsigned long long* prof;   // [waves][8] per-region cycle sums (instrumented build, tools/r5_march_accounting.sh)
 #endif
@@ -250,6 +254,16 @@ __device__ __forceinline__ void void_entries(float4* __restrict__ app_pos, int* 
     }
 }
 
+// The feature rows of `count` slots from `slot` on, whose entries this wave has just written or voided (ROWS frames: whoever writes or
+// voids app_pos[slot] also writes feat[slot], with what k_app_features_vol computes from that entry). slot / count wave-uniform.
+__device__ __forceinline__ void slot_rows(const FieldDev& F, const float4* __restrict__ app_pos, float* __restrict__ feat, size_t slot,
+                                          unsigned count, int lane) {
+    if (!count) return;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the entries have reached L2: av_slot_rows reads them back there
+    const AvVolume vol{F.avol, F.av_row, F.av_slice, (unsigned)F.app.H[0] + 1u};
+    av_slot_rows(F.app, vol, app_pos + slot, feat + slot * 32u, count, lane);
+}
+
 constexpr int kDenseLd = 20;                          // floats per ray row of the transpose tile (16 steps + pad, 16-B aligned)
 constexpr int kDenseFloats = 64 * kDenseLd;           // per wave: the weights tile
 struct __attribute__((aligned(4))) F4U { float x, y, z, w; };   // row segments of an [n_rays, N] tensor are only 4-B aligned for odd N
@@ -290,7 +304,11 @@ struct __attribute__((aligned(4))) F4U { float x, y, z, w; };   // row segments 
 // gathers is decided exactly as without the cache (the two forms round differently, and the frame is the same bit for bit either way),
 // so the tap bit set stays; the operand loads, the MFMAs, the LDS table, its sum pass and the three fences go.
 constexpr int mt_waves(bool dense, bool cached) { return cached ? (dense ? T2N_MTCD_WAVES : T2N_MTC_WAVES) : (dense ? T2N_MTD_WAVES : T2N_MT_WAVES); }
-template <bool DENSE, bool ALPHA = false, bool RELU = false, bool CACHED = false>
+// ROWS (CACHED && !DENSE frames that hold the current feature volume and a row per list slot, launch_march_tiles): the wave's tail
+// also produces the feature rows of the slots it filled or voided — eight corner fetches and 64 multiply-adds per entry, work bound by
+// the texture addresser that runs beside the other waves' marching (bound by VALU issue) instead of in a kernel of its own behind
+// this one. Everything the step loop kept in registers is dead by then: the step loop's allocation is what it was.
+template <bool DENSE, bool ALPHA = false, bool RELU = false, bool CACHED = false, bool ROWS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DENSE, CACHED), mt_waves(DENSE, CACHED)))) void k_march_tiles(const TileArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -558,6 +576,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
             }
         }
     }
+    if constexpr (ROWS) {
+        static_assert(CACHED && !DENSE, "rows in the tail: cached, weight-free frames only");
+#ifndef T2N_MT_NO_TAIL_ROWS   // (timing-only build without the tails' rows: the frame's colours are invalid)
+        // the wave's region of the list: its rays' entries (fits), or what void_entries defined below list_cap
+        const unsigned ubase = (unsigned)__builtin_amdgcn_readfirstlane((int)base), utotal = (unsigned)__builtin_amdgcn_readfirstlane((int)total);
+        unsigned cnt = utotal;
+        if (ubase + utotal > a.list_cap) cnt = ubase < a.list_cap ? a.list_cap - ubase : 0u;
+        slot_rows(F, a.app_pos, a.feat, (size_t)list * a.list_cap + ubase, cnt, lane);
+#endif
+    }
 }
 
 // The rays the tile marcher handed over: one wave per ray finishes their appearance slices.
@@ -569,6 +597,7 @@ struct CompactArgs {
     unsigned long long* stats;
     const float4* scratch; int cap;   // the marcher's per-ray staging slices
     int finisher;                     // a ray that fits no sub-list is left to k_finish_rays (t2n_shade.hip) instead of losing its samples
+    float* feat;                      // fused frames (TileArgs::feat): the rows of the slots this kernel fills or voids; else NULL
 };
 // lane 0 reserves `napp` slots on the first sub-list with room; returns (slot0, napp or 0 when nothing fits) to all lanes
 // A ray that fits nowhere (budgeted lists, t2n_render_forward): with a finisher behind this kernel the ray keeps its hand-over record
@@ -578,19 +607,21 @@ struct CompactArgs {
 __device__ __forceinline__ void reserve_slots(const CompactArgs& a, long long r, unsigned list, int lane, const int4 ra, unsigned& slot0,
                                               unsigned& napp, int* ovf_slot) {
     slot0 = 0;
-    if (lane == 0) {
-        bool fits = napp == 0;
-        for (unsigned att = 0; att < (unsigned)kLists && !fits; ++att) {     // first sub-list with room (a failed try leaves the
-            const unsigned l = (list + att) & (unsigned)(kLists - 1);          // counter above list_cap: readers clamp it)
-            if (a.counters[l * kCounterStride] + napp > a.list_cap) continue;
-            const unsigned s0 = atomicAdd(&a.counters[l * kCounterStride], napp);
-            if (s0 + napp <= a.list_cap) { slot0 = l * a.list_cap + s0; fits = true; }
-            else                                                              // lost a race for the list's tail: its part of the
-                for (unsigned e = s0; e < a.list_cap; ++e) {                  // list gets defined entries (void_entries), by this lane
-                    a.app_pos[(size_t)l * a.list_cap + e] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    a.app_ray[(size_t)l * a.list_cap + e] = 0;
-                }
+    napp = (unsigned)__builtin_amdgcn_readfirstlane((int)napp);   // (every lane holds the ray's record)
+    bool fits = napp == 0;
+    for (unsigned att = 0; att < (unsigned)kLists && !fits; ++att) {     // first sub-list with room (a failed try leaves the
+        const unsigned l = (list + att) & (unsigned)(kLists - 1);          // counter above list_cap: readers clamp it)
+        unsigned s0 = 0xffffffffu;                                         // (no try: the list is full already)
+        if (lane == 0 && a.counters[l * kCounterStride] + napp <= a.list_cap) s0 = atomicAdd(&a.counters[l * kCounterStride], napp);
+        s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)s0);
+        if (s0 == 0xffffffffu) continue;
+        if (s0 + napp <= a.list_cap) { slot0 = l * a.list_cap + s0; fits = true; }
+        else if (s0 < a.list_cap) {                                        // lost a race for the list's tail: its part of the
+            void_entries(a.app_pos, a.app_ray, l, a.list_cap, s0, a.list_cap, lane);   // list gets defined entries (and rows)
+            if (a.feat) slot_rows(a.F, a.app_pos, a.feat, (size_t)l * a.list_cap + s0, a.list_cap - s0, lane);
         }
+    }
+    if (lane == 0) {
         if (fits || !a.finisher) a.ray_app[r] = make_int4((int)slot0, fits ? (int)napp : 0, ra.z, ra.w);
         else {
             a.ray_app[r] = make_int4(-ra.x - 1, (int)napp, ra.z, ra.w);
@@ -599,10 +630,8 @@ __device__ __forceinline__ void reserve_slots(const CompactArgs& a, long long r,
         }
         if (!fits && !a.finisher && a.stats) a.stats[T2N_STAT_OVERFLOW] = 1ull;
         if (!fits) a.counters[kOverflowWord] = 1u;   // budgeted lists: read back by the host (the next frames' budget, list_retries)
-        if (!fits) napp = 0;
     }
-    slot0 = __shfl(slot0, 0);
-    napp = __shfl(napp, 0);
+    if (!fits) napp = 0;
 }
 // append the entries of wbuf[r][from, end) above the threshold at slot0 + run.. (sample order)
 __device__ __forceinline__ void compact_span(const CompactArgs& a, long long r, const Ray& ray, int from, int end, unsigned slot0, unsigned run,
@@ -642,6 +671,7 @@ __device__ __forceinline__ void compact_ray_staged(const CompactArgs& a, long lo
         const Ray ray = load_ray(a.F, a.rays + r * a.ray_stride, a.ray_stride);
         compact_span(a, r, ray, from, first + Lw, slot0, staged, lane);
     }
+    if (a.feat) slot_rows(a.F, a.app_pos, a.feat, (size_t)slot0, napp, lane);
 }
 // the rays the tile marcher could not stage (more than cap appearance samples): a small persistent grid walks the list
 __global__ __launch_bounds__(256) void k_compact_list(const CompactArgs a, const unsigned* ovf_count, int* ovf_list) {
@@ -782,6 +812,12 @@ int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h
     a.scratch = scratch; a.cap = cap; a.ovf_count = ovf_count; a.ovf_list = ovf_list;
     a.app_pos = L.app_pos; a.app_ray = L.app_ray; a.counters = L.counters; a.list_cap = L.list_cap; a.stats = (unsigned long long*)L.stats;
     a.dense_w = L.weights;
+    // fused frame (t2n_render_forward decided: cached table, current feature volume, a row per list slot): rows in the marcher's tail
+    // (not with an alpha mask: the masked instantiations already spill at five waves, and the tail adds to it)
+    const bool rows = L.slot_rows && f->dev.dsum != nullptr && f->dev.avol != nullptr && !dense && !f->dev.alpha;
+    if (L.slot_rows && !rows) { set_error("launch_march_tiles: a fused frame needs the cached table, the feature volume, no mask and no weights rows"); return T2N_ERR_STATE; }
+    a.feat = rows ? L.feat : nullptr;
+    ++f->fusion_counts[rows ? 0 : 1];
     a.F.term_eps = (!L.weights && !L.z_vals && !L.sigma_ctx) ? f->term_eps : 0.f;   // (eval only: this marcher has no train form)
 #ifdef MT_PROF
     static unsigned long long* prof = nullptr;
@@ -802,7 +838,8 @@ int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h
     const size_t lds = (size_t)4 * ((cached ? 0 : kStageFloats) + (dense ? kDenseFloats : 0)) * sizeof(float);
     const bool mask = f->dev.alpha != nullptr, relu = f->dev.act == T2N_ACT_RELU;
     ++f->dcache_counts[cached ? 0 : 1];
-#define T2N_MT_LAUNCH(D, A, R) do { if (cached) hipLaunchKernelGGL((k_march_tiles<D, A, R, true>), grid, dim3(256), lds, s, a); \
+#define T2N_MT_LAUNCH(D, A, R) do { if (rows) hipLaunchKernelGGL((k_march_tiles<D, A, R, true, !D && !A>), grid, dim3(256), lds, s, a); \
+                                    else if (cached) hipLaunchKernelGGL((k_march_tiles<D, A, R, true>), grid, dim3(256), lds, s, a); \
                                     else hipLaunchKernelGGL((k_march_tiles<D, A, R, false>), grid, dim3(256), lds, s, a); } while (0)
     if (dense) { if (mask) { if (relu) T2N_MT_LAUNCH(true, true, true); else T2N_MT_LAUNCH(true, true, false); }
                  else { if (relu) T2N_MT_LAUNCH(true, false, true); else T2N_MT_LAUNCH(true, false, false); } }
@@ -832,6 +869,7 @@ int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h
     c.stats = (unsigned long long*)L.stats;
     c.scratch = scratch; c.cap = cap;
     c.finisher = finish_supported(f) ? 1 : 0;
+    c.feat = a.feat;
     hipLaunchKernelGGL(k_compact_list, dim3(64), dim3(256), 0, s, c, (const unsigned*)ovf_count, ovf_list);
     timing_end(f, T2N_K_MARCH, s);
     T2N_HIP(hipGetLastError());

@@ -64,6 +64,7 @@ struct Args {
     const uint4* w0; const uint4* w1; const uint4* w2; const float* bias; const float* inv_scale;   // packed by k_pack_ss
     const float* bounds;          // [0..3] row-norm bounds of the hidden activations, [4] (as unsigned) 1: the untracked kernel may run (k_ss_scales)
     const float* feat;            // [rows][32] fp32 feature rows (row = tile * 32 + sample): 27 features, the entry's compositing weight, zeros
+                                  // (SLOT: row = the entry's list slot, written by the tile marcher's tail; rows of dead slots are never read)
     const unsigned* counters; unsigned list_cap; int nlists;
     unsigned tile_hi;             // 32-sample tiles [0, min(ntiles, tile_hi)) are this kernel's
     float4* app_rgb;
@@ -528,7 +529,9 @@ __device__ __forceinline__ void l2_last(AEl (&A2)[2], const u4v& Hh, const u4v& 
 // |h1| <= max_j sum_k |W1[j][k]| * that + max |b1| (row norms by k_ss_scales at upload; the features' own maximum is tracked per round
 // in both forms) — and the launch raises the range flag when the bound passes the f16 range. Both instantiations are launched; the word
 // bounds[4] (written at upload: bound fine for features up to 64) makes one of them return at once.
-template <bool TRACK>
+// SLOT: the feature rows are addressed by list slot (fused frames, t2n_march_tiles.hip) instead of by dense tile: the wave-uniform tile
+// index is located in its sub-list from the prefix sums and counts held in lanes 0..7.
+template <bool TRACK, bool SLOT = false>
 __global__ __launch_bounds__(256) void k_mlp_ss3(const Args a) {
     extern __shared__ __attribute__((aligned(16))) uint4 lds[];
     if ((__float_as_uint(a.bounds[4]) != 0u) == TRACK) return;
@@ -569,6 +572,10 @@ __global__ __launch_bounds__(256) void k_mlp_ss3(const Args a) {
     const unsigned nrounds = (ntiles + 11u) / 12u;
     if (blockIdx.x >= nrounds) return;
     if (tid < 8) { LT[tid] = tid < a.nlists ? incl : 0xffffffffu; LT[8 + tid] = cnt_l; }
+    // SLOT: the table above stays in lanes 0..7 of two registers (sixteen scalars are more than the kernel's SGPR budget holds: they
+    // spill); a tile is located with one compare and two v_readlane
+    const unsigned incl_m = lane < a.nlists ? incl : 0xffffffffu;
+    const unsigned s_ntiles = SLOT ? (unsigned)__builtin_amdgcn_readfirstlane((int)ntiles) : 0u;
 
     const float inv0 = a.inv_scale[0], inv1 = a.inv_scale[1], inv2 = a.inv_scale[2];
     for (int i = tid; i < kW1; i += 256) W1[i] = a.w1[i];
@@ -585,8 +592,22 @@ __global__ __launch_bounds__(256) void k_mlp_ss3(const Args a) {
     // rows of round r: tile 12 r + 3 w + t, row 32 tile + j (see k_mlp_ss::load_feat)
     const unsigned last = ntiles * 32u - 1u;
     auto load_feat = [&](unsigned r, int t, float (&f)[14]) {
-        unsigned i = ((r * 4u + (unsigned)w) * 3u + (unsigned)t) * 32u + (unsigned)j;
-        i = i < last ? i : last;
+        unsigned i;
+        if constexpr (SLOT) {
+            // tile -> (sub-list, tile offset) as in SS3_FINAL; the row is clamped to the sub-list's last live slot: a dead lane of a partial
+            // tile (and a tile past the last one) re-reads a live row, whose outputs SS3_FINAL discards
+            unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)((r * 4u + (unsigned)w) * 3u + (unsigned)t));
+            tile = tile < s_ntiles ? tile : s_ntiles - 1u;
+            const int li = (int)__popcll(__ballot(incl_m <= tile));   // (tile < the last prefix sum: li <= 7)
+            const unsigned before = li ? (unsigned)__builtin_amdgcn_readlane((int)incl_m, li - 1) : 0u;
+            const unsigned cnt = (unsigned)__builtin_amdgcn_readlane((int)cnt_l, li);
+            const unsigned lbase = (unsigned)li * a.list_cap, lastl = lbase + cnt - 1u;
+            i = lbase + (tile - before) * 32u + (unsigned)j;
+            i = i < lastl ? i : lastl;
+        } else {
+            i = ((r * 4u + (unsigned)w) * 3u + (unsigned)t) * 32u + (unsigned)j;
+            i = i < last ? i : last;
+        }
         const float2* __restrict__ row = reinterpret_cast<const float2*>(a.feat + (size_t)i * 32 + 14 * h);
 #pragma unroll
         for (int e = 0; e < 7; ++e) { const float2 v = row[e]; f[2 * e] = v.x; f[2 * e + 1] = v.y; }
@@ -919,7 +940,7 @@ int ss_pack(t2n_field* f, hipStream_t s) {
 // the head of the appearance stage for tiles [0, tile_hi) of the sub-lists, from feature rows; *range_flag is set when an
 // activation left the f16 range (the caller then re-runs the launch on the exact path)
 int launch_mlp_ss(t2n_field* f, const float* feat, const unsigned* counters_dev, unsigned list_cap, unsigned tile_hi, float4* app_rgb,
-                  unsigned* range_flag, hipStream_t s) {
+                  unsigned* range_flag, hipStream_t s, bool slot_rows) {
     using namespace ss;
     if (f->ss_dirty || !f->buf_ss) { const int rc = ss_pack(f, s); if (rc) return rc; }
     else if (f->ss_event && f->ss_stream != (void*)s) T2N_HIP(hipStreamWaitEvent(s, (hipEvent_t)f->ss_event, 0));
@@ -927,6 +948,8 @@ int launch_mlp_ss(t2n_field* f, const float* feat, const unsigned* counters_dev,
     if (!attr_set) {
         T2N_HIP(hipFuncSetAttribute((const void*)k_mlp_ss3<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
         T2N_HIP(hipFuncSetAttribute((const void*)k_mlp_ss3<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+        T2N_HIP(hipFuncSetAttribute((const void*)(k_mlp_ss3<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
+        T2N_HIP(hipFuncSetAttribute((const void*)(k_mlp_ss3<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds));
         attr_set = true;
     }
     const size_t nw = (size_t)kW0 + kW1 + kW2;
@@ -947,8 +970,13 @@ int launch_mlp_ss(t2n_field* f, const float* feat, const unsigned* counters_dev,
         f->ss_variant = *f->ss_ok_host ? 0 : 1;   // 0: untracked (bounds hold), 1: tracked
     else if (f->ss_variant == -1) (void)hipGetLastError();   // (hipErrorNotReady)
     // (a kernel started for the wrong word returns at once: bounds[4] on the device decides, the host copy only saves the empty launch)
-    if (f->ss_variant != 1) hipLaunchKernelGGL(k_mlp_ss3<false>, dim3(256), dim3(256), kLds, s, a);
-    if (f->ss_variant != 0) hipLaunchKernelGGL(k_mlp_ss3<true>, dim3(256), dim3(256), kLds, s, a);
+    if (slot_rows) {
+        if (f->ss_variant != 1) hipLaunchKernelGGL((k_mlp_ss3<false, true>), dim3(256), dim3(256), kLds, s, a);
+        if (f->ss_variant != 0) hipLaunchKernelGGL((k_mlp_ss3<true, true>), dim3(256), dim3(256), kLds, s, a);
+    } else {
+        if (f->ss_variant != 1) hipLaunchKernelGGL(k_mlp_ss3<false>, dim3(256), dim3(256), kLds, s, a);
+        if (f->ss_variant != 0) hipLaunchKernelGGL(k_mlp_ss3<true>, dim3(256), dim3(256), kLds, s, a);
+    }
 #ifdef SS3_PROF
     if (++prof_calls == 20) {   // one report per process: per-wave cycle sums, averaged over the waves
         static unsigned long long h[1024 * 10];

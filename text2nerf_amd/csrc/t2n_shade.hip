@@ -1984,7 +1984,8 @@ int launch_feature_rows(t2n_field* f, const float4* app_pos, const unsigned* cou
 
 int launch_shade_list(t2n_field* f, const float4* app_pos, const int* app_ray, const float* rays, int ray_stride,
                       const unsigned* counters_dev, unsigned list_cap, float4* app_rgb, const ShadeCtx* ctx, hipStream_t s,
-                      bool features_only, unsigned ctx_rows, float* feat, unsigned feat_rows, uint64_t* stats, unsigned tile_lo, unsigned tile_hi) {
+                      bool features_only, unsigned ctx_rows, float* feat, unsigned feat_rows, uint64_t* stats, unsigned tile_lo, unsigned tile_hi,
+                      bool slot_rows) {
     ShadeArgs a;
     memset(&a, 0, sizeof(a));
     if (ctx) a.ctx = *ctx;
@@ -2005,17 +2006,23 @@ int launch_shade_list(t2n_field* f, const float4* app_pos, const int* app_ray, c
     }
     const dim3 grid(shade_grid((unsigned long long)list_cap * kLists));
     const bool half = f->factor_bf16 && f->dev.app.plane_h[0];
-    const unsigned ws_tiles = feat ? feat_rows / 128u * 4u : 0u;
+    // (fused launch: the rows are addressed by list slot and cover every slot, so every tile the lists can hold is the head's)
+    const unsigned ws_tiles = slot_rows ? (unsigned)kLists * ((list_cap + 31u) / 32u) : (feat ? feat_rows / 128u * 4u : 0u);
+    if (slot_rows && !(use_ws(f) && !ctx && !features_only && feat && fuse_rows(list_cap, feat_rows))) {
+        set_error("launch_shade_list: slot-addressed rows need the fused MLP_Fea_noview head and a row per list slot");
+        return T2N_ERR_STATE;
+    }
     if (use_ws(f) && !ctx && !features_only && ws_tiles >= 4u) {
         // default render path: K2a gather + basis -> feature rows (k_app_features_p), K2b sample-stationary head (t2n_mlp_ss.hip);
         // tiles past the row capacity take the one-kernel path; a launch that met a value outside the f16 range is redone on the
         // exact fp32 path
         unsigned* flag = const_cast<unsigned*>(counters_dev) + kRangeFlagWord;
+        // (fused launch: the tile marcher's tail has written the rows; the bracket stays, around what is left of the stage)
         timing_begin(f, T2N_K_APPFEAT, s);
-        { const int rc = feature_stage(f, a, ws_tiles, feat, flag, half, s); if (rc) return rc; }
+        if (!slot_rows) { const int rc = feature_stage(f, a, ws_tiles, feat, flag, half, s); if (rc) return rc; }
         timing_end(f, T2N_K_APPFEAT, s);
         timing_begin(f, T2N_K_SHADE, s);
-        const int rc = launch_mlp_ss(f, feat, counters_dev, list_cap, ws_tiles, app_rgb, flag, s);
+        const int rc = launch_mlp_ss(f, feat, counters_dev, list_cap, ws_tiles, app_rgb, flag, s, slot_rows);
         if (rc) return rc;
         ShadeArgs oa = a;
         oa.tile_lo = ws_tiles; oa.range_flag = flag; oa.split_unsafe = f->split_unsafe;

@@ -436,6 +436,10 @@ class TensorBase(nn.Module):
         self.appearance_volume = True
         self.appearance_volume_min_frames = 0
         self.appearance_volume_cap_bytes = 0
+        # Frames that read the cached density table AND the feature volume, and whose workspace holds a feature row per list slot
+        # (budgeted lists, small launches), write their feature rows in the tile marcher's tail and run no feature kernel (same frames
+        # bit for bit; False = the feature stage stays a kernel of its own). See feature_fusion_counts().
+        self.feature_fusion = True
         # Early ray termination of eval renders that return neither weights nor z_vals (evaluation(), render_views, ...): OPT-IN. The
         # reference never terminates (models/tensorBase.py:19-26,494-505: every in-box sample is evaluated), so the default 0.0 is its
         # sample-for-sample arithmetic (exact evaluated-sample counts). A threshold eps > 0 stops a ray whose transmittance fell below it:
@@ -900,6 +904,7 @@ class TensorBase(nn.Module):
             self._staging_set = None
             self._dcache_set = (True, 0)
             self._avol_set = (True, 0, 0)
+            self._fusion_set = True
             self._stage_shape_set = (0, 0)
             self._head_rows_set = 32
             self._alpha_key = "unset"
@@ -949,6 +954,10 @@ class TensorBase(nn.Module):
             _lib.check(lib.t2n_field_set_appearance_volume(self._handle, 1 if av[0] else 0, av[1]), "t2n_field_set_appearance_volume")
             _lib.check(lib.t2n_field_set_appearance_volume_cap(self._handle, av[2]), "t2n_field_set_appearance_volume_cap")
             self._avol_set = av
+        fu = bool(getattr(self, "feature_fusion", True))
+        if getattr(self, "_fusion_set", True) != fu:
+            _lib.check(lib.t2n_field_set_feature_fusion(self._handle, 1 if fu else 0), "t2n_field_set_feature_fusion")
+            self._fusion_set = fu
         shape = tuple(int(v) for v in self.feature_stage_shape)
         if getattr(self, "_stage_shape_set", (0, 0)) != shape:
             _lib.check(lib.t2n_field_set_feature_stage_shape(self._handle, shape[0], shape[1]), "t2n_field_set_feature_stage_shape")
@@ -1876,6 +1885,14 @@ class TensorBase(nn.Module):
         if self._handle is not None:
             _lib.check(_lib.load().t2n_field_appearance_volume_counts(self._handle, out), "t2n_field_appearance_volume_counts")
         return {"bytes": int(out[0]), "builds": int(out[1]), "volume": int(out[2]), "direct": int(out[3])}
+
+    def feature_fusion_counts(self):
+        """Tile-marcher launches of the current native field that wrote their feature rows in the marcher's tail ('fused') and that ran the
+        feature stage as a kernel of its own ('unfused'); sub-launches of a split call count one each. Host-side counters: no device wait."""
+        out = (C.c_uint64 * 2)()
+        if self._handle is not None:
+            _lib.check(_lib.load().t2n_field_feature_fusion_counts(self._handle, out), "t2n_field_feature_fusion_counts")
+        return {"fused": int(out[0]), "unfused": int(out[1])}
 
     def density_sum_table(self, shift=(0, 0, 0)):
         """Diagnostic: the summed density table of the whole grid as the cache's builder computes it with its 4 x 4 x 4 boxes anchored at

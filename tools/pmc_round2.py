@@ -11,14 +11,21 @@ import os
 import sys
 
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
+names = collections.defaultdict(set)   # kernel -> the instantiations seen
 for f in glob.glob(os.path.join(sys.argv[1], "**", "*counter_collection.csv"), recursive=True):
     with open(f) as fh:
         for row in csv.DictReader(fh):
             full = row["Kernel_Name"].split("(")[0].replace("void ", "").replace("t2n::", "").replace("ss::", "")
             k = full.split("<")[0]
-            if full.startswith("k_mlp_ss3<true>"):
-                k = "k_mlp_ss3_tracked"      # round 5: the instantiation that returns at once on the bench weights must not dilute the head's means
+            args = [a.strip() for a in full[len(k) + 1:].rstrip(">").split(",")] if "<" in full else []
+            if k == "k_mlp_ss3" and args[:1] == ["true"]:
+                k = "k_mlp_ss3_tracked"      # round 5: the instantiations (rows by tile or by slot) that return at once on the bench weights must not dilute the head's means
+            if k == "k_march_tiles" and not (len(args) >= 5 and args[4] == "true"):
+                k = "k_march_tiles_norows"   # launches without the feature rows in the tail (the frames before the volume is built, unfused frames)
+            names[k].add(full)
             acc[k][row["Counter_Name"]].append(float(row["Counter_Value"]))
+if "k_march_tiles" not in acc and "k_march_tiles_norows" in acc:   # a run without fused frames: its marcher is THE marcher
+    acc["k_march_tiles"] = acc.pop("k_march_tiles_norows")
 import hashlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
