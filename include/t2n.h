@@ -248,6 +248,19 @@ int t2n_field_appearance_volume_counts(const t2n_field* f, uint64_t out[4]);
 int t2n_field_set_feature_fusion(t2n_field* f, int on);
 int t2n_field_feature_fusion_counts(const t2n_field* f, uint64_t out[2]);
 int t2n_render_list_shape(int64_t n_rays, int n_samples, int entries_per_ray, uint64_t out[6]);
+/* Staged rows of a fused launch. The 64 rays of a tile are less than a voxel apart, so the entries a step pair emits lie in the <= 4 x 4 x 4
+ * corner box whose density taps the pair read. With staging on, a wave logs its emitting step pairs (box origin, who emitted) in LDS while
+ * it marches; its tail then walks the entries in emission order, copies each logged pair's corner box from the feature volume to LDS once
+ * and reads every row's eight corners there instead of fetching 8 x 128 B per entry. Slots, entries and rows are the direct tail's, bit for
+ * bit. A wave runs the direct tail when it emitted on a step pair outside the table path, logged more than 32 pairs or its list region did
+ * not fit; rays handed to k_compact_list and voided regions keep the direct rows. A launch is staged only when the appearance and density
+ * factor sets have the same grid (the box is the box of the density taps) of fewer than 1024 texels per axis. Default of a new handle: on.
+ * t2n_field_row_staging_counts: out[0] / out[1] = waves of the handle's LAST fused tile-marcher launch whose tail wrote its rows from LDS
+ * boxes / in the direct form (both 0 when that launch was not staged: off, unequal grids, unfused). The waves count themselves on the device
+ * in words 50 / 51 of each sub-list's line of the launch's counter block; the call waits for that launch's stream and reads the block, so
+ * the workspace of that launch must still be allocated. */
+int t2n_field_set_row_staging(t2n_field* f, int on);
+int t2n_field_row_staging_counts(const t2n_field* f, uint64_t out[2]);
 /* DIAGNOSTIC, for tests of the feature stage: the stage alone on caller-made appearance lists. app_pos: device [8][list_cap] entries
  * (x, y, z normalised to [-1, 1], compositing weight); counters: device block of 8 x 64 words, word 64 l = entries of sub-list l (word 32
  * is the stage's f16-range flag: zero it); feat: device [feat_rows][32] rows, row 32 t + s = entry s of tile t, tiles numbered through

@@ -1001,6 +1001,22 @@ extern "C" int t2n_field_feature_fusion_counts(const t2n_field* f, uint64_t out[
     out[0] = f->fusion_counts[0]; out[1] = f->fusion_counts[1];
     return T2N_OK;
 }
+// ---- the tail's rows from corner boxes staged in LDS (t2n_march_tiles.hip) ----------------------------------------------------------
+extern "C" int t2n_field_set_row_staging(t2n_field* f, int on) {
+    if (!f) { set_error("t2n_field_set_row_staging: NULL field"); return T2N_ERR_INVALID; }
+    f->row_staging_on = on ? 1 : 0;
+    return T2N_OK;
+}
+extern "C" int t2n_field_row_staging_counts(const t2n_field* f, uint64_t out[2]) {
+    if (!f || !out) { set_error("t2n_field_row_staging_counts: NULL argument"); return T2N_ERR_INVALID; }
+    out[0] = out[1] = 0;
+    if (!f->rows_counters) return T2N_OK;
+    unsigned raw[kLists * kCounterStride];
+    T2N_HIP(hipStreamSynchronize((hipStream_t)f->rows_stream));
+    T2N_HIP(hipMemcpy(raw, f->rows_counters, sizeof(raw), hipMemcpyDeviceToHost));
+    for (int l = 0; l < kLists; ++l) { out[0] += raw[l * kCounterStride + kRowsStagedWord]; out[1] += raw[l * kCounterStride + kRowsDirectWord]; }
+    return T2N_OK;
+}
 extern "C" int t2n_render_list_shape(int64_t n_rays, int n_samples, int entries_per_ray, uint64_t out[6]) {
     if (n_rays <= 0 || n_samples <= 0 || entries_per_ray < 0 || !out) { set_error("t2n_render_list_shape: bad argument"); return T2N_ERR_INVALID; }
     const Carve c = carve_workspace(n_rays, n_samples, true, true, (unsigned)entries_per_ray);

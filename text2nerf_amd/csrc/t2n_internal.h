@@ -174,6 +174,10 @@ struct t2n_field {
     // holds the current feature volume and a row per list slot writes its rows there and runs no feature kernel
     int fusion_on = 1;
     unsigned long long fusion_counts[2] = {0, 0};      // tile-marcher launches with the rows in the marcher's tail / with the feature stage
+    // the tail's rows from corner boxes staged in LDS (t2n_field_set_row_staging); the counter block and stream of the last tile-marcher
+    // launch (NULL: it wrote no rows in its tail), where t2n_field_row_staging_counts reads the waves' counts
+    int row_staging_on = 1;
+    const unsigned* rows_counters = nullptr; void* rows_stream = nullptr;
 };
 
 namespace t2n {
@@ -279,6 +283,9 @@ constexpr int kRangeFlagWord = 32;
 constexpr int kKeptMagicWord = 33, kKeptRowsWord = 34;
 constexpr int kOverflowWord = 35;   // raised by the march kernels when a ray's appearance entries fit no sub-list (budgeted lists only)
 constexpr int kHeadPlanWord = 40;      // general view-dependent heads: the forward's device-side plan (HeadPlanDev, 10 words) lives here
+// words 50 / 51 of EVERY sub-list's counter line (a fused tile-marcher launch with staged rows): waves of that XCD whose tail wrote its rows
+// from LDS boxes / in the direct form
+constexpr int kRowsStagedWord = 50, kRowsDirectWord = 51;
 constexpr int kFailEntriesWord = 36;   // appearance entries of the rays that fit no sub-list (finished by k_finish_rays): the next budget counts them
 constexpr unsigned kKeptMagic = 0x4b455054u;   // "KEPT"
 int launch_mlp_ss(t2n_field* f, const float* feat, const unsigned* counters_dev, unsigned list_cap, unsigned tile_hi, float4* app_rgb,

@@ -25,6 +25,7 @@
 // (k_density_sum_table, density_cache_prepare) and the CACHED instantiations read a cell's eight entries there — the same bits,
 // without the per-step-pair loads, MFMAs, LDS table and fences (C2 frame: 0.51 -> 0.38 ms; profiles/march_density_cache_ab.txt).
 // Replaces the same reference lines as k_march (see t2n_march.hip).
+#include <type_traits>
 #include "t2n_device.h"
 #include "t2n_app_rows.h"
 
@@ -264,6 +265,83 @@ __device__ __forceinline__ void slot_rows(const FieldDev& F, const float4* __res
     av_slot_rows(F.app, vol, app_pos + slot, feat + slot * 32u, count, lane);
 }
 
+// ---- STAGE: the tail's rows from corner boxes staged in LDS ---------------------------------------------------------------------------
+// The 64 rays of a tile are less than a voxel apart, so all entries a step pair emits lie in the pair's tap box (<= 4 x 4 x 4 corners,
+// the box whose summed-table entries the pair read). The step loop logs every emitting pair (box origin, the ballots of the lanes that
+// emitted at step 0 / step 1) in a wave-private LDS log; the tail then walks its entries in EMISSION order instead of list order: per
+// logged pair it copies the box's corners from the volume to LDS once (8 coalesced wave loads instead of 8 x 128 B per entry) and
+// every row pass reads its eight corners there — no pass holds a dependent global load. Slots, entries and rows are what the direct
+// tail writes, bit for bit. A wave whose log overflowed, or that emitted on a pair outside the table path, runs the direct tail.
+// Per wave: the box | count, direct flag | the log.
+constexpr int kRsLogMax = 32;
+constexpr unsigned kRsBoxBytes = 64u * kAvBoxCornerBytes;
+constexpr unsigned kRsHdrBytes = 16u;
+constexpr unsigned kRsRecWords = 6u;                  // origin (10 bits per axis), spare, ballot of step 0 (lo, hi), ballot of step 1 (lo, hi)
+constexpr unsigned kRsWaveBytes = kRsBoxBytes + kRsHdrBytes + (unsigned)kRsLogMax * kRsRecWords * 4u;
+static_assert(4u * kRsWaveBytes <= 32768u && kRsWaveBytes % 16u == 0u, "five blocks per CU: at most 32 KB of LDS per block; 16-B aligned regions");
+
+// the corners of the box at (ox, oy, oz) -> registers: load j covers corners 8 j .. 8 j + 7, lane = corner 8 j + lane / 8, quad lane % 8
+// (one wave instruction = eight whole corners; quad 7 is not needed). Corners past the padded volume's last index read that index.
+struct RsBoxRegs { float4 p0, p1, p2, p3, p4, p5, p6, p7; };   // (named members: an array indexed in an unrolled loop stays in scratch)
+template <int J>
+__device__ __forceinline__ float4 rs_corner_load(const FieldDev& F, unsigned xq, int oy, int oz, int lane) {
+    const unsigned cy = (unsigned)min(oy + ((J & 1) * 2 + (lane >> 5)), F.app.H[0]), cz = (unsigned)min(oz + (J >> 1), F.app.H[1]);
+    const unsigned off = umad24(umad24(cz, (unsigned)F.app.H[0] + 1u, cy), F.av_row, xq);
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(F.avol) + off);
+}
+__device__ __forceinline__ RsBoxRegs rs_box_load(const FieldDev& F, int ox, int oy, int oz, int lane) {
+    // (the eighth lane of a corner repeats quad 6: nothing of it is kept)
+    const unsigned xq = (unsigned)min(ox + ((lane >> 3) & 3), F.app.W[0]) * kAvCornerBytes + (unsigned)min(lane & 7, 6) * 16u;
+    RsBoxRegs b;
+    b.p0 = rs_corner_load<0>(F, xq, oy, oz, lane); b.p1 = rs_corner_load<1>(F, xq, oy, oz, lane);
+    b.p2 = rs_corner_load<2>(F, xq, oy, oz, lane); b.p3 = rs_corner_load<3>(F, xq, oy, oz, lane);
+    b.p4 = rs_corner_load<4>(F, xq, oy, oz, lane); b.p5 = rs_corner_load<5>(F, xq, oy, oz, lane);
+    b.p6 = rs_corner_load<6>(F, xq, oy, oz, lane); b.p7 = rs_corner_load<7>(F, xq, oy, oz, lane);
+    return b;
+}
+// one dword of each of the box's 64 corners (lane = corner): their lines are on the way to the CU's L1; the caller hands the value to
+// rs_touch_done behind the work the fetch runs beside (an unused load would be dropped, a volatile one waited for at once)
+__device__ __forceinline__ unsigned rs_box_touch(const FieldDev& F, int ox, int oy, int oz, int lane) {
+    const unsigned cx = (unsigned)min(ox + (lane & 3), F.app.W[0]), cy = (unsigned)min(oy + ((lane >> 2) & 3), F.app.H[0]);
+    const unsigned cz = (unsigned)min(oz + (lane >> 4), F.app.H[1]);
+    const unsigned off = umad24(umad24(cz, (unsigned)F.app.H[0] + 1u, cy), F.av_row, cx * kAvCornerBytes);
+    return *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(F.avol) + off);
+}
+__device__ __forceinline__ void rs_touch_done(unsigned v) { asm volatile("" ::"v"(v)); }
+__device__ __forceinline__ void rs_box_store(char* __restrict__ box, int lane, const RsBoxRegs& b) {
+    if ((lane & 7) < 7) {
+        constexpr int S = 8 * (int)kAvBoxCornerBytes;
+        char* __restrict__ d = box + (unsigned)(lane >> 3) * kAvBoxCornerBytes + (unsigned)(lane & 7) * 16u;
+        *reinterpret_cast<float4*>(d) = b.p0;         *reinterpret_cast<float4*>(d + S) = b.p1;
+        *reinterpret_cast<float4*>(d + 2 * S) = b.p2; *reinterpret_cast<float4*>(d + 3 * S) = b.p3;
+        *reinterpret_cast<float4*>(d + 4 * S) = b.p4; *reinterpret_cast<float4*>(d + 5 * S) = b.p5;
+        *reinterpret_cast<float4*>(d + 6 * S) = b.p6; *reinterpret_cast<float4*>(d + 7 * S) = b.p7;
+    }
+}
+__device__ __forceinline__ int rs_permute(int dest, int v) { return __builtin_amdgcn_ds_permute(dest << 2, v); }
+// The rows of the entries one step of a logged pair emitted: `mask` = the lanes that hold one (`ent`, list slot `slot`). The entries are
+// compacted across lanes (rank by mbcnt, forward permute; the other lanes fill the positions behind them), then eight entries per pass,
+// eight lanes per entry, as in av_slot_rows.
+__device__ __forceinline__ void rs_rows(const FieldDev& F, const AvVolume& vol, const AvBox& box, unsigned long long mask, const float4 ent,
+                                        unsigned slot, float* __restrict__ feat, int lane) {
+    const int cnt = __popcll(mask);
+    const int rank = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+    const bool bit = (mask >> lane) & 1ull;
+    const int dest = bit ? rank : cnt + (lane - rank);
+    const int px = rs_permute(dest, __float_as_int(ent.x)), py = rs_permute(dest, __float_as_int(ent.y)), pz = rs_permute(dest, __float_as_int(ent.z));
+    const int pw = rs_permute(dest, __float_as_int(ent.w)), ps = rs_permute(dest, (int)slot);
+    const int e = lane >> 3, q = lane & 7;
+#pragma unroll 1
+    for (int s0 = 0; s0 < cnt; s0 += 8) {
+        const int src = s0 + e;
+        const float4 mine = make_float4(__int_as_float(__shfl(px, src)), __int_as_float(__shfl(py, src)), __int_as_float(__shfl(pz, src)),
+                                        __int_as_float(__shfl(pw, src)));
+        const unsigned sl = (unsigned)__shfl(ps, src);
+        const bool live = src < cnt;
+        av_feature_row<8>(F.app, vol, mine, live, q, feat + (size_t)(live ? sl : 0u) * 32u + 4u * (unsigned)q, live, box);
+    }
+}
+
 constexpr int kDenseLd = 20;                          // floats per ray row of the transpose tile (16 steps + pad, 16-B aligned)
 constexpr int kDenseFloats = 64 * kDenseLd;           // per wave: the weights tile
 struct __attribute__((aligned(4))) F4U { float x, y, z, w; };   // row segments of an [n_rays, N] tensor are only 4-B aligned for odd N
@@ -308,7 +386,8 @@ constexpr int mt_waves(bool dense, bool cached) { return cached ? (dense ? T2N_M
 // also produces the feature rows of the slots it filled or voided — eight corner fetches and 64 multiply-adds per entry, work bound by
 // the texture addresser that runs beside the other waves' marching (bound by VALU issue) instead of in a kernel of its own behind
 // this one. Everything the step loop kept in registers is dead by then: the step loop's allocation is what it was.
-template <bool DENSE, bool ALPHA = false, bool RELU = false, bool CACHED = false, bool ROWS = false>
+// STAGE (ROWS only): the tail's rows from corner boxes staged in LDS, see kRsLogMax above.
+template <bool DENSE, bool ALPHA = false, bool RELU = false, bool CACHED = false, bool ROWS = false, bool STAGE = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DENSE, CACHED), mt_waves(DENSE, CACHED)))) void k_march_tiles(const TileArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -320,16 +399,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
     }
     float* __restrict__ wt = smem + (CACHED ? 0 : 4 * kStageFloats) + (size_t)wid * kDenseFloats;   // DENSE only
     const FieldDev& F = a.F;
+    static_assert(!STAGE || ROWS, "staged rows: a tail that writes rows");
+    // STAGE only: box | header | log (the wave's offset as a scalar: a lane value would sit in a register pair across the step loop)
+    char* __restrict__ rs_box = reinterpret_cast<char*>(smem) + (unsigned)__builtin_amdgcn_readfirstlane(wid) * kRsWaveBytes;
+    unsigned* __restrict__ rs_hdr = reinterpret_cast<unsigned*>(rs_box + kRsBoxBytes);
+    if constexpr (STAGE) {
+        if (lane == 0) { rs_hdr[0] = 0u; rs_hdr[1] = 0u; }   // logged pairs, direct flag (written and read in the loop by lane 0 alone)
+    }
     const int tiles_x = (a.img_w + 7) >> 3;
     const long long tile = (long long)blockIdx.x * 4 + wid;
     const int ty = (int)(tile / tiles_x), tx = (int)(tile - (long long)ty * tiles_x);
     const int px = tx * 8 + (lane & 7), py = ty * 8 + (lane >> 3);
     if (ty * 8 >= a.img_h) return;
     const bool have = px < a.img_w && py < a.img_h;
-    const long long r = have ? (long long)py * a.img_w + px : 0;
+    // (STAGE: the ray index in one register — a launch's rays fit an int, as its list slots do — the staged tail leaves no room for two)
+    typedef typename std::conditional<STAGE, int, long long>::type ray_t;
+    const ray_t r = have ? (ray_t)((long long)py * a.img_w + px) : 0;
     const int N = a.n_samples;
     Ray ray;
-    if (have) ray = load_ray(F, a.rays + r * a.ray_stride, a.ray_stride);
+    if (have) ray = load_ray(F, a.rays + (long long)r * a.ray_stride, a.ray_stride);
     else { ray.ox = ray.oy = ray.oz = 1e30f; ray.dx = ray.dy = ray.dz = 0.f; ray.tmin = 0.f; ray.last = 0.f; }
     int lo = N, hi = -1;
     if (have) ray_interval<false>(F, ray, N, lo, hi);
@@ -397,6 +485,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
         float part[kSteps];
 #pragma unroll
         for (int q = 0; q < kSteps; ++q) part[q] = 0.f;
+        unsigned emv = 0u;           // STAGE: bit q = the lane stored an entry at step q (one register: masks kept per step cost four scalars)
+        unsigned bo = 0u;            // STAGE: the pair took the table path (bit 30) and its box origin, 10 bits per axis, in ONE scalar
         if (okm) {
 #pragma unroll
             for (int q = 0; q < kSteps; ++q) A[q] = sample_axes_inbox(F.den, xn[q], yn[q], zn[q]);   // used by samples inside the box only (ok[q])
@@ -427,6 +517,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
             const bool ranged = !(bits & 0x40000000u);
             MT_T(p_axes);
             if (CACHED && ranged && span <= 4) {
+                if constexpr (STAGE) bo = 0x40000000u | (unsigned)amn[0] | (unsigned)amn[1] << 10 | (unsigned)amn[2] << 20;
                 // both samples' eight loads in flight together; a lane without a sample reads the table's first cell
                 unsigned off[kSteps];
                 CellTaps ct[kSteps];
@@ -484,7 +575,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
                 dep = fmaf(w, z[q], dep);
                 // in-kernel compaction: (x, y, z, w) of the samples above the threshold go to the ray's staging slice
                 if (w > F.thres) {
-                    if (napp < (unsigned)a.cap) a.scratch[(size_t)r * a.cap + napp] = make_float4(xn[q], yn[q], zn[q], w);
+                    if (napp < (unsigned)a.cap) {
+                        a.scratch[(size_t)r * a.cap + napp] = make_float4(xn[q], yn[q], zn[q], w);
+                        if constexpr (STAGE) emv |= 1u << q;
+                    }
                     ++napp;
                     if (napp == (unsigned)a.cap) ovf_from = idx + 1;
                 }
@@ -493,7 +587,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
                 ++nev;
                 w_out[q] = w;
             }
-            if (spill) a.wbuf[r * N + idx] = w_out[q];
+            if (spill) a.wbuf[(long long)r * N + idx] = w_out[q];
             if constexpr (DENSE) {
                 if (idx < N) {
                     const int c16 = idx & 15;
@@ -517,6 +611,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
                         }
                     }
                     lds_fence_w();
+                }
+            }
+        }
+        if constexpr (STAGE) {
+            // an emitting pair: one record (lane 0), or the wave's tail turns direct (pair outside the table path, log full)
+            if (__any(emv != 0u)) {
+                const unsigned long long b0 = __ballot((emv & 1u) != 0u), b1 = __ballot((emv & 2u) != 0u);
+                if (lane == 0) {
+                    const unsigned c = rs_hdr[0];
+                    if (!bo || c >= (unsigned)kRsLogMax) rs_hdr[1] = 1u;
+                    else {
+                        unsigned* __restrict__ rec = rs_hdr + 4 + c * kRsRecWords;
+                        rec[0] = bo; rec[1] = 0u;
+                        rec[2] = (unsigned)b0; rec[3] = (unsigned)(b0 >> 32); rec[4] = (unsigned)b1; rec[5] = (unsigned)(b1 >> 32);
+                        rs_hdr[0] = c + 1u;
+                    }
                 }
             }
         }
@@ -554,6 +664,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
     const bool fits = base + total <= a.list_cap;
     if (!fits && total) void_entries(a.app_pos, a.app_ray, list, a.list_cap, base, base + total, lane);
     const unsigned slot0 = list * a.list_cap + base + (incl - n);
+    // STAGE: the wave's tail runs staged when its region fits and every emitting pair is in the log
+    unsigned rs_n = 0u;
+    bool staged = false;
+    if constexpr (STAGE) {
+        lds_fence_w();
+        rs_n = (unsigned)__builtin_amdgcn_readfirstlane((int)rs_hdr[0]);
+        const unsigned flag = (unsigned)__builtin_amdgcn_readfirstlane((int)rs_hdr[1]);
+        staged = __builtin_amdgcn_readfirstlane((int)(fits && total)) && !flag;
+#ifdef T2N_MT_NO_TAIL_ROWS
+        staged = false;   // (timing-only build: the copy loop still fills the list)
+#endif
+    }
     if (have) {
         if (over || !fits) {
             const unsigned k = atomicAdd(a.ovf_count, 1u);
@@ -561,7 +683,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
             a.ray_app[r] = make_int4(ovf_from, (int)napp, nev, Lw > 0 ? (first | (Lw << 11)) : 0);   // k_compact_list finishes this ray
         } else {
             a.ray_app[r] = make_int4((int)slot0, fits ? (int)n : 0, nev, Lw > 0 ? (first | (Lw << 11)) : 0);
-            if (fits) {
+            if (fits && !staged) {
                 // four entries in flight per trip (a wave's tail lasts as long as its longest slice; one dependent round trip
                 // per entry otherwise)
                 const float4* __restrict__ src = a.scratch + (size_t)r * a.cap;
@@ -583,7 +705,73 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
         const unsigned ubase = (unsigned)__builtin_amdgcn_readfirstlane((int)base), utotal = (unsigned)__builtin_amdgcn_readfirstlane((int)total);
         unsigned cnt = utotal;
         if (ubase + utotal > a.list_cap) cnt = ubase < a.list_cap ? a.list_cap - ubase : 0u;
-        slot_rows(F, a.app_pos, a.feat, (size_t)list * a.list_cap + ubase, cnt, lane);
+        if constexpr (STAGE) {
+            // proof of path: one fire-and-forget atomic per wave with rows, on the XCD's counter line
+            if (lane == 0 && cnt) atomicAdd(&a.counters[list * kCounterStride + (staged ? kRowsStagedWord : kRowsDirectWord)], 1u);
+#ifdef T2N_RS_STATS   // (instrumented build: logged pairs and entries of the staged waves, words 52 / 53 of the XCD's counter line)
+            if (lane == 0 && staged) { atomicAdd(&a.counters[list * kCounterStride + 52], rs_n); atomicAdd(&a.counters[list * kCounterStride + 53], utotal); }
+#endif
+            if (staged) {
+                const AvVolume vol{F.avol, F.av_row, F.av_slice, (unsigned)F.app.H[0] + 1u};
+                const unsigned long long mine_m = __ballot(have && !over);   // (a ray handed to k_compact_list contributes nothing here)
+                // (the ray's staging slice from its index at every use: the address would sit in a register pair across the passes)
+                auto entry_at = [&](unsigned k) {
+                    int rr = (int)r;
+                    asm volatile("" : "+v"(rr));
+                    return a.scratch[(size_t)rr * a.cap + k];
+                };
+                const unsigned* __restrict__ log = rs_hdr + 4;
+                const unsigned last_k = (unsigned)a.cap - 1u;
+                // per record: the box to LDS, then the passes of its entries. While record m's passes run, the entries of record m + 1 are
+                // on their way to registers and the 64 lines of box m + 1 to this CU's L1 (rs_box_touch: the five-wave allocation has no
+                // room for a box in registers beside a pass), so the box load in front of a record's passes is a short round trip.
+                float4 ne0, ne1;
+                unsigned long long nm0, nm1;
+                unsigned kc = 0u;    // entries of this lane's ray walked so far
+                nm0 = ((unsigned long long)log[3] << 32 | log[2]) & mine_m; nm1 = ((unsigned long long)log[5] << 32 | log[4]) & mine_m;
+                nm0 = (unsigned long long)__builtin_amdgcn_readfirstlane((int)(nm0 >> 32)) << 32 | (unsigned)__builtin_amdgcn_readfirstlane((int)nm0);
+                nm1 = (unsigned long long)__builtin_amdgcn_readfirstlane((int)(nm1 >> 32)) << 32 | (unsigned)__builtin_amdgcn_readfirstlane((int)nm1);
+                unsigned nbo = (unsigned)__builtin_amdgcn_readfirstlane((int)log[0]);
+                ne0 = entry_at(min(kc, last_k));
+                ne1 = entry_at(min(kc + (unsigned)((nm0 >> lane) & 1ull), last_k));
+#pragma unroll 1
+                for (unsigned m = 0; m < rs_n; ++m) {
+                    // (a record whose emitting rays were all handed to k_compact_list later has nothing left: no box, no passes)
+                    const bool work = (nm0 | nm1) != 0ull;
+                    const AvBox box{rs_box, (int)(nbo & 1023u), (int)((nbo >> 10) & 1023u), (int)((nbo >> 20) & 1023u)};
+                    if (work) rs_box_store(rs_box, lane, rs_box_load(F, box.ox, box.oy, box.oz, lane));
+                    const float4 e0 = ne0, e1 = ne1;
+                    const unsigned long long m0 = nm0, m1 = nm1;
+                    const bool bit0 = (m0 >> lane) & 1ull, bit1 = (m1 >> lane) & 1ull;
+                    const unsigned k0 = kc, k1 = kc + (bit0 ? 1u : 0u);
+                    kc = k1 + (bit1 ? 1u : 0u);
+                    lds_fence_w();
+                    unsigned touched = 0u;
+                    if (m + 1 < rs_n) {
+                        const unsigned* __restrict__ rec = log + (m + 1) * kRsRecWords;
+                        nm0 = ((unsigned long long)rec[3] << 32 | rec[2]) & mine_m; nm1 = ((unsigned long long)rec[5] << 32 | rec[4]) & mine_m;
+                        nm0 = (unsigned long long)__builtin_amdgcn_readfirstlane((int)(nm0 >> 32)) << 32 | (unsigned)__builtin_amdgcn_readfirstlane((int)nm0);
+                        nm1 = (unsigned long long)__builtin_amdgcn_readfirstlane((int)(nm1 >> 32)) << 32 | (unsigned)__builtin_amdgcn_readfirstlane((int)nm1);
+                        nbo = (unsigned)__builtin_amdgcn_readfirstlane((int)rec[0]);
+                        if (nm0 | nm1) {
+                            touched = rs_box_touch(F, (int)(nbo & 1023u), (int)((nbo >> 10) & 1023u), (int)((nbo >> 20) & 1023u), lane);
+                            ne0 = entry_at(min(kc, last_k));
+                            ne1 = entry_at(min(kc + (unsigned)((nm0 >> lane) & 1ull), last_k));
+                        }
+                    }
+                    if (work) {
+                        // the entries to their slots (the values and slots of the direct tail's copy loop), then their rows
+                        if (bit0) { a.app_pos[slot0 + k0] = e0; a.app_ray[slot0 + k0] = (int)r; }
+                        if (bit1) { a.app_pos[slot0 + k1] = e1; a.app_ray[slot0 + k1] = (int)r; }
+#pragma unroll 1   // (one copy of the passes: two inlined copies push the tail past the five-wave allocation)
+                        for (int q = 0; q < kSteps; ++q)
+                            rs_rows(F, vol, box, q ? m1 : m0, q ? e1 : e0, slot0 + (q ? k1 : k0), a.feat, lane);
+                    }
+                    rs_touch_done(touched);
+                    lds_fence_w();   // the passes' reads of box m are done before box m + 1 overwrites it
+                }
+            } else slot_rows(F, a.app_pos, a.feat, (size_t)list * a.list_cap + ubase, cnt, lane);
+        } else slot_rows(F, a.app_pos, a.feat, (size_t)list * a.list_cap + ubase, cnt, lane);
 #endif
     }
 }
@@ -818,6 +1006,13 @@ int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h
     if (L.slot_rows && !rows) { set_error("launch_march_tiles: a fused frame needs the cached table, the feature volume, no mask and no weights rows"); return T2N_ERR_STATE; }
     a.feat = rows ? L.feat : nullptr;
     ++f->fusion_counts[rows ? 0 : 1];
+    // staged rows (t2n_field_set_row_staging): the box of a step pair is the box of its DENSITY taps, so it holds the entries' appearance
+    // cells only where both factor sets have the same tap indices
+    const FactorSet& fd = f->dev.den; const FactorSet& fa = f->dev.app;
+    const bool stage = rows && f->row_staging_on && fd.W[0] == fa.W[0] && fd.H[0] == fa.H[0] && fd.H[1] == fa.H[1] &&
+                       fa.W[0] < 1024 && fa.H[0] < 1024 && fa.H[1] < 1024 &&   // (the log packs the box origin into 10 bits per axis)
+                       L.n_rays <= 0x7fffffffll;                               // (the staged kernel holds the ray index in an int)
+    f->rows_counters = rows ? L.counters : nullptr; f->rows_stream = (void*)s;
     a.F.term_eps = (!L.weights && !L.z_vals && !L.sigma_ctx) ? f->term_eps : 0.f;   // (eval only: this marcher has no train form)
 #ifdef MT_PROF
     static unsigned long long* prof = nullptr;
@@ -835,10 +1030,11 @@ int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h
         hipLaunchKernelGGL(k_dense_fill, dim3((unsigned)((L.n_rays + 3) / 4)), dim3(256), 0, s, f->dev, L.rays, (long long)L.n_rays, L.ray_stride,
                            L.n_samples, L.weights, L.z_vals);
     const bool cached = f->dev.dsum != nullptr;
-    const size_t lds = (size_t)4 * ((cached ? 0 : kStageFloats) + (dense ? kDenseFloats : 0)) * sizeof(float);
+    const size_t lds = stage ? (size_t)4 * kRsWaveBytes : (size_t)4 * ((cached ? 0 : kStageFloats) + (dense ? kDenseFloats : 0)) * sizeof(float);
     const bool mask = f->dev.alpha != nullptr, relu = f->dev.act == T2N_ACT_RELU;
     ++f->dcache_counts[cached ? 0 : 1];
-#define T2N_MT_LAUNCH(D, A, R) do { if (rows) hipLaunchKernelGGL((k_march_tiles<D, A, R, true, !D && !A>), grid, dim3(256), lds, s, a); \
+#define T2N_MT_LAUNCH(D, A, R) do { if (stage) hipLaunchKernelGGL((k_march_tiles<D, A, R, true, !D && !A, !D && !A>), grid, dim3(256), lds, s, a); \
+                                    else if (rows) hipLaunchKernelGGL((k_march_tiles<D, A, R, true, !D && !A>), grid, dim3(256), lds, s, a); \
                                     else if (cached) hipLaunchKernelGGL((k_march_tiles<D, A, R, true>), grid, dim3(256), lds, s, a); \
                                     else hipLaunchKernelGGL((k_march_tiles<D, A, R, false>), grid, dim3(256), lds, s, a); } while (0)
     if (dense) { if (mask) { if (relu) T2N_MT_LAUNCH(true, true, true); else T2N_MT_LAUNCH(true, true, false); }

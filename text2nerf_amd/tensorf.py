@@ -440,6 +440,9 @@ class TensorBase(nn.Module):
         # (budgeted lists, small launches), write their feature rows in the tile marcher's tail and run no feature kernel (same frames
         # bit for bit; False = the feature stage stays a kernel of its own). See feature_fusion_counts().
         self.feature_fusion = True
+        # Fused frames read the corners of their feature rows from 4 x 4 x 4 corner boxes staged in LDS, one box per emitting step pair of
+        # a tile, instead of fetching eight corners per entry (same rows bit for bit; False = the direct tail). See row_staging_counts().
+        self.row_staging = True
         # Early ray termination of eval renders that return neither weights nor z_vals (evaluation(), render_views, ...): OPT-IN. The
         # reference never terminates (models/tensorBase.py:19-26,494-505: every in-box sample is evaluated), so the default 0.0 is its
         # sample-for-sample arithmetic (exact evaluated-sample counts). A threshold eps > 0 stops a ray whose transmittance fell below it:
@@ -905,6 +908,7 @@ class TensorBase(nn.Module):
             self._dcache_set = (True, 0)
             self._avol_set = (True, 0, 0)
             self._fusion_set = True
+            self._row_staging_set = True
             self._stage_shape_set = (0, 0)
             self._head_rows_set = 32
             self._alpha_key = "unset"
@@ -958,6 +962,10 @@ class TensorBase(nn.Module):
         if getattr(self, "_fusion_set", True) != fu:
             _lib.check(lib.t2n_field_set_feature_fusion(self._handle, 1 if fu else 0), "t2n_field_set_feature_fusion")
             self._fusion_set = fu
+        rs = bool(getattr(self, "row_staging", True))
+        if getattr(self, "_row_staging_set", True) != rs:
+            _lib.check(lib.t2n_field_set_row_staging(self._handle, 1 if rs else 0), "t2n_field_set_row_staging")
+            self._row_staging_set = rs
         shape = tuple(int(v) for v in self.feature_stage_shape)
         if getattr(self, "_stage_shape_set", (0, 0)) != shape:
             _lib.check(lib.t2n_field_set_feature_stage_shape(self._handle, shape[0], shape[1]), "t2n_field_set_feature_stage_shape")
@@ -1893,6 +1901,15 @@ class TensorBase(nn.Module):
         if self._handle is not None:
             _lib.check(_lib.load().t2n_field_feature_fusion_counts(self._handle, out), "t2n_field_feature_fusion_counts")
         return {"fused": int(out[0]), "unfused": int(out[1])}
+
+    def row_staging_counts(self):
+        """Waves of the current native field's last fused tile-marcher launch whose tail wrote its feature rows from corner boxes staged in
+        LDS ('staged') and in the direct form ('direct'); both 0 when that launch was not staged. Waits for that launch and reads its
+        counter block in the workspace."""
+        out = (C.c_uint64 * 2)()
+        if self._handle is not None:
+            _lib.check(_lib.load().t2n_field_row_staging_counts(self._handle, out), "t2n_field_row_staging_counts")
+        return {"staged": int(out[0]), "direct": int(out[1])}
 
     def density_sum_table(self, shift=(0, 0, 0)):
         """Diagnostic: the summed density table of the whole grid as the cache's builder computes it with its 4 x 4 x 4 boxes anchored at
