@@ -268,6 +268,17 @@ int t2n_field_row_staging_counts(const t2n_field* f, uint64_t out[2]);
  * volume = 0: the direct form; 1: the rows from the cached feature volume, built here if it is not current. */
 int t2n_field_feature_rows(t2n_field* f, const float* app_pos, const uint32_t* counters, uint32_t list_cap, int volume, float* feat,
                            uint32_t feat_rows, t2n_stream stream);
+/* DIAGNOSTIC, for tests of the appearance head: the sample-stationary head (k_mlp_ss3) alone on caller-made feature rows — no feature
+ * stage, no one-kernel tail, no exact redo. feat: device [feat_rows][32] fp32 rows, columns 0..26 the features, column 27 the entry's
+ * compositing weight, the rest unused. counters: device block of 8 x 64 words, word 64 l = entries of sub-list l (clamped to list_cap);
+ * word 32 is the head's f16-range flag: the caller zeroes it and reads it back. slot_rows = 0: row 32 t + s = entry s of tile t, tiles
+ * numbered through the sub-lists in order (feat_rows must cover min(tiles, tile_hi) x 32 rows: a partial tile's dead rows are read);
+ * slot_rows = 1: row = list slot l * list_cap + entry (feat_rows >= 8 list_cap; dead slots are never read). Tiles from tile_hi on are
+ * left alone. app_rgb: device [8 list_cap] float4 by list slot (r, g, b, the row's weight); slots without a live entry are not written.
+ * variant_out (host): the word the weight packer wrote, 1 = the untracked instantiation ran, 0 = the tracked one. Waits for the stream.
+ * Other heads and the exact-fp32 mode: T2N_ERR_UNSUPPORTED; sizes that do not cover the launch: T2N_ERR_INVALID. */
+int t2n_field_head_rows(t2n_field* f, const float* feat, uint32_t feat_rows, uint32_t* counters, uint32_t list_cap, uint32_t tile_hi,
+                        int slot_rows, float* app_rgb, uint32_t* variant_out, t2n_stream stream);
 /* DIAGNOSTIC, for tests of the feature stage's tile queue only (like the staging counters above, not part of the rendering API): the
  * shape of the feature stage's launch. At most `workgroups` workgroups of eight waves (0 = the default, 512), and `defer_cap` tiles
  * (1 .. 64; 0 = the default, 16) that a wave sets aside for its gathered loop before it drains them. Small values make one wave see

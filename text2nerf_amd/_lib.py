@@ -117,6 +117,8 @@ SIGNATURES = {
     "t2n_field_row_staging_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "t2n_render_list_shape": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "t2n_field_feature_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "t2n_field_head_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+                                      C.POINTER(C.c_uint32), C.c_void_p]),
     "t2n_field_density_sum_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "t2n_sample_ray": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),

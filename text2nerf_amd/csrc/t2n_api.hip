@@ -1042,6 +1042,25 @@ extern "C" int t2n_field_feature_rows(t2n_field* f, const float* app_pos, const 
     }
     return launch_feature_rows(f, (const float4*)app_pos, counters, list_cap, feat, feat_rows, s);
 }
+extern "C" int t2n_field_head_rows(t2n_field* f, const float* feat, uint32_t feat_rows, uint32_t* counters, uint32_t list_cap, uint32_t tile_hi,
+                                   int slot_rows, float* app_rgb, uint32_t* variant_out, t2n_stream stream) {
+    if (!f || !feat || !counters || !app_rgb || !variant_out || !list_cap || list_cap > 0x0fffffffu) { set_error("t2n_field_head_rows: bad argument"); return T2N_ERR_INVALID; }
+    if (!f->uploaded) { set_error("t2n_field_head_rows: the field has no uploaded parameters"); return T2N_ERR_STATE; }
+    if (f->desc.shading != T2N_SHADE_MLP_FEA_NOVIEW || !f->mlp_split) { set_error("t2n_field_head_rows: needs the fused MLP_Fea_noview head on split products"); return T2N_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    // the rows the launch will read, from the counters as the kernel reads them (a diagnostic: a synchronising copy is fine)
+    unsigned raw[kLists * kCounterStride];
+    T2N_HIP(hipStreamSynchronize(s));
+    T2N_HIP(hipMemcpy(raw, counters, sizeof(raw), hipMemcpyDeviceToHost));
+    unsigned long long tiles = 0;
+    for (int l = 0; l < kLists; ++l) { const unsigned c = raw[l * kCounterStride]; tiles += ((c < list_cap ? c : list_cap) + 31u) / 32u; }
+    if (tiles > tile_hi) tiles = tile_hi;
+    const unsigned long long need = slot_rows ? (unsigned long long)kLists * list_cap : tiles * 32ull;
+    if (feat_rows < need) { set_error("t2n_field_head_rows: feat_rows does not cover the rows the launch reads"); return T2N_ERR_INVALID; }
+    const int rc = launch_mlp_ss(f, feat, counters, list_cap, tile_hi, (float4*)app_rgb, counters + kRangeFlagWord, s, slot_rows != 0);
+    if (rc) return rc;
+    return ss_variant_word(f, variant_out, s);
+}
 extern "C" int t2n_field_density_sum_table(const t2n_field* f, const int* shift, float* out, t2n_stream stream) {
     if (!f || !shift || !out) { set_error("t2n_field_density_sum_table: NULL argument"); return T2N_ERR_INVALID; }
     if (!f->uploaded) { set_error("t2n_field_density_sum_table: the field has no uploaded factors"); return T2N_ERR_STATE; }

@@ -290,6 +290,7 @@ constexpr int kFailEntriesWord = 36;   // appearance entries of the rays that fi
 constexpr unsigned kKeptMagic = 0x4b455054u;   // "KEPT"
 int launch_mlp_ss(t2n_field* f, const float* feat, const unsigned* counters_dev, unsigned list_cap, unsigned tile_hi, float4* app_rgb,
                   unsigned* range_flag, hipStream_t s, bool slot_rows = false);   // slot_rows: the row of list slot s is feat + 32 s
+int ss_variant_word(t2n_field* f, unsigned* out, hipStream_t s);   // DIAGNOSTIC: which head instantiation the packed weights select
 // features_only: gather + basis stages only (the general heads take over); ctx_rows: capacity of the ctx buffers in rows
 
 // the general (unfused) view-dependent heads (t2n_heads.hip): MLP_Fea / MLP_PE / MLP input layout and launchers

@@ -992,5 +992,15 @@ int launch_mlp_ss(t2n_field* f, const float* feat, const unsigned* counters_dev,
     return T2N_OK;
 }
 
+// DIAGNOSTIC (t2n_field_head_rows): the word k_ss_scales wrote for the packed weights (1: the untracked kernel may run); waits for `s`
+int ss_variant_word(t2n_field* f, unsigned* out, hipStream_t s) {
+    using namespace ss;
+    if (!f->buf_ss) { set_error("ss_variant_word: the head's weights are not packed"); return T2N_ERR_STATE; }
+    const float* scales = (const float*)((uint4*)f->buf_ss + ((size_t)kW0 + kW1 + kW2)) + kBias;
+    T2N_HIP(hipMemcpyAsync(out, scales + 12, 4, hipMemcpyDeviceToHost, s));
+    T2N_HIP(hipStreamSynchronize(s));
+    return T2N_OK;
+}
+
 }  // namespace t2n
 

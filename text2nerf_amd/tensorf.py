@@ -1911,6 +1911,25 @@ class TensorBase(nn.Module):
             _lib.check(_lib.load().t2n_field_row_staging_counts(self._handle, out), "t2n_field_row_staging_counts")
         return {"staged": int(out[0]), "direct": int(out[1])}
 
+    def head_rows(self, feat, counters, list_cap, tile_hi=0xffffffff, slot_rows=False, app_rgb=None):
+        """Diagnostic: the sample-stationary appearance head alone on caller-made feature rows (t2n_field_head_rows). feat: [rows, 32]
+        float32 on the device (columns 0..26 features, 27 the weight); counters: int32 [8 * 64] block (word 64 l = sub-list l's count,
+        word 32 the range flag, zeroed by the caller); app_rgb: [8 * list_cap, 4] float32 to write into (slots without a live entry keep
+        what they held; a new zero tensor when None). Returns (app_rgb, flag, variant): variant 1 = the untracked kernel ran."""
+        h = self.sync_params()
+        dev = feat.device
+        assert feat.dtype == torch.float32 and feat.dim() == 2 and feat.shape[1] == 32 and feat.is_contiguous()
+        assert counters.dtype == torch.int32 and counters.numel() == 8 * 64 and counters.is_contiguous()
+        if app_rgb is None:
+            app_rgb = torch.zeros((8 * int(list_cap), 4), dtype=torch.float32, device=dev)
+        assert app_rgb.dtype == torch.float32 and app_rgb.numel() == 8 * int(list_cap) * 4 and app_rgb.is_contiguous()
+        variant = C.c_uint32(0xffffffff)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().t2n_field_head_rows(h, _lib.ptr(feat), int(feat.shape[0]), _lib.ptr(counters), int(list_cap), int(tile_hi),
+                                                       1 if slot_rows else 0, _lib.ptr(app_rgb), C.byref(variant), _lib.current_stream_ptr(dev)),
+                       "t2n_field_head_rows")
+        return app_rgb, int(counters[32].item()), int(variant.value)
+
     def density_sum_table(self, shift=(0, 0, 0)):
         """Diagnostic: the summed density table of the whole grid as the cache's builder computes it with its 4 x 4 x 4 boxes anchored at
         4 b - shift per axis: a [grid z + 1, grid y + 1, grid x + 1] tensor (the last index of every axis repeats the clamped texel)."""
