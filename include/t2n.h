@@ -325,6 +325,36 @@ int t2n_shade_at(const t2n_field* f, const float* xyz_norm, const float* viewdir
 int t2n_raw2alpha(const float* sigma, const float* dist, int64_t n_rays, int n_samples, float* alpha, float* weights,
                   float* bg, t2n_stream stream);
 
+/* ---- geometry outputs of a view (csrc/t2n_geometry.hip; not in the reference, which returns the expected depth only).
+ * Density-feature gradient: f(p) = compute_densityfeature at world point p; grad f is its exact gradient under the kernels' own
+ *   trilinear arithmetic: on axis a the difference of the two taps axis_taps selects (clamped indices, so 0 on the exact upper face;
+ *   the cell is the one the float32 coordinate falls into: floor, one-sided at a cell face) times inv_aabb_size[a] (grid[a] - 1) / 2.
+ *   softplus' > 0 and relu' >= 0, so -grad f / |grad f| is the direction of steepest density decrease: no activation derivative is
+ *   needed for a unit normal. xyz_norm [n,3] normalised like t2n_density_at's; feat [n] is that call's feature bit for bit;
+ *   grad_world [n,3] is in world units. Either output may be NULL.
+ * Per ray, for EVAL sampling: the z values, box mask, world-z gate, AlphaGridMask test and last-interval-0 rule of the render call
+ *   without T2N_FLAG_TRAIN; early termination is ignored (a ray is always marched to its end). With w_i, z_i as in raw2alpha
+ *   (models/tensorBase.py:19-26,448,475):
+ *     acc          = sum_i w_i, and depth = the render call's depth_map, with its (1 - acc) rays[..., -1] term
+ *     depth_var    = sum_i w_i (z_i - depth)^2: compute_depth_loss's pred_var (utils.py:306-320) without its + 1e-8; float64 moments
+ *                    about the first valid sample's depth, rounded once
+ *     depth_median = z_k + dist_k (quantile - C_{k-1}) / w_k, with C_i = sum_{j <= i} w_j, k the first sample with C_k >= quantile
+ *                    and dist_k the UNSCALED interval z_{k+1} - z_k: w_k is taken as spread over the interval that produced it, so
+ *                    the value is continuous and monotone in the quantile. Rays whose cumulative weight never reaches the quantile
+ *                    get miss_depth.
+ *     normal       = sum_i w_i n_i, n_i = -grad f(p_i) / max(|grad f(p_i)|, FLT_MIN): world space, NOT normalised (length <= acc;
+ *                    exactly 0 for a ray without weight)
+ *   Every output [n_rays] (normal [n_rays,3]) may be NULL. No workspace, no atomics, no host read; two calls give the same bits and a
+ *   ray's outputs depend neither on n_rays nor on its place in the batch. bf16 factor storage and alpha masks are supported.
+ *   quantile outside (0,1): T2N_ERR_INVALID. NDC sampling is a flag of one render call (T2N_FLAG_NDC), not a property of the field,
+ *   and this entry point takes no flags: it has no NDC form (a normal in NDC space means nothing); the Python mirror refuses
+ *   ndc_ray=True, and general-shape fields, which have no native handle. */
+int t2n_density_grad_at(const t2n_field* f, const float* xyz_norm, int64_t n, float* feat, float* grad_world /*[n,3]*/,
+                        t2n_stream stream);
+int t2n_render_geometry(const t2n_field* f, const float* rays, int64_t n_rays, int ray_stride, int n_samples, float quantile,
+                        float miss_depth, float* acc, float* depth, float* depth_median, float* depth_var,
+                        float* normal /*[n_rays,3]*/, t2n_stream stream);
+
 /* ---- a-3/a-4: the render call. Replaces the chunk loop of OctreeRender_trilinear_fast (renderer.py:28-42) and
  * TensorBase.forward (models/tensorBase.py:436-507) for ndc_ray=False, alphaMask=None.
  *   rays      [n_rays, ray_stride] fp32 rows, first 6 = (o, d); the LAST channel feeds depth's background term (:505)

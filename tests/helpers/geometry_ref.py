@@ -1,0 +1,353 @@
+"""Float64 reference of the geometry outputs (csrc/t2n_geometry.hip; definitions in include/t2n.h).
+
+Sample positions, cells and tap indices come from the oracle's float32 geometry (oracle_torch.sample_ray / normalize_coord /
+sample_alpha, which the suite holds bit-equal to the kernels' z values and normalised coordinates) and from `taps`, float32
+arithmetic identical to the kernels' axis_taps. Everything after that is float64. Given float64 coordinates, `taps` runs in float64
+too: that form is compared with torch's grid_sample and autograd in tests/test_geometry_cpu.py.
+
+`mutate` switches on one deliberate error; the CPU file checks that every checker used on the device catches each of them."""
+import numpy as np
+import torch
+
+from oracle import oracle_torch as O
+
+MAT_MODE = ((0, 1), (0, 2), (1, 2))
+VEC_MODE = (2, 1, 0)
+# tolerances at which tests/test_hip_parity.py holds the eval forward's weights and depth to the oracle on the TINY field
+T_W, T_D = 5e-6, 2e-4          # W_ATOL, DEPTH_ATOL
+EPS32 = 2.0 ** -24             # one float32 rounding, relative
+# Float32 roundings that reach one term of an element of grad_world (pair_grad / density_grad_quad), counted in the code; the
+# coordinate ix, floor and w1 = ix - floor are the reference's own (w1 is exact):
+#   line-axis term P_c (l1 - l0)_c: w0 = 1 - w1 on the plane's two axes (2), their product (1), tap x weight (1), the three fma of
+#     taps_plane (3); the tap difference (1)                                                                                      8
+#   plane-axis term (dP/du)_c L_c: tap difference (1), w0 (1), product (1), fma (1); L_c: w0 (1), product (1), fma (1)             7
+#   either kind: the lane's 12 fma over three pairs x four channels (12), the quad reduction's two additions (2)                   14
+#   the scale inv (grid - 1) (1; the halving is exact) and its product with the sum (1)                                            2
+# m = 8 + 14 + 2.
+M_GRAD = 24
+GAMMA = (M_GRAD + 2) * EPS32
+# feat (k_density_at's chain): P_c (7), L_c (3), 12 fma, 2 additions
+GAMMA_F = (24 + 2) * EPS32
+
+
+def taps(g, size):
+    """axis_taps of csrc/t2n_device.h in g's own dtype: clamped tap indices, float64 weights (0 for out-of-range taps)."""
+    ix = ((g + 1) / 2) * (size - 1)
+    f0 = torch.floor(ix)
+    w1 = (ix - f0).double()        # exact in float32: ix and floor(ix) are less than one apart
+    w0 = 1.0 - w1
+    ok0 = (f0 >= 0) & (f0 <= size - 1)
+    ok1 = (f0 >= -1) & (f0 <= size - 2)
+    i = torch.clamp(f0, -1, size - 1).long()
+    return dict(i0=i.clamp(min=0), i1=(i + 1).clamp(max=size - 1), w0=w0 * ok0, w1=w1 * ok1)
+
+
+def density_grad(params64, xn, inv, grid, mutate=None):
+    """f, its world gradient [n,3] and the sums of the absolute values of their terms (A_f [n], A_grad [n,3]) at normalised points
+    xn [n,3] (float32: the kernels' cells; float64: the continuous form). params64: float64 factors in the reference layouts; inv:
+    inv_aabb_size as the field holds it."""
+    n = xn.shape[0]
+    T = [taps(xn[:, a], int(grid[a])) for a in range(3)]
+    f = torch.zeros(n, dtype=torch.float64)
+    Af = torch.zeros(n, dtype=torch.float64)
+    g = torch.zeros(n, 3, dtype=torch.float64)
+    A = torch.zeros(n, 3, dtype=torch.float64)
+    for k in range(3):
+        m0, m1 = MAT_MODE[k]
+        v = VEC_MODE[k]
+        plane = params64[f"density_plane.{k}"][0]          # [C, g[m1], g[m0]]
+        line = params64[f"density_line.{k}"][0, :, :, 0]   # [C, g[v]]
+        ax, ay, al = T[m0], T[m1], T[v]
+        nw, ne = plane[:, ay["i0"], ax["i0"]], plane[:, ay["i0"], ax["i1"]]
+        sw, se = plane[:, ay["i1"], ax["i0"]], plane[:, ay["i1"], ax["i1"]]
+        l0, l1 = line[:, al["i0"]], line[:, al["i1"]]
+        wx0, wx1, wy0, wy1, wl0, wl1 = ax["w0"], ax["w1"], ay["w0"], ay["w1"], al["w0"], al["w1"]
+        P = nw * (wy0 * wx0) + ne * (wy0 * wx1) + sw * (wy1 * wx0) + se * (wy1 * wx1)
+        aP = nw.abs() * (wy0 * wx0) + ne.abs() * (wy0 * wx1) + sw.abs() * (wy1 * wx0) + se.abs() * (wy1 * wx1)
+        L = l0 * wl0 + l1 * wl1
+        aL = l0.abs() * wl0 + l1.abs() * wl1
+        du = (ne - nw) * wy0 + (se - sw) * wy1             # along m0
+        adu = (ne.abs() + nw.abs()) * wy0 + (se.abs() + sw.abs()) * wy1
+        dv = (sw - nw) * wx0 + (se - ne) * wx1             # along m1
+        adv = (sw.abs() + nw.abs()) * wx0 + (se.abs() + ne.abs()) * wx1
+        dl = l1 - l0
+        adl = l1.abs() + l0.abs()
+        f += (P * L).sum(0)
+        Af += (aP * aL).sum(0)
+        a0, a1 = (m1, m0) if mutate == "swap_axis" else (m0, m1)
+        g[:, a0] += (du * L).sum(0)
+        A[:, a0] += (adu * aL).sum(0)
+        g[:, a1] += (dv * L).sum(0)
+        A[:, a1] += (adv * aL).sum(0)
+        if mutate != "drop_line":
+            g[:, v] += (P * dl).sum(0)
+            A[:, v] += (aP * adl).sum(0)
+    scale = torch.as_tensor(np.asarray(inv, np.float32)).double() * (torch.tensor([int(x) for x in grid], dtype=torch.float64) - 1) / 2
+    return f, g * scale, Af, A * scale
+
+
+def pointwise_ratio(got, want, A, gamma=GAMMA):
+    """max over elements of |got - want| / (gamma A); an element whose terms are all zero (A = 0) must be exactly `want`."""
+    got, want, A = (np.asarray(x, np.float64) for x in (got, want, A))
+    err = np.abs(got - want)
+    if np.any((A == 0) & (err != 0)):
+        return float("inf")
+    return float((err / np.where(A == 0, 1.0, gamma * A)).max()) if err.size else 0.0
+
+
+def params64_of(params, bf16=False):
+    """float64 factors from a numpy state dict; bf16: rounded to bfloat16 first (t2n_field_set_factor_storage)."""
+    out = {}
+    for k, v in params.items():
+        if k.startswith("density_"):
+            t = torch.from_numpy(np.asarray(v, np.float32))
+            out[k] = (t.bfloat16().float() if bf16 else t).double()
+    return out
+
+
+def inv_of(cfg):
+    a = torch.tensor(cfg.aabb, dtype=torch.float32)
+    return (2.0 / (a[1] - a[0])).numpy()
+
+
+def ulp32(x):
+    return np.spacing(np.abs(np.asarray(x, np.float64)).astype(np.float32)).astype(np.float64)
+
+
+class RayRef:
+    """Everything the ray-level checks need, for eval rays [R, >= 6] (float32) at N samples."""
+
+    def __init__(self, cfg, params64, rays, N, mutate=None):
+        rays = torch.as_tensor(np.asarray(rays, np.float32))
+        self.N, self.R, self.mutate = int(N), rays.shape[0], mutate
+        pts, z, valid = O.sample_ray(cfg, rays[:, :3], rays[:, 3:6], self.N)
+        inbox = valid
+        if cfg.alpha_volume is not None and valid.any():      # models/tensorBase.py:451-456
+            keep = O.sample_alpha(cfg, pts[valid]) > 0
+            valid = valid.clone()
+            valid[valid.clone()] = keep
+        valid = valid & (pts[:, :, 2] > cfg.z_gate)
+        box = inbox & (pts[:, :, 2] > cfg.z_gate)          # the kernel's window [first, last]: box test and z gate, not the mask
+        idx = torch.arange(self.N)[None]
+        self.first = torch.where(box, idx, self.N).amin(-1).numpy()
+        self.Lw = np.maximum(torch.where(box, idx, -1).amax(-1).numpy() - self.first + 1, 0)
+        xn = O.normalize_coord(cfg, pts)
+        dist32 = torch.cat([z[:, 1:] - z[:, :-1], torch.zeros_like(z[:, :1])], -1)
+        self.z, self.dist, self.valid = z.double().numpy(), dist32.double().numpy(), valid.numpy()
+        sigma = torch.zeros(z.shape, dtype=torch.float64)
+        nrm = torch.zeros(z.shape + (3,), dtype=torch.float64)
+        perr = torch.zeros(z.shape, dtype=torch.float64)      # min(2, gamma |A_i| / |grad f_i|): the unit normal's point-wise bound
+        if valid.any():
+            f, g, _, A = density_grad(params64, xn[valid], inv_of(cfg), cfg.grid_size, mutate=mutate)
+            x = f + cfg.density_shift
+            sigma[valid] = torch.where(x > 20, x, torch.log1p(torch.exp(torch.clamp(x, max=20.0))))
+            ln = g.norm(dim=-1)
+            tiny = float(np.finfo(np.float32).tiny)
+            nrm[valid] = -g / ln.clamp_min(tiny)[:, None]
+            perr[valid] = torch.minimum(torch.full_like(ln, 2.0), GAMMA * A.norm(dim=-1) / ln.clamp_min(1e-300))
+        alpha, w, _ = O.raw2alpha(sigma, torch.from_numpy(self.dist) * float(np.float32(cfg.distance_scale)))
+        self.w = w.numpy()
+        if mutate == "drop_carry":       # the transmittance starts again at 1 in every 64-sample block of the window
+            self.w = self._blockwise(lambda a: a * np.concatenate([[1.0], np.cumprod(1.0 - a + 1e-10)[:-1]]), alpha.numpy())
+        self.last = rays[:, -1].double().numpy()
+        self.acc = self.w.sum(-1)
+        self.depth = (self.w * self.z).sum(-1) + (1.0 - self.acc) * self.last
+        centre = (self.w * self.z).sum(-1) / np.maximum(self.acc, 1e-300) if mutate == "var_about_mean" else self.depth
+        dz = self.z - centre[:, None]
+        self.var = (self.w * dz * dz).sum(-1)
+        self.normal = (self.w[..., None] * nrm.numpy()).sum(1)
+        self.nvalid = self.valid.sum(-1)
+        # bounds of the issue, per ray
+        self.var_bound = T_W * (self.valid * dz * dz).sum(-1) + 2 * T_D * (self.w * np.abs(dz)).sum(-1) + 2.0 ** -22 * self.var
+        self.normal_bound = T_W * self.nvalid + (self.w * perr.numpy()).sum(-1)
+        self.delta = self.N * T_W
+        self.cum = np.cumsum(self.w, -1)
+        if mutate == "drop_ccum":        # the cumulative weight starts again at 0 in every 64-sample block of the window
+            self.cum = self._blockwise(np.cumsum, self.w)
+        self.scale = float(np.float32(cfg.distance_scale))
+        self.step = float(cfg.step_size)
+
+    def _blockwise(self, fn, x):
+        """fn applied to x [R,N] separately on each 64-sample block of each ray's window (the mutations that forget a carry)."""
+        out = np.zeros_like(x)
+        for r in range(self.R):
+            for b in range(int(self.first[r]), int(self.first[r] + self.Lw[r]), 64):
+                e = min(b + 64, int(self.first[r] + self.Lw[r]))
+                out[r, b:e] = fn(x[r, b:e])
+        return out
+
+    def median(self, tau, miss):
+        """depth_median(tau) in float64 ([R]) and the index of the crossing sample (-1: the ray's weight stays below tau)."""
+        out = np.full(self.R, float(miss))
+        ks = np.full(self.R, -1)
+        for r in range(self.R):
+            hit = np.nonzero(self.cum[r] >= tau)[0]
+            if hit.size:
+                k = int(hit[0])
+                prev = self.cum[r, k - 1] if k else 0.0
+                if self.mutate == "drop_ccum" and (k - int(self.first[r])) % 64 == 0:
+                    prev = 0.0
+                d = self.dist[r, k] * (self.scale if self.mutate == "scaled_dist_median" else 1.0)
+                out[r] = self.z[r, k] + d * (tau - prev) / self.w[r, k]
+                ks[r] = k
+        return out, ks
+
+    def median_interval(self, tau, miss):
+        """[lo, hi] the device value must lie in, and `either` (rays whose acc is within delta of tau: a median or miss_depth) /
+        `must_miss` (acc < tau - delta: miss_depth exactly)."""
+        lo, _ = self.median(max(tau - self.delta, 1e-300), miss)
+        hi, khi = self.median(tau + self.delta, miss)
+        either = np.abs(self.acc - tau) <= self.delta
+        must_miss = self.acc < tau - self.delta
+        # a ray in `either` that returns a median may stop anywhere up to the end of its last sample that carries weight
+        end = np.where(self.w > 0, self.z + self.dist, -np.inf).max(-1)
+        hi = np.where(khi < 0, end, hi)
+        return lo - 2 * ulp32(lo), hi + 2 * ulp32(hi), either, must_miss
+
+    def check_median(self, got, tau, miss):
+        """Indices of the rays whose device median breaks the issue's rule."""
+        lo, hi, either, must_miss = self.median_interval(tau, miss)
+        got = np.asarray(got, np.float64)
+        is_miss = got == float(np.float32(miss))
+        inside = (got >= lo) & (got <= hi)
+        ok = np.where(must_miss, is_miss, np.where(either, is_miss | inside, inside))
+        return np.nonzero(~ok)[0]
+
+    def check_var(self, got):
+        return np.nonzero(~(np.abs(np.asarray(got, np.float64) - self.var) <= self.var_bound))[0]
+
+    def check_normal(self, got):
+        return np.nonzero(~(np.abs(np.asarray(got, np.float64) - self.normal) <= self.normal_bound[:, None]).all(-1))[0]
+
+    def check_acc_depth(self, acc, depth):
+        bad_a = ~(np.abs(np.asarray(acc, np.float64) - self.acc) <= self.N * T_W)
+        bad_d = ~(np.abs(np.asarray(depth, np.float64) - self.depth) <= T_D)
+        return np.nonzero(bad_a | bad_d)[0]
+
+    def informative(self, tau, miss):
+        """The condition that keeps the bounds from hiding a failure: among the rays with acc >= 0.6, the share whose median interval
+        is narrower than a tenth of the step, whose normal bound is below 1e-2 and whose variance bound is below 10 % of Var + 1e-6.
+        Returns (share, number of such rays)."""
+        sel = self.acc >= 0.6
+        if not sel.any():
+            return 1.0, 0
+        lo, hi, _, _ = self.median_interval(tau, miss)
+        good = ((hi - lo) < self.step / 10) & (self.normal_bound < 1e-2) & (self.var_bound < 0.1 * (self.var + 1e-6))
+        return float(good[sel].mean()), int(sel.sum())
+
+
+def pool_rays(tiny_rays):
+    """The 22 rays of the ray-level cases: twelve of the tiny golden's, then rays that start outside the box, a ray with a zero direction
+    component, rays that miss the box and rays wholly behind the z gate (world z <= 2). Batches of R rays are windows of this pool
+    (`batch`), laid out so that every window holds golden and special rays. The golden rays were picked on the float64 reference alone:
+    the first ten reach acc >= 0.6 on the plain, masked and bf16 field at every N > 1 (so every window holds opaque rays, which the
+    quantiles 0.5 and 0.9 need to return a median at all), the last two stay far below it."""
+    g = np.asarray(tiny_rays, np.float32)[:, :6]
+    pick = g[[1, 19, 35, 49, 64, 80, 96, 112, 129, 144, 0, 108]]
+    special = np.array([
+        [-12.0, 0.5, 3.0, 1.0, 0.02, 0.05],      # starts outside the box (x < -8), crosses it
+        [0.3, -9.0, 4.0, 0.05, 1.0, 0.03],       # starts outside (y < -6)
+        [0.5, 0.25, -9.5, 0.02, 0.01, 1.0],      # starts below the box, ends above the z gate
+        [1.0, -2.0, 2.5, 0.0, 0.6, 0.8],         # a zero direction component
+        [2.0, 1.0, 3.0, 1.0, 0.0, 0.0],          # two zero components, along x above the gate
+        [30.0, 0.0, 0.0, 0.0, 1.0, 0.0],         # misses the box
+        [0.0, 20.0, 30.0, 0.1, 0.2, 1.0],        # misses the box
+        [0.0, 0.0, -1.0, 1.0, 0.1, 0.0],         # wholly behind the z gate (z = -1)
+        [-3.0, 2.0, 1.5, 0.5, -0.5, -0.7],       # starts under the gate and descends
+        [-7.5, -5.5, -6.5, 0.55, 0.45, 0.7],     # corner to corner
+    ], np.float32)
+    order = [0, 1, 12, 2, 3, 17, 4, 5, 6, 13, 7, 19, 10, 8, 14, 9, 18, 15, 20, 16, 21, 11]
+    return np.concatenate([pick, special])[order].copy()
+
+
+# The ray-level field: TINY of tests/conftest.py from synth.make_field_params(RAY_SEED, density_scale=RAY_SCALE). Seed and scale were
+# chosen on the float64 reference alone (tests/test_geometry_cpu.py::test_bounds_are_informative): fields whose rays end on one hard
+# sample have variances near 0, against which the issue's variance bound says nothing.
+RAY_SEED, RAY_SCALE = 23, 1.1
+MASK_GRID = (12, 10, 8)
+MASK_THRES = 0.1               # alphaMask_thres set on the field before updateAlphaMask(MASK_GRID): at make_field's 1e-4 the dilated
+                               # 12 x 10 x 8 mask of this field is all ones; at 0.1 it keeps half the box and drops a quarter of the samples
+KINDS = ("plain", "mask", "bf16")
+# the second point-wise field
+GRID37 = dict(grid=[37, 23, 29], aabb=[[-3.0, -2.0, -2.5], [3.5, 2.5, 2.0]], near_far=[0.5, 8.0])
+
+
+def ray_params(tiny):
+    from text2nerf_amd import synth
+    return synth.make_field_params(RAY_SEED, tiny["grid"], density_scale=RAY_SCALE, aabb=tiny["aabb"])
+
+
+def make_cfg(tiny, volume=None, step_ratio=1.0):
+    """volume: [D(z), H(y), W(x)] occupancy of an AlphaGridMask over the field's own box, or None."""
+    kw = {} if volume is None else dict(alpha_volume=torch.as_tensor(volume, dtype=torch.float32), alpha_aabb=tiny["aabb"])
+    return O.FieldConfig(aabb=tiny["aabb"], grid_size=tiny["grid"], near_far=tiny["near_far"], step_ratio=step_ratio, **kw)
+
+
+def oracle_mask_volume(tiny, params):
+    """updateAlphaMask(MASK_GRID) restated by the oracle (float32, on the CPU)."""
+    cfg = make_cfg(tiny)
+    alpha, xyz = O.dense_alpha(cfg, O.params_from_numpy(params), MASK_GRID)
+    return O.alpha_volume(alpha, xyz, MASK_THRES)[0]
+
+
+def points(grid, seed=5):
+    """257 normalised float32 points inside the box; the first n of them are the case `n` (1, 63, 64, 65, 257). Row 0: the exact upper
+    faces; 1: the exact lower faces; 2-3: mixed faces; 4-23: nodes of the grid (exact cell faces where the float32 coordinate lands on
+    the node, the neighbouring cell's edge where it lands an ulp off); 24-43: an axis-aligned line along x through a node row; the
+    rest: interior points."""
+    rng = np.random.default_rng(seed)
+    p = rng.uniform(-1.0, 1.0, (257, 3)).astype(np.float32)
+    p[0] = 1.0
+    p[1] = -1.0
+    p[2] = (1.0, -1.0, 0.25)
+    p[3] = (-0.5, 1.0, -1.0)
+    for r in range(4, 24):
+        for a in range(3):
+            i = int(rng.integers(0, grid[a]))
+            p[r, a] = np.float32(2.0) * np.float32(i) / np.float32(grid[a] - 1) - np.float32(1.0)
+        if r % 2:
+            p[r, r % 3] = np.float32(rng.uniform(-1, 1))       # a face of two axes only
+    p[24:44, 0] = np.linspace(-1.0, 1.0, 20, dtype=np.float32)
+    p[24:44, 1] = np.float32(2.0) * np.float32(3) / np.float32(grid[1] - 1) - np.float32(1.0)
+    p[24:44, 2] = np.float32(0.3)
+    return p
+
+
+POINT_NS = (1, 63, 64, 65, 257)
+BATCHES = {1: 0, 3: 1, 4: 4, 5: 8, 9: 13}     # R -> first pool row of its window (together: all 22 rows)
+NS = (1, 63, 64, 65, 130)
+TAUS = (0.1, 0.5, 0.9)
+
+
+def batch(pool, R):
+    return pool[BATCHES[R]:BATCHES[R] + R]
+
+
+# ---- windows of more than one 64-sample block -------------------------------------------------------------------------------------------
+# At step_ratio 1 the TINY field's step is 0.76 in a box of 16 x 13 x 13.5, of which the z gate leaves a slab 4.5 high: no ray holds
+# more than some 33 valid samples, and k_geometry's block loop runs once whatever N is. The same factors at FINE_RATIO have a step of
+# 0.076, and a ray that travels inside the slab holds up to 200 valid samples. FINE_NS stand either side of the block edges of a window
+# that begins at sample 0 (Lw = N = 64, 65, 128, 129) and 200 gives windows of three and four blocks. The rays were picked on the
+# float64 reference alone (a search over random rays in the slab) for informative bounds on the plain, masked and bf16 field and for
+# where the quantile is crossed: in the first block (row 7), the second (rows 3-6) and the third (rows 0-2) of the window.
+FINE_RATIO = 0.1
+FINE_NS = (64, 65, 128, 129, 200)
+FINE_BATCHES = {1: 0, 3: 1, 4: 4, 5: 4, 9: 0}
+
+
+def fine_rays():
+    return np.array([
+        [-3.10, 0.00, 2.77, 0.92, -0.39, 0.09],
+        [7.42, -5.64, 2.44, -0.99, 0.14, 0.12],
+        [-7.61, -1.70, 2.24, 0.76, 0.65, 0.07],
+        [8.68, 3.67, 5.13, -0.99, 0.17, -0.11],      # starts outside the box
+        [-7.03, -1.02, 3.00, 0.95, -0.32, -0.03],
+        [6.89, -3.91, 2.97, -1.00, -0.04, 0.13],
+        [-7.37, -2.77, 5.88, 0.83, 0.56, -0.05],
+        [0.89, -2.25, 4.73, 0.16, -0.99, 0.04],      # opaque within the first block
+        [30.0, 0.0, 0.0, 0.0, 1.0, 0.0],             # misses the box
+    ], np.float32)
+
+
+def fine_batch(rays, R):
+    return rays[FINE_BATCHES[R]:FINE_BATCHES[R] + R]

@@ -205,6 +205,32 @@ def render_views(tensorf, poses, intrinsic, H, W, N_samples=-1, white_bg=True, f
     return torch.stack(rgbs), torch.stack(depths)
 
 
+@torch.no_grad()
+def render_geometry_views(tensorf, poses, intrinsic, H, W, N_samples=-1, quantile=0.5, camera_space=True):
+    """Geometry maps of whole views, beside `render_views`: for every camera-to-world pose generate the [H*W,6] rays on the GPU as
+    `render_views` does and run `tensorf.render_geometry` on them, on the caller's stream. Returns a `Geometry` namedtuple of stacked
+    maps: ``acc``, ``depth`` (forward's expected depth), ``depth_median`` (the depth at `quantile` of each ray's weights; near_far[1]
+    where the weight stays below it), ``depth_var`` [V,H,W] and ``normal`` [V,H,W,3] (sum of w n: not normalised, length <= acc).
+    ``camera_space=True`` rotates the normals into each view's camera frame (n_cam = c2w[:3,:3]^T n_world: x right, y down, z
+    forward, so a surface facing the camera has n_z < 0); False leaves them in world space."""
+    from .ray_utils import generate_rays
+    from .tensorf import Geometry
+    dev = tensorf.basis_mat.weight.device
+    maps = [[], [], [], [], []]
+    for c2w in poses:
+        rays = generate_rays(H, W, intrinsic, c2w, device=dev)
+        g = tensorf.render_geometry(rays, N_samples=N_samples, quantile=quantile)
+        nrm = g.normal
+        if camera_space:
+            rot = c2w.detach() if isinstance(c2w, torch.Tensor) else torch.as_tensor(np.asarray(c2w, dtype=np.float32))
+            rot = rot[:3, :3].float().to(dev)
+            nrm = nrm @ rot                    # rows n^T R = (R^T n)^T
+        for lst, t in zip(maps, (g.acc, g.depth, g.depth_median, g.depth_var)):
+            lst.append(t.reshape(H, W))
+        maps[4].append(nrm.reshape(H, W, 3))
+    return Geometry(*[torch.stack(m) for m in maps])
+
+
 
 @torch.no_grad()
 def postprocess_frame(rgb, depth, near_far, push_depth=None, gt_rgb=None):

@@ -10,6 +10,7 @@ a GPU raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -26,6 +27,9 @@ from ._lib import FLAG_ADD_BG, FLAG_COHERENT, FLAG_DEVICE_ROWS, FLAG_KEEP_CTX, F
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
 VEC_MODE = [2, 1, 0]
+
+# what TensorBase.render_geometry returns: device tensors, None for outputs not asked for
+Geometry = collections.namedtuple("Geometry", ("acc", "depth", "depth_median", "depth_var", "normal"))
 
 # train_step seeds the TV terms on a side stream (two more library calls and two stream hand-overs per step) only for batches whose step is
 # GPU-bound; below, the TV pass stays inside the optimiser step
@@ -1091,6 +1095,69 @@ class TensorBase(nn.Module):
         """compute_densityfeature + feature2density fused in the kernel."""
         return self._density_at(xyz_norm, want_sigma=True)
 
+    @torch.no_grad()
+    def density_gradient(self, xyz_world):
+        """The density feature and its analytic WORLD-space gradient at world points [..., 3] (t2n_density_grad_at): returns
+        (feat [n], grad [n,3]). The gradient is exact under the kernels' trilinear arithmetic, in the cell the float32 coordinate falls
+        into; -grad / |grad| is the direction of steepest density decrease (the activation is monotone). Not differentiable."""
+        lib = _lib.load()
+        h = self.sync_params()
+        dev = self.basis_mat.weight.device
+        xyz = self.normalize_coord(xyz_world.detach().reshape(-1, 3).float().to(dev)).contiguous()
+        n = xyz.shape[0]
+        feat = torch.empty(n, device=dev, dtype=torch.float32)
+        grad = torch.empty(n, 3, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.check(lib.t2n_density_grad_at(h, _lib.ptr(xyz), n, _lib.ptr(feat), _lib.ptr(grad), _lib.current_stream_ptr(dev)),
+                       "t2n_density_grad_at")
+        self._note_reader(dev)
+        return feat, grad
+
+    GEOMETRY_OUTPUTS = ("depth", "median", "var", "normal")
+
+    @torch.no_grad()
+    def render_geometry(self, rays, N_samples=-1, quantile=0.5, miss_depth=None, want=GEOMETRY_OUTPUTS, ndc_ray=False):
+        """Geometry of eval rays [R, >= 6] beside the render (t2n_render_geometry; definitions in include/t2n.h): a `Geometry(acc,
+        depth, depth_median, depth_var, normal)` namedtuple of device tensors. `acc` [R] is always returned; `depth` [R] is forward's
+        depth_map, `depth_median` [R] the depth at `quantile` of the ray's weight distribution (`miss_depth`, default near_far[1], for
+        rays whose weight stays below it), `depth_var` [R] = sum w (z - depth)^2, `normal` [R,3] = sum w n in world space, not
+        normalised (length <= acc). Outputs not named in `want` are None. Eval sampling of forward(is_train=False) with early
+        termination ignored; the render path, its caches and its workspace are not involved. There is no CPU path and no NDC form."""
+        lib = _lib.load()
+        unknown = set(want) - set(self.GEOMETRY_OUTPUTS)
+        if unknown:
+            raise T2NError(f"render_geometry: unknown outputs {sorted(unknown)} (known: {self.GEOMETRY_OUTPUTS})")
+        if ndc_ray:
+            raise T2NError("render_geometry: unsupported for NDC rays (a normal or a depth quantile in NDC space means nothing)")
+        if self._is_general():
+            raise T2NError("render_geometry: unsupported for a general-shape field (no native field handle)")
+        if not isinstance(rays, torch.Tensor) or rays.device.type != "cuda":
+            raise T2NError("render_geometry takes rays on the field's GPU (there is no CPU fallback)")
+        h = self.sync_params()
+        dev = self.basis_mat.weight.device
+        if rays.device != dev:
+            raise T2NError(f"render_geometry: rays on {rays.device}, field on {dev}")
+        rays = rays.detach().reshape(-1, rays.shape[-1])
+        if rays.dtype != torch.float32 or not rays.is_contiguous():
+            rays = rays.contiguous().float()
+        R = rays.shape[0]
+        N = int(N_samples) if N_samples > 0 else self.nSamples
+        miss = float(self.near_far[1] if miss_depth is None else miss_depth)
+
+        def out(name, *shape):
+            return torch.empty(*shape, device=dev, dtype=torch.float32) if name is None or name in want else None
+        acc, depth, med, var, nrm = out(None, R), out("depth", R), out("median", R), out("var", R), out("normal", R, 3)
+        if R == 0:
+            if not 0.0 < float(quantile) < 1.0:
+                raise T2NError(f"render_geometry: quantile {quantile} is not inside (0, 1)")
+            return Geometry(acc, depth, med, var, nrm)
+        with torch.cuda.device(dev):
+            _lib.check(lib.t2n_render_geometry(h, _lib.ptr(rays), R, rays.shape[1], N, float(quantile), miss, _lib.ptr(acc), _lib.ptr(depth),
+                                               _lib.ptr(med), _lib.ptr(var), _lib.ptr(nrm), _lib.current_stream_ptr(dev)),
+                       "t2n_render_geometry")
+        self._note_reader(dev)
+        return Geometry(acc, depth, med, var, nrm)
+
     def shade(self, xyz_norm, viewdirs=None, want_features=True, want_rgb=True):
         """compute_appfeature (+ renderModule) at normalised points: returns (app_features [n,app_dim], rgb [n,3])."""
         lib = _lib.load()
@@ -1238,8 +1305,18 @@ class TensorBase(nn.Module):
 
         Colours: shade(normalize_coord(verts), viewdirs=-normals)[1], clamped to [0,1] and rounded to uint8 on the device. The driver's
         fields use MLP_Fea_noview, whose colour does not depend on the direction. A general-shape field has no `shade`: there
-        colors=True raises T2NError and colors=False works. Faces and normals point towards lower alpha: out of the dense region."""
+        colors=True raises T2NError and colors=False works. Faces and normals point towards lower alpha: out of the dense region.
+
+        normals="field": the vertex normals are -grad f / |grad f| of the density feature at the vertices (`density_gradient`: the
+        field's analytic gradient) instead of the sampled volume's finite differences; verts, faces and colours are those of
+        normals=True bit for bit (the colours keep the volume normals as view directions)."""
         from . import mesh as M
+        field_normals = isinstance(normals, str)
+        if field_normals and normals != "field":
+            raise T2NError(f"export_mesh: normals={normals!r} (True, False or 'field')")
+        if field_normals and self._is_general():
+            raise T2NError("export_mesh(normals='field') needs the tuned-shape field's density_gradient; a general-shape field exports "
+                           "with the volume's normals")
         if colors and self._is_general():
             raise T2NError("export_mesh(colors=True) needs the tuned-shape field's shade stage; a general-shape field exports with "
                            "colors=False")
@@ -1255,6 +1332,12 @@ class TensorBase(nn.Module):
                 rgb8 = (rgb.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8)
             else:
                 rgb8 = torch.empty(0, 3, dtype=torch.uint8, device=verts.device)
+        if field_normals:
+            # -grad f / |grad f| at the vertices: the field's own normal instead of finite differences of the sampled volume
+            g = self.density_gradient(verts)[1] if verts.shape[0] else verts.new_empty(0, 3)
+            # (scaled by the largest |component| first, as k_geometry does: the squares of components below 1e-19 underflow)
+            h = g / g.abs().amax(dim=-1, keepdim=True).clamp_min(torch.finfo(torch.float32).tiny)
+            nrm = -h / h.norm(dim=-1, keepdim=True).clamp_min(1.0)
         out = M.Mesh(verts, faces, nrm if normals else None, rgb8)
         if path is not None:
             M.write_ply(path, out.verts, out.faces, out.normals, out.colors)
