@@ -115,38 +115,59 @@ def ulp32(x):
 
 
 class RayRef:
-    """Everything the ray-level checks need, for eval rays [R, >= 6] (float32) at N samples."""
+    """Everything the ray-level checks need, for rays [R, >= 6] (float32) at N samples. The eval form by default; `train`: the
+    reference's is_train geometry (the captured jitter draw [R] added to the sample index, no z gate). The activation is cfg's.
+    `samples`: keep, per sample [R,N] (0 where the sample is not evaluated), the float64 feature f, the sum A of the absolute values of
+    its 48 channel products, sigma, alpha, the transmittance T in front of the sample, and the oracle's float32 normalised position
+    xn [R,N,3] (tests/helpers/march_ref.py)."""
 
-    def __init__(self, cfg, params64, rays, N, mutate=None):
+    def __init__(self, cfg, params64, rays, N, mutate=None, train=False, jitter=None, samples=False):
         rays = torch.as_tensor(np.asarray(rays, np.float32))
         self.N, self.R, self.mutate = int(N), rays.shape[0], mutate
-        pts, z, valid = O.sample_ray(cfg, rays[:, :3], rays[:, 3:6], self.N)
+        jit = torch.as_tensor(np.asarray(jitter, np.float32)).reshape(-1, 1) if train else None
+        pts, z, valid = O.sample_ray(cfg, rays[:, :3], rays[:, 3:6], self.N, jit)
         inbox = valid
         if cfg.alpha_volume is not None and valid.any():      # models/tensorBase.py:451-456
             keep = O.sample_alpha(cfg, pts[valid]) > 0
             valid = valid.clone()
             valid[valid.clone()] = keep
-        valid = valid & (pts[:, :, 2] > cfg.z_gate)
-        box = inbox & (pts[:, :, 2] > cfg.z_gate)          # the kernel's window [first, last]: box test and z gate, not the mask
+        gate = torch.ones_like(valid) if train else pts[:, :, 2] > cfg.z_gate      # models/tensorBase.py:459-460: eval only
+        valid = valid & gate
+        box = inbox & gate                                 # the kernel's window [first, last]: box test and z gate, not the mask
         idx = torch.arange(self.N)[None]
         self.first = torch.where(box, idx, self.N).amin(-1).numpy()
         self.Lw = np.maximum(torch.where(box, idx, -1).amax(-1).numpy() - self.first + 1, 0)
         xn = O.normalize_coord(cfg, pts)
         dist32 = torch.cat([z[:, 1:] - z[:, :-1], torch.zeros_like(z[:, :1])], -1)
+        if mutate == "last_dist":        # the last sample gets the step instead of 0
+            dist32[:, -1] = dist32[:, -2]
         self.z, self.dist, self.valid = z.double().numpy(), dist32.double().numpy(), valid.numpy()
         sigma = torch.zeros(z.shape, dtype=torch.float64)
         nrm = torch.zeros(z.shape + (3,), dtype=torch.float64)
         perr = torch.zeros(z.shape, dtype=torch.float64)      # min(2, gamma |A_i| / |grad f_i|): the unit normal's point-wise bound
         if valid.any():
-            f, g, _, A = density_grad(params64, xn[valid], inv_of(cfg), cfg.grid_size, mutate=mutate)
-            x = f + cfg.density_shift
-            sigma[valid] = torch.where(x > 20, x, torch.log1p(torch.exp(torch.clamp(x, max=20.0))))
+            f, g, Af, A = density_grad(params64, xn[valid], inv_of(cfg), cfg.grid_size, mutate=mutate)
+            if cfg.fea2dense_act == "relu":
+                sigma[valid] = torch.relu(f)
+            else:
+                x = f + cfg.density_shift
+                sigma[valid] = torch.where(x > 20, x, torch.log1p(torch.exp(torch.clamp(x, max=20.0))))
+            if mutate == "sigma_scale":
+                sigma = sigma * (1.0 + 1e-4)
             ln = g.norm(dim=-1)
             tiny = float(np.finfo(np.float32).tiny)
             nrm[valid] = -g / ln.clamp_min(tiny)[:, None]
             perr[valid] = torch.minimum(torch.full_like(ln, 2.0), GAMMA * A.norm(dim=-1) / ln.clamp_min(1e-300))
-        alpha, w, _ = O.raw2alpha(sigma, torch.from_numpy(self.dist) * float(np.float32(cfg.distance_scale)))
+        dscale = 1.0 if mutate == "unscaled_dist" else float(np.float32(cfg.distance_scale))
+        alpha, w, _ = O.raw2alpha(sigma, torch.from_numpy(self.dist) * dscale)
         self.w = w.numpy()
+        if samples:
+            self.f, self.A = np.zeros(z.shape), np.zeros(z.shape)
+            if valid.any():
+                self.f[self.valid], self.A[self.valid] = f.numpy(), Af.numpy()
+            self.sigma, self.alpha, self.xn = sigma.numpy(), alpha.numpy(), xn.numpy()
+            fac = 1.0 - self.alpha + 1e-10
+            self.T = np.concatenate([np.ones((self.R, 1)), np.cumprod(fac, -1)[:, :-1]], -1)
         if mutate == "drop_carry":       # the transmittance starts again at 1 in every 64-sample block of the window
             self.w = self._blockwise(lambda a: a * np.concatenate([[1.0], np.cumprod(1.0 - a + 1e-10)[:-1]]), alpha.numpy())
         self.last = rays[:, -1].double().numpy()

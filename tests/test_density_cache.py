@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from text2nerf_amd import synth, tensorf
+from tests.helpers.march_lists import frame_lists, list_capacity      # noqa: F401 (other test files import them from here)
 from tests.test_hip_parity import dev, make_field
 from tests.test_march_summed_table import pinhole_rays, step_pairs
 
@@ -60,37 +61,6 @@ def alpha_mask(seed=3):
     rng = np.random.Generator(np.random.PCG64(seed))
     vol = (rng.random((7, 6, 5)) > 0.35).astype(np.float32)
     return AlphaGridMask(dev(), torch.tensor(AABB), torch.from_numpy(vol))
-
-
-def list_capacity(R, n_samples):
-    nblocks = (R + 3) // 4
-    return ((nblocks >> 3) + (1 if nblocks & 7 else 0)) * 4 * n_samples + n_samples
-
-
-def frame_lists(R, n_samples):
-    """The per-ray records and the appearance-list entries the last frame left in the stream's workspace (carve_workspace,
-    t2n_api.hip: counters | acc | ray_app | app_pos | app_rgb | app_ray; worst-case lists for frames this small). A ray's slot0 depends
-    on the order in which the waves reserved their regions, so the entries are returned ray by ray, in sample order."""
-    ws = tensorf._WORKSPACE[tensorf._ws_key(dev())]
-    up = lambda v: (v + 255) // 256 * 256
-    cap = list_capacity(R, n_samples) * 8
-    o_acc = up(8 * 64 * 4)
-    o_ray_app = o_acc + up(R * 4)
-    o_pos = o_ray_app + up(R * 16)
-    o_rgb = o_pos + up(cap * 16)
-    o_ray = o_rgb + up(cap * 16)
-    acc = ws[o_acc:o_acc + R * 4].view(torch.float32).clone()
-    ray_app = ws[o_ray_app:o_ray_app + R * 16].view(torch.int32).view(R, 4).clone()
-    pos = ws[o_pos:o_pos + cap * 16].view(torch.float32).view(cap, 4)
-    ray = ws[o_ray:o_ray + cap * 4].view(torch.int32)
-    n = ray_app[:, 1].long()
-    assert int(n.min()) >= 0 and int(ray_app[:, 0].min()) >= 0
-    start = torch.repeat_interleave(ray_app[:, 0].long(), n)
-    first = torch.repeat_interleave(torch.cumsum(n, 0) - n, n)
-    idx = start + (torch.arange(int(n.sum()), device=ws.device) - first)
-    owner = torch.repeat_interleave(torch.arange(R, device=ws.device), n)
-    assert torch.equal(ray[idx].long(), owner)
-    return {"acc": acc, "ray_app": ray_app[:, 1:].clone(), "entries": pos[idx].clone(), "total": int(n.sum())}
 
 
 def render(f, rays, W, cache):

@@ -17,18 +17,12 @@ import torch
 
 from text2nerf_amd import _lib, synth, tensorf
 from tests.conftest import TINY
-from tests.test_density_cache import AABB, NEAR_FAR, camera_rays, frame_lists
+from tests.helpers.march_lists import counters_now, frame_lists, list_shape
+from tests.test_density_cache import AABB, NEAR_FAR, camera_rays
 from tests.test_hip_parity import dev, make_field
 
 GRIDS = {"9x13x17": [9, 13, 17], "16x16x16": [16, 16, 16]}      # tests/test_app_volume_gpu.py's
 N = 32      # samples per ray: 8 x list_cap <= 32 rows per ray + 1024 for both frame sizes, so the worst-case carve holds a row per slot
-
-
-def list_shape(R, n, budget=0):
-    out = (C.c_uint64 * 6)()
-    _lib.check(_lib.load().t2n_render_list_shape(R, n, budget, out), "t2n_render_list_shape")
-    return {"list_cap": int(out[0]), "feat_rows": int(out[1]), "fusable": bool(out[2]), "o_pos": int(out[3]), "o_feat": int(out[4]),
-            "o_counters": int(out[5])}
 
 
 # ---- the host-side sizing rule (no GPU) -------------------------------------------------------------------------------------------
@@ -64,12 +58,6 @@ def new_field(seed, grid, density_scale=0.8):
     f.materialize_weights = False
     f.appearance_volume_min_frames = 1          # the volume exists from the first frame
     return f
-
-
-def counters_now(R, n):
-    ws = tensorf._WORKSPACE[tensorf._ws_key(dev())]
-    o = list_shape(R, n)["o_counters"]
-    return ws[o:o + 8 * 64 * 4].view(torch.int32).clone()
 
 
 def frame(f, rays, W, fused, n=N, lists=True):

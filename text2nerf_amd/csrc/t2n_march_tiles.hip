@@ -426,7 +426,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
     float T = 1.f, acc = 0.f, dep = 0.f;
     int first = -1, last = -1;
     unsigned napp = 0;
-    int nev = 0;         // evaluated samples (the window [first, last] has gaps under an alpha mask)
+    int nev = 0;         // evaluated samples (the window [first, last] is the box window: it has gaps under an alpha mask)
     int ovf_from = 0;    // first sample whose weight went to wbuf instead of the (full) staging slice
 
     // row segments of the transpose flush: lane -> (ray rho = lane / 4 + 16 j, columns 4 (lane & 3) .. + 3), j = 0..3
@@ -474,7 +474,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
             if (have && idx >= lo && idx <= hi && idx <= i_end && !dead) {
                 z[q] = sample_z<false, true>(F, ray, idx, 0.f);
                 ok[q] = sample_point<false>(F, ray, z[q], xn[q], yn[q], zn[q]);
-                if constexpr (ALPHA) { if (ok[q]) ok[q] = alpha_pass(F, ray, z[q]); }      // models/tensorBase.py:451-456
+                if constexpr (ALPHA) {
+                    // the record's window is the box window (box test and z gate), as k_march's: the mask leaves gaps inside it
+                    if (ok[q]) {
+                        if (first < 0) first = idx;
+                        last = idx;
+                        ok[q] = alpha_pass(F, ray, z[q]);      // models/tensorBase.py:451-456
+                    }
+                }
             }
             any_ok |= ok[q];
         }
@@ -582,8 +589,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
                     ++napp;
                     if (napp == (unsigned)a.cap) ovf_from = idx + 1;
                 }
-                if (first < 0) first = idx;
-                last = idx;
+                if constexpr (!ALPHA) {
+                    if (first < 0) first = idx;
+                    last = idx;
+                }
                 ++nev;
                 w_out[q] = w;
             }
