@@ -70,7 +70,8 @@ __global__ __launch_bounds__(256) void k_compute_alpha(const AlphaArgs a) {
 // updateAlphaMask's volume: dense alpha [gx][gy][gz] -> clamp(0,1) -> transposed to [gz][gy][gx] -> 3x3x3 max pool
 // (stride 1, implicit -inf padding) -> 1 where >= thres else 0. The bounding box of the kept voxels is returned as grid
 // indices (min x,y,z / max x,y,z; mins start at INT_MAX, maxs at -1), which the host maps to coordinates through the
-// same lerp as getDenseAlpha (the node coordinates are monotone in the index).
+// same lerp as getDenseAlpha (the node coordinates are monotone in the index). Finite input only: fmaxf / fminf drop a NaN operand (a
+// NaN node counts as 0 here) where torch's clamp and max_pool3d propagate it; nothing is kept means the box comes back as initialised.
 __global__ __launch_bounds__(256) void k_alpha_volume(const float* __restrict__ dense, int gx, int gy, int gz, float thres,
                                                       float* __restrict__ vol, int* __restrict__ bbox) {
     const long long n = (long long)gx * gy * gz;

@@ -919,7 +919,11 @@ class TensorBase(nn.Module):
         queued = False     # device work queued by this call (mask / parameter uploads)
         mask = self.alphaMask
         mkey = None if mask is None else (mask.alpha_volume.data_ptr(), mask.alpha_volume._version, tuple(mask.alpha_volume.shape))
-        if getattr(self, "_alpha_key", "unset") != mkey:
+        # the key alone cannot tell a new volume from the one it replaced: a mask dropped and another of the same shape attached before
+        # the next sync often gets the freed block back (same pointer, version 0). The weak reference dies with the uploaded tensor.
+        held = self.__dict__.get("_alpha_ref")
+        same_tensor = mask is None or (held is not None and held() is mask.alpha_volume)
+        if getattr(self, "_alpha_key", "unset") != mkey or not same_tensor:
             queued = True
             self._wait_readers(dev)
             with torch.cuda.device(dev):
@@ -935,6 +939,7 @@ class TensorBase(nn.Module):
                                                             _lib.current_stream_ptr(dev)), "t2n_field_set_alpha_mask")
                     object.__setattr__(mask, "_field", self)   # plain attribute: a Module attribute would register a cycle
             self._alpha_key = mkey
+            self.__dict__["_alpha_ref"] = None if mask is None else weakref.ref(mask.alpha_volume)
         hr = int(getattr(self, "head_scratch_rows_per_ray", 32))
         if getattr(self, "_head_rows_set", 32) != hr:
             _lib.check(lib.t2n_field_set_head_scratch_rows(self._handle, hr), "t2n_field_set_head_scratch_rows")
@@ -1279,10 +1284,12 @@ class TensorBase(nn.Module):
         with torch.cuda.device(dev):
             _lib.check(lib.t2n_alpha_volume(_lib.ptr(alpha), g[0], g[1], g[2], float(self.alphaMask_thres), _lib.ptr(vol),
                                             _lib.ptr(box), _lib.current_stream_ptr(dev)), "t2n_alpha_volume")
-        self.alphaMask = AlphaGridMask(self.device, self.aabb, vol)
         b = box.cpu().tolist()
         if b[3] < 0:
+            # raised BEFORE the mask is attached: an all-zero mask left on the field would blank every later render and cut every
+            # gradient (the reference attaches it and then fails on the empty amin; a caller that catches the error keeps the old mask)
             raise T2NError("updateAlphaMask: no voxel reaches alphaMask_thres (the reference fails on the empty amin too)")
+        self.alphaMask = AlphaGridMask(self.device, self.aabb, vol)
         lins = [torch.linspace(0, 1, n) for n in g]
         a = self.aabb.detach().float().cpu()
         lo = torch.stack([a[0, k] * (1 - lins[k][b[k]]) + a[1, k] * lins[k][b[k]] for k in range(3)])
