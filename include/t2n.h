@@ -941,6 +941,40 @@ int t2n_mesh_filter_emit(const int32_t* faces, int64_t n_faces, const int32_t* l
                          void* workspace, size_t workspace_bytes, float* verts_out, float* normals_out_or_null,
                          uint8_t* colors_out_or_null, int32_t* faces_out, t2n_stream stream);
 
+/* ---- Floaters in the field: connected components of a dense volume on the device and removal of the unwanted ones, the stage users of
+ * TensoRF-family code run on the host (alpha volume to the CPU, scipy.ndimage.label, a mask built by hand). All integer: every output is
+ * a function of the input alone, two calls give bit-equal arrays. No float atomics, no host read inside the calls.
+ *   volume         [n0][n1][n2] fp32, C order, n2 fastest (t2n_alpha_volume's layout). A voxel is foreground iff volume > level (strict:
+ *                  NaN is background, +inf foreground).
+ *   connectivity   6, 18 or 26: two foreground voxels are neighbours when their indices differ by at most one on every axis and on at
+ *                  most 1, 2 or 3 axes (faces; plus edges; plus corners): scipy's generate_binary_structure(3, 1 | 2 | 3).
+ *   labels         [n0][n1][n2] int32: -1 on background; on foreground dense, 0 .. K-1, numbered in the order of each component's
+ *                  SMALLEST linear voxel index. `labels` is one fixed array for an input, not merely a partition.
+ *   t2n_volume_components        fills labels and K (n_components_out: device int64 [1]). Block-based union-find: a workgroup owns a tile
+ *                  (t2n_volume_components_tile: 4 x 8 x 64, the n2 extent one wave of 256 contiguous bytes), finds the runs along n2
+ *                  with one ballot per row, unites the runs of neighbouring rows in an LDS parent array (atomicMin, larger root under
+ *                  smaller) and writes every voxel's parent as the global linear index of its tile-local root. One thread per voxel on a
+ *                  tile face then unites it with its foreground neighbours in other tiles (also those that share only an edge or a
+ *                  corner) on the global parents, with the find / atomicMin discipline of t2n_mesh_components: parent[x] <= x only ever
+ *                  decreases, so a component's final root is its smallest voxel whatever order the threads ran in. Then flatten,
+ *                  exclusive scan of the root flags (per-256 sums, one workgroup with a running carry), labels = rank of the root.
+ *                  With K = 0 only labels (all -1) and K are written.
+ *   t2n_volume_component_stats   voxel_counts [K] int32 and, unless NULL, boxes [K][6] int32 (min0, min1, min2, max0, max1, max2:
+ *                  inclusive index box); integer atomics, equal labels combined inside a wave first. K = 0 writes nothing.
+ *   t2n_volume_filter            keep [K] uint8: volume_out = keep[label] ? volume : fill on foreground (label in [0, K)), volume_out =
+ *                  volume elsewhere, bits preserved. volume_out may alias volume.
+ * Workspace of t2n_volume_components: t2n_volume_components_workspace_bytes(n0, n1, n2) bytes of device memory (0 = bad argument).
+ * T2N_ERR_INVALID (before any HIP call): NULL required pointer, a dimension < 1, n0 * n1 * n2 >= 2^31, a connectivity other than 6, 18
+ * or 26, a level that is not finite, workspace_bytes smaller than required, n_components outside [0, n0 * n1 * n2]. */
+size_t t2n_volume_components_workspace_bytes(int n0, int n1, int n2);
+int t2n_volume_components_tile(int tile3[3]);
+int t2n_volume_components(const float* volume, int n0, int n1, int n2, float level, int connectivity, int32_t* labels,
+                          int64_t* n_components_out, void* workspace, size_t workspace_bytes, t2n_stream stream);
+int t2n_volume_component_stats(const int32_t* labels, int n0, int n1, int n2, int64_t n_components, int32_t* voxel_counts,
+                               int32_t* boxes_or_null, t2n_stream stream);
+int t2n_volume_filter(const float* volume, const int32_t* labels, int n0, int n1, int n2, const uint8_t* keep, int64_t n_components,
+                      float fill, float* volume_out, t2n_stream stream);
+
 /* ---- One optimisation step of the reference's loop (text2nerf_main.py:547-601) as ONE submission: TV gradient -> train-mode render
  * (KEEP_CTX) -> t2n_train_loss -> t2n_render_backward (device-side row plan, as T2N_FLAG_DEVICE_ROWS) -> Adam on all 19 tensors ->
  * re-packed head operands, on the caller's stream and three library-owned side streams (forked from / joined into `stream` by events, so

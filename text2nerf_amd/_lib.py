@@ -174,6 +174,13 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "t2n_mesh_filter_emit": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2n_volume_components_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "t2n_volume_components_tile": (C.c_int, [C.POINTER(C.c_int)]),
+    "t2n_volume_components": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
+    "t2n_volume_component_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "t2n_volume_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
+                                    C.c_void_p]),
     "t2n_field_grad_buffer_bytes": (C.c_size_t, [C.c_void_p]),
     "t2n_field_set_grad_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "t2n_field_grad_buffer_density_bytes": (C.c_size_t, [C.c_void_p]),

@@ -30,6 +30,9 @@ VEC_MODE = [2, 1, 0]
 
 # what TensorBase.render_geometry returns: device tensors, None for outputs not asked for
 Geometry = collections.namedtuple("Geometry", ("acc", "depth", "depth_median", "depth_var", "normal"))
+# what TensorBase.prune_floaters returns: K, keep [K] bool, voxel_counts [K] int32 (device tensors), the voxels it set to zero (int), and
+# the volume.VolumeComponents of the mask volume
+PruneReport = collections.namedtuple("PruneReport", ("n_components", "keep", "voxel_counts", "removed_voxels", "components"))
 
 # train_step seeds the TV terms on a side stream (two more library calls and two stream hand-overs per step) only for batches whose step is
 # GPU-bound; below, the TV pass stays inside the optimiser step
@@ -1272,18 +1275,25 @@ class TensorBase(nn.Module):
         return alpha, dense_xyz
 
     @torch.no_grad()
-    def updateAlphaMask(self, gridSize=(200, 200, 200)):
-        """models/tensorBase.py:346-370: rebuild the occupancy mask from the current density (3x3x3 dilation, threshold
-        alphaMask_thres) and return the bounding box of the occupied voxels."""
+    def _alpha_mask_volume(self, g):
+        """The occupancy volume of the current density on the grid g = [gx, gy, gz]: getDenseAlpha, then t2n_alpha_volume (3x3x3 dilation,
+        binarised at alphaMask_thres). Returns (volume [gz,gy,gx] float32 of 0 / 1, the index box of its ones as a device int32 [6])."""
         lib = _lib.load()
         dev = self.basis_mat.weight.device
-        g = [int(x) for x in gridSize]
         alpha, _ = self.getDenseAlpha(g)
         vol = torch.empty((g[2], g[1], g[0]), device=dev, dtype=torch.float32)
         box = torch.empty(6, device=dev, dtype=torch.int32)
         with torch.cuda.device(dev):
             _lib.check(lib.t2n_alpha_volume(_lib.ptr(alpha), g[0], g[1], g[2], float(self.alphaMask_thres), _lib.ptr(vol),
                                             _lib.ptr(box), _lib.current_stream_ptr(dev)), "t2n_alpha_volume")
+        return vol, box
+
+    @torch.no_grad()
+    def updateAlphaMask(self, gridSize=(200, 200, 200)):
+        """models/tensorBase.py:346-370: rebuild the occupancy mask from the current density (3x3x3 dilation, threshold
+        alphaMask_thres) and return the bounding box of the occupied voxels."""
+        g = [int(x) for x in gridSize]
+        vol, box = self._alpha_mask_volume(g)
         b = box.cpu().tolist()
         if b[3] < 0:
             # raised BEFORE the mask is attached: an all-zero mask left on the field would blank every later render and cut every
@@ -1298,6 +1308,44 @@ class TensorBase(nn.Module):
         total = int(g[0] * g[1] * g[2])
         print(f"bbox: {lo, hi} alpha rest %%%f" % (float(vol.sum()) / total * 100))
         return new_aabb
+
+    @torch.no_grad()
+    def prune_floaters(self, gridSize=None, min_voxels=0, keep_largest=None, connectivity=26, dry_run=False):
+        """Remove detached blobs ("floaters") from what the field renders, through its occupancy mask. The volume is exactly the one
+        `updateAlphaMask(gridSize)` would attach (getDenseAlpha, then the 3x3x3-dilated binary [gz,gy,gx] volume at alphaMask_thres;
+        default grid: the field's own); its connected components are labelled on the device (`volume.volume_components` at level 0),
+        component c stays iff voxel_counts[c] >= min_voxels and, with keep_largest = k, it is among the k with the most voxels (ties to
+        the lower label), the others are set to 0, and the result is attached as `self.alphaMask` over the field's aabb: the
+        assignment updateAlphaMask makes, without its shrinking. Returns PruneReport(n_components, keep [K] bool, voxel_counts [K],
+        removed_voxels, components). `dry_run=True` returns the report and attaches nothing. T2NError, with the mask left as it was,
+        when no voxel reaches the threshold or the selection keeps no component. Tuned-shape and general-shape fields alike.
+
+        What the mask means for the caller: samples in the removed regions are skipped by render, by `compute_alpha` and hence by
+        `getDenseAlpha` and `export_mesh`; the parameters are untouched, and `tensorf.alphaMask = None` undoes the call. An attached
+        mask already zeroes getDenseAlpha outside itself, so repeated calls only ever remove. With a mask attached `train_step` takes
+        the composed route and eval frames the masked marcher forms (both as with any alphaMask), so the call belongs after training
+        and before the render / warp stages, not between fused steps."""
+        from . import volume as Vm
+        if connectivity not in (6, 18, 26):
+            raise ValueError(f"prune_floaters: connectivity {connectivity!r} (6, 18 or 26)")
+        if int(min_voxels) < 0:
+            raise ValueError(f"prune_floaters: min_voxels {min_voxels} < 0")
+        if keep_largest is not None and int(keep_largest) < 1:
+            raise ValueError(f"prune_floaters: keep_largest {keep_largest} < 1")
+        g = [int(x) for x in (self.gridSize if gridSize is None else gridSize)]
+        vol, _ = self._alpha_mask_volume(g)
+        out, comp, keep = Vm.filter_volume(vol, min_voxels=min_voxels, keep_largest=keep_largest, level=0.0, connectivity=connectivity,
+                                           fill=0.0)
+        if comp.n_components == 0:
+            raise T2NError("prune_floaters: no voxel reaches alphaMask_thres; the mask is left as it was")
+        counts = comp.voxel_counts.to(torch.int64)
+        kept, removed = (int(x) for x in torch.stack(((counts * keep).sum(), (counts * ~keep).sum())).cpu().tolist())
+        if kept == 0:
+            raise T2NError(f"prune_floaters: min_voxels={min_voxels}, keep_largest={keep_largest} keep none of the "
+                           f"{comp.n_components} components; the mask is left as it was")
+        if not dry_run:
+            self.alphaMask = AlphaGridMask(self.device, self.aabb, out)
+        return PruneReport(comp.n_components, keep, comp.voxel_counts, removed, comp)
 
     @torch.no_grad()
     def export_mesh(self, path=None, level=0.005, gridSize=None, colors=True, normals=True):
