@@ -454,6 +454,12 @@ int t2n_generic_backward_staged(const t2n_generic_desc* desc, const t2n_field_pa
  * descriptor are read. Threshold, dilation and bounding box (updateAlphaMask, :346-370) are t2n_alpha_volume's. */
 int t2n_generic_dense_alpha(const t2n_generic_desc* desc, const t2n_field_params* params, const float* lin_x, const float* lin_y,
                             const float* lin_z, int gx, int gy, int gz, float length, float* alpha, t2n_stream stream);
+/* The pre-activation density feature (compute_densityfeature, models/tensoRF.py:205-220) at exactly the nodes of
+ * t2n_generic_dense_alpha, by the same node arithmetic and feature chain: feat [gx][gy][gz], -INFINITY where the descriptor's
+ * alpha_volume (if any) samples <= 0 (outside at every finite level: the counterpart of dense alpha's 0 there). The activation is
+ * monotone, so feat > f* classifies a node as alpha > alpha(f*) does; marching cubes on feat puts its vertices on the level set. */
+int t2n_generic_dense_feature(const t2n_generic_desc* desc, const t2n_field_params* params, const float* lin_x, const float* lin_y,
+                              const float* lin_z, int gx, int gy, int gz, float* feat, t2n_stream stream);
 /* filtering_rays on the general-shape path (models/tensorBase.py:372-404): bbox_only != 0 — the slab test t_max > t_min against
  * aabb_min / aabb_max (:385-391); bbox_only == 0 — any of the ray's first n_samples eval samples (t_min + i * step, no box test) reads
  * the descriptor's alpha_volume > 0 (:393-395; needs a mask). mask[r] = 0 / 1. No parameters are read. */
@@ -813,6 +819,9 @@ int t2n_field_upload_head(t2n_field* f, const t2n_field_params* p, t2n_stream st
  *   where the field's AlphaGridMask (if one is set) samples <= 0.
  * t2n_dense_alpha: models/tensorBase.py:328-344 (getDenseAlpha) — the same at the nodes aabb0*(1-s) + aabb1*s of a dense
  *   grid, s = (lin_x[i], lin_y[j], lin_z[k]) (device arrays holding torch.linspace(0,1,g)); alpha is [gx][gy][gz].
+ * t2n_dense_feature: the pre-activation density feature (compute_densityfeature, models/tensoRF.py:205-220) at exactly those nodes,
+ *   by the same node arithmetic, taps and sum (fp32 or bf16 factor storage alike); feat is [gx][gy][gz], -INFINITY where the
+ *   AlphaGridMask samples <= 0 (outside at every finite level: the counterpart of dense alpha's 0 there).
  * t2n_alpha_volume: models/tensorBase.py:349-363 (updateAlphaMask) — clamp, transpose to [gz][gy][gx], 3x3x3 max pool,
  *   binarise at `thres`; bbox_idx (device int[6]) receives the index box of the kept voxels (min x,y,z, max x,y,z;
  *   INT_MAX / -1 when nothing is kept).
@@ -821,6 +830,8 @@ int t2n_field_upload_head(t2n_field* f, const t2n_field_params* p, t2n_stream st
 int t2n_compute_alpha(const t2n_field* f, const float* xyz_world, int64_t n, float length, float* alpha, t2n_stream stream);
 int t2n_dense_alpha(const t2n_field* f, const float* lin_x, const float* lin_y, const float* lin_z, int gx, int gy, int gz,
                     float length, float* alpha, t2n_stream stream);
+int t2n_dense_feature(const t2n_field* f, const float* lin_x, const float* lin_y, const float* lin_z, int gx, int gy, int gz,
+                      float* feat, t2n_stream stream);
 int t2n_alpha_volume(const float* dense_alpha, int gx, int gy, int gz, float thres, float* volume, int* bbox_idx,
                      t2n_stream stream);
 int t2n_upsample_bilinear(const float* src, int C, int Hin, int Win, float* dst, int Hout, int Wout, t2n_stream stream);
@@ -940,6 +951,40 @@ int t2n_mesh_filter_emit(const int32_t* faces, int64_t n_faces, const int32_t* l
                          int64_t n_components, const float* verts, const float* normals_or_null, const uint8_t* colors_or_null,
                          void* workspace, size_t workspace_bytes, float* verts_out, float* normals_out_or_null,
                          uint8_t* colors_out_or_null, int32_t* faces_out, t2n_stream stream);
+
+/* ---- Mesh export: Taubin (lambda | mu) smoothing and vertex normals on the device, the stage users of TensoRF-family exports run
+ * afterwards in MeshLab. Every output is a function of the face SET and the positions alone (not of face order, corner order or thread
+ * order): no float atomics, two calls give bit-equal arrays. faces [F][3] int32 into n_verts vertices, 6 * n_faces < 2^31.
+ *   rows           Both row structures are CSR arrays (offsets [V+1] int64, values [E] int32) built from 64-bit keys row << 32 | value:
+ *                  t2n_mesh_edge_keys writes keys [6 F] (face (a,b,c): a->b, b->a, b->c, c->b, c->a, a->c; an edge whose ends are the
+ *                  same index, and every edge of a face with an index outside [0, n_verts), is INT64_MAX), t2n_mesh_face_keys keys [3 F]
+ *                  ((vertex, face index) per corner). The caller sorts the keys ascending (any 64-bit sort), and t2n_mesh_csr keeps each
+ *                  key that differs from its predecessor and whose row is inside [0, n_rows): values [count] int32 = the keys' low
+ *                  words in sorted order (room for n_keys), offsets[v] = the number of kept keys below v << 32, count_out (device int64
+ *                  [1]) = offsets[n_rows]. So every row is ascending and unique: N(v) of the adjacency is the set of u != v sharing
+ *                  a face edge with v, duplicate faces add nothing, and a vertex twice in a face owns that face once.
+ *                  Workspace: t2n_mesh_csr_workspace_bytes(n_keys) bytes of device memory (0 = bad argument).
+ *   t2n_mesh_smooth_pass   pos_out[v] = x_v + s * (mean_{u in N(v)} x_u - x_v) on float64 positions [V][3], one thread per vertex: the
+ *                  sum starts at 0.0 and runs over the row in its ascending order, then / (double)degree, - x_v, * s, + x_v, every
+ *                  operation rounded on its own (no contraction). A vertex with an empty row, or with fixed_or_null[v] != 0, keeps its
+ *                  position. One Taubin iteration = a pass with s = lambda, then one with s = mu < 0, between two buffers of the
+ *                  caller (pos_out must not be pos_in). n_entries = the length of `neighbours`; rows are clipped to it and a neighbour
+ *                  outside [0, n_verts) is skipped, so no memory is touched through a bad array.
+ *   t2n_mesh_vertex_normals   n_v = sum over the faces of row v (vf_offsets / vf_faces: the CSR of t2n_mesh_face_keys), in ascending
+ *                  face index, of (x_b - x_a) x (x_c - x_a), in float64 from the fp32 positions; h = n / max |component|; normals[v] =
+ *                  (float)(h / sqrt(h0 h0 + h1 h1 + h2 h2)): right-hand orientation, which is marching cubes' (out of the dense
+ *                  region). Exactly 0 for a vertex of no face, of degenerate faces only, or with a sum that is not finite.
+ * T2N_ERR_INVALID (before any HIP call): NULL required pointer, a negative count, n_verts / n_rows / n_keys >= 2^31, 6 * n_faces >=
+ * 2^31, workspace_bytes smaller than required, pos_out == pos_in, s not finite. Empty inputs launch nothing they do not need. */
+size_t t2n_mesh_csr_workspace_bytes(int64_t n_keys);
+int t2n_mesh_edge_keys(const int32_t* faces, int64_t n_faces, int64_t n_verts, int64_t* keys, t2n_stream stream);
+int t2n_mesh_face_keys(const int32_t* faces, int64_t n_faces, int64_t n_verts, int64_t* keys, t2n_stream stream);
+int t2n_mesh_csr(const int64_t* sorted_keys, int64_t n_keys, int64_t n_rows, int64_t* offsets, int32_t* values, int64_t* count_out,
+                 void* workspace, size_t workspace_bytes, t2n_stream stream);
+int t2n_mesh_smooth_pass(const double* pos_in, double* pos_out, const int64_t* offsets, const int32_t* neighbours, int64_t n_entries,
+                         const uint8_t* fixed_or_null, int64_t n_verts, double s, t2n_stream stream);
+int t2n_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t n_faces, const int64_t* vf_offsets, const int32_t* vf_faces,
+                            int64_t n_entries, int64_t n_verts, float* normals, t2n_stream stream);
 
 /* ---- Floaters in the field: connected components of a dense volume on the device and removal of the unwanted ones, the stage users of
  * TensoRF-family code run on the host (alpha volume to the CPU, scipy.ndimage.label, a mask built by hand). All integer: every output is

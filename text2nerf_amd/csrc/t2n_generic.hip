@@ -842,7 +842,9 @@ size_t gen_head_lds(const t2n_generic_desc* d, bool rows_only) {
 
 // getDenseAlpha on the reference layouts (models/tensorBase.py:328-344 -> compute_alpha :412-434): one thread per node
 // (i, j, k) = aabb0 * (1 - s) + aabb1 * s, s = (lin_x[i], lin_y[j], lin_z[k]) — the node arithmetic of k_compute_alpha —, sigma = 0 where
-// the field's mask (if any) samples <= 0, alpha = 1 - exp(-sigma * length); output index ((i * gy) + j) * gz + k
+// the field's mask (if any) samples <= 0, alpha = 1 - exp(-sigma * length); output index ((i * gy) + j) * gz + k. kFeature: the
+// pre-activation density feature of the same chain goes out instead (t2n_generic_dense_feature), -inf where the mask samples <= 0
+template <bool kFeature>
 __global__ __launch_bounds__(256) void k_gen_dense_alpha(const GenArgs a, const float* __restrict__ lin_x, const float* __restrict__ lin_y,
                                                          const float* __restrict__ lin_z, int gy, int gz, long long n, float length,
                                                          float* __restrict__ alpha) {
@@ -855,12 +857,13 @@ __global__ __launch_bounds__(256) void k_gen_dense_alpha(const GenArgs a, const 
     const float px = F.aabb0[0] * (1.f - sx) + F.aabb1[0] * sx;
     const float py = F.aabb0[1] * (1.f - sy) + F.aabb1[1] * sy;
     const float pz = F.aabb0[2] * (1.f - sz) + F.aabb1[2] * sz;
-    float sg = 0.f;
+    float sg = 0.f, feat = -INFINITY;
     if (!F.alpha || alpha_value(F, px, py, pz) > 0.f) {
         const float xn = (px - F.aabb0[0]) * F.inv[0] - 1.f, yn = (py - F.aabb0[1]) * F.inv[1] - 1.f, zn = (pz - F.aabb0[2]) * F.inv[2] - 1.f;
-        sg = feature2density(F, gen_density_feature(a, gen_taps(a, xn, yn, zn)));
+        feat = gen_density_feature(a, gen_taps(a, xn, yn, zn));
+        if (!kFeature) sg = feature2density(F, feat);
     }
-    alpha[p] = 1.f - expf((-sg) * length);
+    alpha[p] = kFeature ? feat : 1.f - expf((-sg) * length);
 }
 
 // the forward takes its kernel form when the head's LDS fits and T2N_GENERIC_PLAIN is not set (and the workspace has room, which the
@@ -1046,8 +1049,21 @@ extern "C" int t2n_generic_dense_alpha(const t2n_generic_desc* desc, const t2n_f
     if (rc) return rc;
     if (!lin_x || !lin_y || !lin_z || !alpha || gx < 1 || gy < 1 || gz < 1) { set_error("t2n_generic_dense_alpha: bad argument"); return T2N_ERR_INVALID; }
     const long long n = (long long)gx * gy * gz;
-    hipLaunchKernelGGL(k_gen_dense_alpha, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, lin_x, lin_y, lin_z, gy, gz,
+    hipLaunchKernelGGL(k_gen_dense_alpha<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, lin_x, lin_y, lin_z, gy, gz,
                        n, length, alpha);
+    T2N_HIP(hipGetLastError());
+    return T2N_OK;
+}
+
+extern "C" int t2n_generic_dense_feature(const t2n_generic_desc* desc, const t2n_field_params* params, const float* lin_x, const float* lin_y,
+                                         const float* lin_z, int gx, int gy, int gz, float* feat, t2n_stream stream) {
+    GenArgs a;
+    int rc = gen_fill(a, desc, params, "t2n_generic_dense_feature");
+    if (rc) return rc;
+    if (!lin_x || !lin_y || !lin_z || !feat || gx < 1 || gy < 1 || gz < 1) { set_error("t2n_generic_dense_feature: bad argument"); return T2N_ERR_INVALID; }
+    const long long n = (long long)gx * gy * gz;
+    hipLaunchKernelGGL(k_gen_dense_alpha<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, lin_x, lin_y, lin_z, gy, gz,
+                       n, 0.f, feat);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
 }

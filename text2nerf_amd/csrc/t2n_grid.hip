@@ -21,6 +21,9 @@ struct AlphaArgs {
     float* alpha;
 };
 
+// kFeature: the pre-activation density feature itself goes out (t2n_dense_feature), -inf where the mask samples <= 0: the same nodes, taps
+// and sum, without the activation and the exponential.
+template <bool kFeature>
 __global__ __launch_bounds__(256) void k_compute_alpha(const AlphaArgs a) {
     constexpr int LPS = 4;
     const FieldDev& F = a.F;
@@ -62,8 +65,12 @@ __global__ __launch_bounds__(256) void k_compute_alpha(const AlphaArgs a) {
     }
     const float feat = group_sum<LPS>(part);
     if (inb && q == 0) {
-        const float sg = ok ? feature2density(F, feat) : 0.f;
-        a.alpha[p] = 1.f - expf((-sg) * a.length);
+        if (kFeature) {
+            a.alpha[p] = ok ? feat : -INFINITY;
+        } else {
+            const float sg = ok ? feature2density(F, feat) : 0.f;
+            a.alpha[p] = 1.f - expf((-sg) * a.length);
+        }
     }
 }
 
@@ -162,9 +169,11 @@ int t2n::launch_filter_alpha(const FieldDev& F, const float* rays, long long n_r
     return T2N_OK;
 }
 
-static int launch_alpha(const t2n_field* f, const AlphaArgs& a, hipStream_t s) {
+static int launch_alpha(const t2n_field* f, const AlphaArgs& a, hipStream_t s, bool feature = false) {
     const long long threads = a.n * 4;
-    hipLaunchKernelGGL(k_compute_alpha, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (feature) hipLaunchKernelGGL(k_compute_alpha<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_compute_alpha<false>, grid, dim3(256), 0, s, a);
     T2N_HIP(hipGetLastError());
     return T2N_OK;
 }
@@ -189,6 +198,17 @@ extern "C" int t2n_dense_alpha(const t2n_field* f, const float* lin_x, const flo
     a.F = f->dev; a.lin_x = lin_x; a.lin_y = lin_y; a.lin_z = lin_z; a.gy = gy; a.gz = gz;
     a.n = (long long)gx * gy * gz; a.length = length; a.alpha = alpha;
     return launch_alpha(f, a, (hipStream_t)stream);
+}
+
+extern "C" int t2n_dense_feature(const t2n_field* f, const float* lin_x, const float* lin_y, const float* lin_z, int gx, int gy,
+                                 int gz, float* feat, t2n_stream stream) {
+    if (!f || !lin_x || !lin_y || !lin_z || !feat || gx < 1 || gy < 1 || gz < 1) { set_error("t2n_dense_feature: bad argument"); return T2N_ERR_INVALID; }
+    if (!f->uploaded) { set_error("t2n_dense_feature: field has no uploaded parameters"); return T2N_ERR_STATE; }
+    AlphaArgs a;
+    memset(&a, 0, sizeof(a));
+    a.F = f->dev; a.lin_x = lin_x; a.lin_y = lin_y; a.lin_z = lin_z; a.gy = gy; a.gz = gz;
+    a.n = (long long)gx * gy * gz; a.alpha = feat;
+    return launch_alpha(f, a, (hipStream_t)stream, true);
 }
 
 extern "C" int t2n_alpha_volume(const float* dense_alpha, int gx, int gy, int gz, float thres, float* volume, int* bbox_idx,

@@ -8,6 +8,9 @@ writer, in the place of `skimage.measure.marching_cubes` on a host copy followed
     Mesh                         what `TensorBase.export_mesh` returns: verts, faces, normals, colors
     mesh_components              faces, n_verts -> Components(labels, n_components, vert_counts, face_counts)
     filter_components            a Mesh without its unwanted components ("floaters"): min_faces and / or keep_largest
+    mesh_adjacency               faces, n_verts -> Adjacency(offsets, neighbours): sorted unique CSR rows (csrc/t2n_mesh_smooth.hip)
+    smooth_mesh                  Taubin lambda | mu smoothing in float64 over those rows, normals recomputed
+    vertex_normals               area-weighted normals of a mesh's faces, float64 sums in ascending face order
 
 The meshes are closed oriented 2-manifolds (the case table is generated from rules, tools/gen_mc_table.py); the right-hand normal of
 every triangle, and every vertex normal, points towards LOWER values: out of the dense region of an alpha volume. Vertex and face order
@@ -17,6 +20,7 @@ A Text2NeRF alpha volume at the export level holds the scene's surface plus deta
 
     m = tensorf.export_mesh(None)                 # colours and normals as before
     m = filter_components(m, keep_largest=1)      # or min_faces=...
+    m = smooth_mesh(m, iterations=10)             # optional: Taubin smoothing, after the floaters have left
     write_ply("scene.ply", *m)
 
 Components are all-integer (lock-free union-find whose roots are each component's smallest vertex, integer counts, scans): labels,
@@ -45,6 +49,11 @@ class Components(NamedTuple):
     n_components: int                   # K
     vert_counts: torch.Tensor           # [K] int32
     face_counts: torch.Tensor           # [K] int32
+
+
+class Adjacency(NamedTuple):
+    offsets: torch.Tensor               # [V+1] int64: row v is neighbours[offsets[v] : offsets[v+1]]
+    neighbours: torch.Tensor            # [E] int32, every row sorted ascending and unique
 
 
 def _device():
@@ -166,12 +175,12 @@ def mesh_components(faces, n_verts):
     return Components(c.labels.cpu().numpy(), c.n_components, c.vert_counts.cpu().numpy(), c.face_counts.cpu().numpy())
 
 
-def _rows(x, V, dtype, dev, what):
+def _rows(x, V, dtype, dev, what, who="filter_components"):
     if x is None:
         return None
     t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
     if tuple(t.shape) != (V, 3):
-        raise ValueError(f"filter_components: {what} of shape {tuple(t.shape)} for {V} vertices, need [V,3]")
+        raise ValueError(f"{who}: {what} of shape {tuple(t.shape)} for {V} vertices, need [V,3]")
     return t.detach().to(device=dev, dtype=dtype).contiguous()
 
 
@@ -243,6 +252,169 @@ def filter_components(mesh, min_faces=0, keep_largest=None, components=None):
         return Mesh(out_v, out_f, out_n, out_c)
     host = lambda x: None if x is None else x.cpu().numpy()
     return Mesh(host(out_v), host(out_f), host(out_n), host(out_c))
+
+
+# ---- adjacency, Taubin smoothing, vertex normals -----------------------------------------------------------------------------------------
+def _csr(lib, f, V, dev, edges):
+    """The sorted, unique rows of checked device faces as (offsets [V+1] int64, values [E] int32): vertex -> neighbouring vertices
+    (edges) or vertex -> faces. Keys row << 32 | value from one launch, a device sort, t2n_mesh_csr; the 8 bytes of E are read."""
+    F = int(f.shape[0])
+    n = (6 if edges else 3) * F
+    if n == 0:                                                  # nothing is launched
+        return torch.zeros(V + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream_ptr(dev)
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        name = "t2n_mesh_edge_keys" if edges else "t2n_mesh_face_keys"
+        _lib.check(getattr(lib, name)(_lib.ptr(f), F, V, _lib.ptr(keys), stream), name)
+        keys = torch.sort(keys).values                          # integer keys: the sorted array does not depend on how it was sorted
+        nbytes = int(lib.t2n_mesh_csr_workspace_bytes(n))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(V + 1, dtype=torch.int64, device=dev)
+        values = torch.empty(n, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.t2n_mesh_csr(_lib.ptr(keys), n, V, _lib.ptr(offsets), _lib.ptr(values), _lib.ptr(count), _lib.ptr(ws), nbytes,
+                                    stream), "t2n_mesh_csr")
+        E = int(count.cpu().item())                             # the one 8-byte read
+        return offsets, values[:E].clone()
+
+
+def _smooth_faces(faces, V, who):
+    f, dev = _faces_on_device(faces, V, who)
+    if 6 * int(f.shape[0]) >= 2**31:
+        raise ValueError(f"{who}: {f.shape[0]} faces (need 6 F < 2^31)")
+    return f, dev
+
+
+@torch.no_grad()
+def mesh_adjacency(faces, n_verts):
+    """Vertex adjacency of a triangle list as CSR: Adjacency(offsets [V+1] int64, neighbours [E] int32); row v = neighbours[offsets[v]
+    : offsets[v+1]] = N(v), the u != v that share a face edge with v (both directions of {a,b}, {b,c}, {c,a}; an edge whose two ends
+    are the same index is ignored; duplicate faces add nothing). Every row is sorted ascending and unique, so the arrays are a function
+    of the face SET alone: face order, the rotation of a face's indices and thread order do not matter, two calls give the same bits.
+    faces [F,3] integer: a device tensor (device tensors come back) or a numpy array / CPU tensor (numpy arrays come back, through the
+    device). Host reads: the index check's min / max and the 8 bytes of E. ValueError: faces that are not [F,3] integer, an index
+    outside [0, n_verts), 6 F >= 2^31. T2NError without a GPU."""
+    lib = _lib.load()
+    f, dev = _smooth_faces(faces, n_verts, "mesh_adjacency")
+    off, nbr = _csr(lib, f, int(n_verts), dev, True)
+    if _is_device(faces):
+        return Adjacency(off, nbr)
+    return Adjacency(off.cpu().numpy(), nbr.cpu().numpy())
+
+
+def _vertex_normals(lib, v, f, dev):
+    V, F = int(v.shape[0]), int(f.shape[0])
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    if V == 0:                                                  # nothing is launched
+        return out
+    off, rows = _csr(lib, f, V, dev, False)
+    with torch.cuda.device(dev):
+        _lib.check(lib.t2n_mesh_vertex_normals(_lib.ptr(v), _lib.ptr(f), F, _lib.ptr(off), _lib.ptr(rows), int(rows.shape[0]), V,
+                                               _lib.ptr(out), _lib.current_stream_ptr(dev)), "t2n_mesh_vertex_normals")
+    return out
+
+
+@torch.no_grad()
+def vertex_normals(verts, faces):
+    """Area-weighted vertex normals [V,3] float32: n_v = sum of (x_b - x_a) x (x_c - x_a) over the faces (a, b, c) that contain v, each
+    face once, in ascending face index (a sorted vertex -> face CSR, built like the adjacency), in float64 from the float32 positions;
+    normalised as export_mesh(normals="field") normalises (prescale by the largest |component|, then divide by the norm) and rounded
+    to float32 once. Exactly 0 for a vertex of no face or of degenerate faces only. Right-hand orientation: `marching_cubes`' (out of
+    the dense region). A function of the positions and the face list with its order; two calls give the same bits. Device tensors in,
+    a device tensor out; numpy arrays / CPU tensors in, a numpy array out. ValueError as `mesh_adjacency`, and for verts that are not
+    [V,3]. T2NError without a GPU."""
+    lib = _lib.load()
+    if len(verts.shape) != 2 or verts.shape[1] != 3:
+        raise ValueError(f"vertex_normals: verts of shape {tuple(verts.shape)}, need [V,3]")
+    V = int(verts.shape[0])
+    f, dev = _smooth_faces(faces, V, "vertex_normals")
+    out = _vertex_normals(lib, _rows(verts, V, torch.float32, dev, "verts", "vertex_normals"), f, dev)
+    return out if _is_device(verts) else out.cpu().numpy()
+
+
+def _checked_adjacency(adjacency, V, dev):
+    """A caller's Adjacency on the device, refused (ValueError) unless its rows can be walked: one host read of five integers."""
+    as_t = lambda x, dt: (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).detach().to(   # noqa: E731
+        device=dev, dtype=dt).contiguous()
+    if len(tuple(adjacency)) != 2:
+        raise ValueError("smooth_mesh: adjacency is not an Adjacency(offsets, neighbours)")
+    off, nbr = as_t(adjacency[0], torch.int64), as_t(adjacency[1], torch.int32)
+    if tuple(off.shape) != (V + 1,) or nbr.dim() != 1:
+        raise ValueError(f"smooth_mesh: adjacency of {tuple(off.shape)} offsets and {tuple(nbr.shape)} neighbours does not belong to a "
+                         f"mesh of {V} vertices")
+    E = int(nbr.shape[0])
+    step = (off[1:] - off[:-1]).amin() if V else off.new_zeros(())
+    lo, hi = torch.aminmax(nbr) if E else (nbr.new_zeros(()), nbr.new_zeros(()))
+    first, last, step, lo, hi = (int(x) for x in torch.stack([off[0], off[-1], step, lo.long(), hi.long()]).cpu().tolist())
+    if first != 0 or last != E or step < 0 or lo < 0 or (E and hi >= V):
+        raise ValueError(f"smooth_mesh: adjacency offsets run from {first} to {last} (smallest step {step}) over {E} neighbours that "
+                         f"span [{lo}, {hi}]: not the rows of a mesh of {V} vertices")
+    return off, nbr
+
+
+@torch.no_grad()
+def smooth_mesh(mesh, iterations=10, lamb=0.5, mu=-0.53, fixed=None, adjacency=None):
+    """Taubin (lambda | mu) smoothing of `mesh` (a Mesh, or (verts, faces[, normals[, colors]])), as a Mesh. One iteration is a pass with
+    s = lamb followed by a pass with s = mu; the mu pass is skipped when mu == 0 (plain Laplacian smoothing, which shrinks). A pass is
+    x_v <- x_v + s * (mean_{u in N(v)} x_u - x_v) over `mesh_adjacency`'s rows, in float64: the sum starts at 0.0 and runs over the row
+    in its ascending order, is divided by the degree, then the subtraction, the product with s, the addition, each rounded on its own.
+    A vertex without neighbours, or with fixed[v] set (`fixed`: an optional [V] bool), keeps its position. Positions stay float64
+    between the passes and are rounded to float32 once at the end, so the result is a function of the positions and the face set:
+    face order, index rotation and thread order do not matter, two calls give the same bits.
+
+    Faces and colours pass through untouched. If the mesh has normals, the output's are `vertex_normals` of the smoothed mesh.
+    iterations=0 returns the input's bits, normals included. `adjacency`: an earlier mesh_adjacency(faces, V) of the same faces, to
+    skip building it. With floater removal the order is `filter_components` first, then `smooth_mesh`. Device tensors in, device
+    tensors out; numpy arrays / CPU tensors in, numpy arrays out. ValueError (before any launch): iterations < 0, lamb outside (0, 1],
+    mu > 0, faces that are not [F,3] integer or hold an index outside [0, V), rows or a `fixed` that do not match verts, an adjacency
+    that is not the rows of V vertices. T2NError without a GPU."""
+    parts = tuple(mesh)
+    if not 2 <= len(parts) <= 4:
+        raise ValueError(f"smooth_mesh: a mesh of {len(parts)} parts, need (verts, faces[, normals[, colors]])")
+    verts, faces, normals, colors = parts + (None,) * (4 - len(parts))
+    if int(iterations) != iterations or int(iterations) < 0:
+        raise ValueError(f"smooth_mesh: iterations {iterations!r} (an integer >= 0)")
+    lamb, mu = float(lamb), float(mu)
+    if not 0.0 < lamb <= 1.0:
+        raise ValueError(f"smooth_mesh: lamb {lamb} outside (0, 1]")
+    if not (mu <= 0.0 and math.isfinite(mu)):
+        raise ValueError(f"smooth_mesh: mu {mu} (finite and <= 0; 0 skips the pass)")
+    if len(verts.shape) != 2 or verts.shape[1] != 3:
+        raise ValueError(f"smooth_mesh: verts of shape {tuple(verts.shape)}, need [V,3]")
+    V = int(verts.shape[0])
+    if fixed is not None and tuple(fixed.shape) != (V,):
+        raise ValueError(f"smooth_mesh: fixed of shape {tuple(fixed.shape)} for {V} vertices, need [V]")
+    lib = _lib.load()
+    f, dev = _smooth_faces(faces, V, "smooth_mesh")
+    v = _rows(verts, V, torch.float32, dev, "verts", "smooth_mesh")
+    n = _rows(normals, V, torch.float32, dev, "normals", "smooth_mesh")
+    c = _rows(colors, V, torch.uint8, dev, "colors", "smooth_mesh")
+    fx = None
+    if fixed is not None:
+        fx = (fixed if isinstance(fixed, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(fixed))).detach().to(dev)
+        fx = (fx != 0).to(torch.uint8).contiguous()
+    adj = None if adjacency is None else _checked_adjacency(adjacency, V, dev)
+    if int(iterations) > 0 and V > 0:
+        off, nbr = adj if adj is not None else _csr(lib, f, V, dev, True)
+        with torch.cuda.device(dev):
+            stream = _lib.current_stream_ptr(dev)
+            x = v.to(torch.float64)
+            y = torch.empty_like(x)
+            for _ in range(int(iterations)):
+                for s in (lamb, mu):
+                    if s == 0.0:
+                        continue
+                    _lib.check(lib.t2n_mesh_smooth_pass(_lib.ptr(x), _lib.ptr(y), _lib.ptr(off), _lib.ptr(nbr), int(nbr.shape[0]),
+                                                        _lib.ptr(fx), V, s, stream), "t2n_mesh_smooth_pass")
+                    x, y = y, x
+            v = x.to(torch.float32)                             # the one rounding
+        if n is not None:
+            n = _vertex_normals(lib, v, f, dev)
+    if _is_device(verts):
+        return Mesh(v, f, n, c)
+    host = lambda x: None if x is None else x.cpu().numpy()     # noqa: E731
+    return Mesh(host(v), host(f), host(n), host(c))
 
 
 def _host(x, dtype):

@@ -1248,31 +1248,68 @@ class TensorBase(nn.Module):
         return out.view(xyz_locs.shape[:-1])
 
     @torch.no_grad()
-    def getDenseAlpha(self, gridSize=None):
-        """models/tensorBase.py:328-344: alpha at the nodes of a dense grid over the aabb, one step long; returns
-        (alpha [gx,gy,gz], dense_xyz [gx,gy,gz,3]). Node positions are generated inside the kernel from the same
-        torch.linspace(0, 1, g) values the reference lerps with."""
+    def _dense_volume(self, gridSize, feature):
+        """getDenseAlpha's launch (feature=False) or the pre-activation density feature at the same nodes (feature=True)."""
         lib = _lib.load()
         general = self._is_general()
         h = None if general else self.sync_params()
         dev = self.basis_mat.weight.device
         g = [int(x) for x in (self.gridSize if gridSize is None else gridSize)]
         lins = [torch.linspace(0, 1, n).to(dev) for n in g]
-        alpha = torch.empty(g, device=dev, dtype=torch.float32)
+        out = torch.empty(g, device=dev, dtype=torch.float32)
+        pl = [_lib.ptr(l) for l in lins]
         with torch.cuda.device(dev):
+            stream = _lib.current_stream_ptr(dev)
             if general:      # wide fields: the density factors in their reference layouts, the mask from the descriptor
                 d = self._general_desc()
                 st = self._param_struct([p.detach() for p in self._real_params()])
-                _lib.check(lib.t2n_generic_dense_alpha(C.byref(d), C.byref(st), _lib.ptr(lins[0]), _lib.ptr(lins[1]), _lib.ptr(lins[2]),
-                                                       g[0], g[1], g[2], float(self.stepSize), _lib.ptr(alpha),
-                                                       _lib.current_stream_ptr(dev)), "t2n_generic_dense_alpha")
+                if feature:
+                    _lib.check(lib.t2n_generic_dense_feature(C.byref(d), C.byref(st), pl[0], pl[1], pl[2], g[0], g[1], g[2], _lib.ptr(out),
+                                                             stream), "t2n_generic_dense_feature")
+                else:
+                    _lib.check(lib.t2n_generic_dense_alpha(C.byref(d), C.byref(st), pl[0], pl[1], pl[2], g[0], g[1], g[2],
+                                                           float(self.stepSize), _lib.ptr(out), stream), "t2n_generic_dense_alpha")
+            elif feature:
+                _lib.check(lib.t2n_dense_feature(h, pl[0], pl[1], pl[2], g[0], g[1], g[2], _lib.ptr(out), stream), "t2n_dense_feature")
             else:
-                _lib.check(lib.t2n_dense_alpha(h, _lib.ptr(lins[0]), _lib.ptr(lins[1]), _lib.ptr(lins[2]), g[0], g[1], g[2],
-                                               float(self.stepSize), _lib.ptr(alpha), _lib.current_stream_ptr(dev)),
+                _lib.check(lib.t2n_dense_alpha(h, pl[0], pl[1], pl[2], g[0], g[1], g[2], float(self.stepSize), _lib.ptr(out), stream),
                            "t2n_dense_alpha")
         samples = torch.stack(torch.meshgrid(*lins, indexing="ij"), -1)
         dense_xyz = self.aabb[0] * (1 - samples) + self.aabb[1] * samples
-        return alpha, dense_xyz
+        return out, dense_xyz
+
+    @torch.no_grad()
+    def getDenseAlpha(self, gridSize=None):
+        """models/tensorBase.py:328-344: alpha at the nodes of a dense grid over the aabb, one step long; returns
+        (alpha [gx,gy,gz], dense_xyz [gx,gy,gz,3]). Node positions are generated inside the kernel from the same
+        torch.linspace(0, 1, g) values the reference lerps with."""
+        return self._dense_volume(gridSize, False)
+
+    @torch.no_grad()
+    def getDenseFeature(self, gridSize=None):
+        """The pre-activation density feature (compute_densityfeature, models/tensoRF.py:205-220) at exactly getDenseAlpha's nodes, by
+        the same node arithmetic and feature chain: returns (feat [gx,gy,gz], dense_xyz [gx,gy,gz,3]). A node where an attached
+        AlphaGridMask samples <= 0 holds -inf: outside at every finite level, the counterpart of getDenseAlpha's 0 there. Alpha
+        saturates within a cell or two of a surface; the feature does not, so marching cubes on this volume at `feature_level(a)`
+        puts its vertices where the field's alpha IS a, with the inside / outside decision of every node unchanged (the activation
+        is monotone)."""
+        return self._dense_volume(gridSize, True)
+
+    def feature_level(self, alpha_level, length=None):
+        """The density feature f* (a float) at which the renderer's alpha over a segment of `length` (default: stepSize), 1 -
+        exp(-sigma * length * distance_scale), equals alpha_level; on the host in double: sigma* = -log1p(-alpha_level) / (length *
+        distance_scale); softplus: f* = log(expm1(sigma*)) - density_shift, and sigma* - density_shift when sigma* > 20 (softplus'
+        identity branch); relu: f* = sigma*. getDenseAlpha's alpha (compute_alpha: 1 - exp(-sigma * stepSize)) leaves distance_scale
+        out; its level is feature_level(a, stepSize / distance_scale). T2NError for an alpha_level outside (0, 1)."""
+        a = float(alpha_level)
+        if not 0.0 < a < 1.0:
+            raise T2NError(f"feature_level: alpha_level {alpha_level!r} outside (0, 1)")
+        length = float(self.stepSize if length is None else length)
+        sigma = -math.log1p(-a) / (length * float(self.distance_scale))
+        if self.fea2denseAct == "relu":
+            return sigma
+        shift = float(self.density_shift)
+        return sigma - shift if sigma > 20.0 else math.log(math.expm1(sigma)) - shift
 
     @torch.no_grad()
     def _alpha_mask_volume(self, g):
@@ -1364,8 +1401,42 @@ class TensorBase(nn.Module):
 
         normals="field": the vertex normals are -grad f / |grad f| of the density feature at the vertices (`density_gradient`: the
         field's analytic gradient) instead of the sampled volume's finite differences; verts, faces and colours are those of
-        normals=True bit for bit (the colours keep the volume normals as view directions)."""
+        normals=True bit for bit (the colours keep the volume normals as view directions).
+
+        `export_surface` is this call with two more keywords: vertices on the field's level set (surface="feature") and Taubin
+        smoothing (smooth=k)."""
+        return self._export(path, level, gridSize, colors, normals, "alpha", 0)
+
+    @torch.no_grad()
+    def export_surface(self, path=None, level=0.005, gridSize=None, colors=True, normals=True, surface="alpha", smooth=0):
+        """`export_mesh` with two more keywords; with their defaults it IS export_mesh, bit for bit. (They live here because
+        export_mesh's five-argument signature is part of the tested public surface.)
+
+        surface="feature": marching cubes runs on `getDenseFeature(gridSize)` instead of the alpha volume, at the feature level where
+        getDenseAlpha's alpha equals `level`. That alpha is compute_alpha's 1 - exp(-sigma * stepSize), without the renderer's
+        distance_scale, so the level is `feature_level(level, stepSize / distance_scale)`. Alpha saturates within a cell or two of a surface, so linear interpolation in alpha drops every vertex almost on
+        the empty node; the density feature is what the field interpolates, so its vertices lie where alpha IS `level` (exactly, up
+        to rounding, when the export grid is the field's own: along an axis-aligned edge between two texels the feature is linear).
+        The inside / outside decision of every node is the same (the activation is monotone), hence so are the faces, index for
+        index, unless a node lies within rounding of the level. normals=True gives the feature volume's finite-difference normals
+        (the same direction: out of the dense region); colours are evaluated at the new vertices; normals="field" and colors=True
+        behave as in export_mesh, and a general-shape field accepts surface="feature" with colors=False. Next to a node that an
+        attached AlphaGridMask empties (feature -inf) the vertex sits on a node and its volume normal is 0. T2NError for a `level`
+        outside (0, 1).
+
+        smooth=k > 0: `mesh.smooth_mesh(iterations=k)` (Taubin, lambda 0.5 | mu -0.53) after marching cubes. Faces and colours are
+        those of smooth=0 bit for bit: colours are evaluated at the UNsmoothed vertices. normals=True becomes `mesh.vertex_normals`
+        of the smoothed mesh; normals="field" keeps its values from the unsmoothed vertices (the field's gradient where the surface
+        was, not where smoothing moved it). With floater removal the order is `filter_components` first, then `smooth_mesh`: export
+        with smooth=0 and smooth afterwards. ValueError for a smooth that is not an integer >= 0."""
+        return self._export(path, level, gridSize, colors, normals, surface, smooth)
+
+    def _export(self, path, level, gridSize, colors, normals, surface, smooth):
         from . import mesh as M
+        if surface not in ("alpha", "feature"):
+            raise T2NError(f"export_surface: surface={surface!r} ('alpha' or 'feature')")
+        if isinstance(smooth, bool) or int(smooth) != smooth or int(smooth) < 0:
+            raise ValueError(f"export_surface: smooth={smooth!r} (an integer >= 0)")
         field_normals = isinstance(normals, str)
         if field_normals and normals != "field":
             raise T2NError(f"export_mesh: normals={normals!r} (True, False or 'field')")
@@ -1376,7 +1447,12 @@ class TensorBase(nn.Module):
             raise T2NError("export_mesh(colors=True) needs the tuned-shape field's shade stage; a general-shape field exports with "
                            "colors=False")
         g = [int(x) for x in (self.gridSize if gridSize is None else gridSize)]
-        alpha, _ = self.getDenseAlpha(g)
+        if surface == "feature":
+            # getDenseAlpha's alpha is compute_alpha's 1 - exp(-sigma * stepSize): no distance_scale in it, unlike the renderer's
+            level = self.feature_level(level, float(self.stepSize) / float(self.distance_scale))
+            alpha, _ = self.getDenseFeature(g)
+        else:
+            alpha, _ = self.getDenseAlpha(g)
         a = self.aabb.detach().float().cpu()
         spacing = (a[1] - a[0]) / (torch.tensor(g, dtype=torch.float32) - 1)
         verts, faces, nrm = M.marching_cubes(alpha, level, spacing=spacing.tolist(), origin=a[0].tolist(), normals=bool(normals or colors))
@@ -1394,6 +1470,10 @@ class TensorBase(nn.Module):
             h = g / g.abs().amax(dim=-1, keepdim=True).clamp_min(torch.finfo(torch.float32).tiny)
             nrm = -h / h.norm(dim=-1, keepdim=True).clamp_min(1.0)
         out = M.Mesh(verts, faces, nrm if normals else None, rgb8)
+        if int(smooth) > 0:
+            # the volume normals are recomputed from the smoothed faces; the field's stay what they were at the unsmoothed vertices
+            sm = M.smooth_mesh(M.Mesh(verts, faces, None if field_normals else out.normals, None), iterations=int(smooth))
+            out = M.Mesh(sm.verts, faces, out.normals if field_normals else sm.normals, rgb8)
         if path is not None:
             M.write_ply(path, out.verts, out.faces, out.normals, out.colors)
         return out
