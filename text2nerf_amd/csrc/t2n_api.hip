@@ -664,10 +664,7 @@ int post_counts(const unsigned* counters_dev, unsigned* host_dst, hipStream_t s)
 static void counts_consume(t2n_field* f, t2n_field::CountSlot& c) {
     const unsigned cap = list_capacity_budget(c.n_rays, c.n_samples, c.budget);
     unsigned long long used = c.host[kFailEntriesWord];
-    for (int l = 0; l < kLists; ++l) {
-        const unsigned n = c.host[l * kCounterStride];
-        used += n < cap ? n : cap;
-    }
+    for (int l = 0; l < kLists; ++l) used += list_live(c.host, l, cap);
     if (c.host[kOverflowWord]) f->list_retries++;
     f->list_hint = (unsigned)((used + (unsigned long long)c.n_rays - 1) / (unsigned long long)c.n_rays);
     if (!f->list_hint) f->list_hint = 1;
@@ -1052,8 +1049,7 @@ extern "C" int t2n_field_head_rows(t2n_field* f, const float* feat, uint32_t fea
     unsigned raw[kLists * kCounterStride];
     T2N_HIP(hipStreamSynchronize(s));
     T2N_HIP(hipMemcpy(raw, counters, sizeof(raw), hipMemcpyDeviceToHost));
-    unsigned long long tiles = 0;
-    for (int l = 0; l < kLists; ++l) { const unsigned c = raw[l * kCounterStride]; tiles += ((c < list_cap ? c : list_cap) + 31u) / 32u; }
+    unsigned long long tiles = tile_prefix(raw, list_cap, nullptr);
     if (tiles > tile_hi) tiles = tile_hi;
     const unsigned long long need = slot_rows ? (unsigned long long)kLists * list_cap : tiles * 32ull;
     if (feat_rows < need) { set_error("t2n_field_head_rows: feat_rows does not cover the rows the launch reads"); return T2N_ERR_INVALID; }

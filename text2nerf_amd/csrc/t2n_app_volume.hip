@@ -91,29 +91,16 @@ __global__ __launch_bounds__(256) void k_app_features_vol(const AvReadArgs a) {
     // (the per-entry body is av_feature_row, t2n_app_rows.h: the tile marcher's tail runs it with eight lanes per entry)
     constexpr int LPE = 4, EPP = 64 / LPE, PASSES = 32 / EPP;   // entries per pass, passes per tile
     const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    unsigned cnt_l = 0;
-    if (lane < a.nlists) {
-        cnt_l = a.counters[lane * kCounterStride];
-        if (cnt_l > a.list_cap) cnt_l = a.list_cap;
-    }
-    unsigned incl = (cnt_l + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    unsigned ntiles = (unsigned)__builtin_amdgcn_readfirstlane((int)__shfl(incl, a.nlists - 1));
+    unsigned cnt_l, incl;
+    unsigned ntiles = (unsigned)__builtin_amdgcn_readfirstlane((int)list_tiles(a.counters, a.list_cap, a.nlists, lane, cnt_l, incl));
     if (ntiles > a.tile_hi) ntiles = a.tile_hi;
     const unsigned wave_stride = gridDim.x * 4u;
     const int e = lane / LPE, q = lane % LPE;
     const AvVolume vol{a.avol, a.row, a.slice, a.ny1};
     for (unsigned tile = blockIdx.x * 4u + wid; tile < ntiles; tile += wave_stride) {
-        // tile -> (first entry, live entries): k_app_features_p's locate
-        const int li = (int)__popcll(__ballot((lane < a.nlists) & (incl <= tile)));
-        const unsigned before = li ? __shfl(incl, li - 1) : 0u;
-        const unsigned lbase = (unsigned)li * a.list_cap;
-        const unsigned base = (unsigned)__builtin_amdgcn_readfirstlane((int)(lbase + (tile - before) * 32u));
-        const unsigned count = lbase + __shfl(cnt_l, li);
+        // tile -> (first entry, live entries), in scalar registers
+        unsigned base, count;
+        list_locate<true>(tile, cnt_l, incl, a.list_cap, a.nlists, lane, base, count);
         const unsigned nlive = (unsigned)__builtin_amdgcn_readfirstlane((int)(count - base < 32u ? count - base : 32u));
         const float4* __restrict__ pb = a.app_pos + base;
         asm volatile("" : "+s"(pb));

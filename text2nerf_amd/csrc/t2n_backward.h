@@ -6,7 +6,6 @@
 
 namespace t2n {
 
-struct TilePrefix { unsigned t[kLists + 1]; };   // tiles before each sub-list (host-computed from the counters)
 struct GradSet { float* plane[3]; float* line[3]; };
 // The same in device memory, for a backward that never reads the counters on the host (T2N_FLAG_DEVICE_ROWS): tile prefix and row
 // count from the forward's counters (k_bwd_plan), clipped to the row CAPACITY the caller's buffers hold; overflow = the count
@@ -19,17 +18,9 @@ struct BwdPlan { TilePrefix tp; unsigned rows; unsigned overflow; };
 __device__ __forceinline__ unsigned plan_prefix(const unsigned* __restrict__ counters, unsigned list_cap, unsigned rows_cap, bool stated,
                                                 BwdPlan* __restrict__ plan, unsigned& ovf) {
     const int lane = threadIdx.x;
-    unsigned cnt = lane < kLists ? counters[lane * kCounterStride] : 0u;
-    if (cnt > list_cap) cnt = list_cap;
-    unsigned incl = (cnt + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    const unsigned excl = incl - (cnt + 31u) / 32u;
-    if (lane < kLists) plan->tp.t[lane] = excl;
-    const unsigned total = __shfl(incl, kLists - 1);
+    unsigned cnt, incl;
+    const unsigned total = list_tiles(counters, list_cap, kLists, lane, cnt, incl);
+    if (lane < kLists) plan->tp.t[lane] = incl - (cnt + 31u) / 32u;
     const unsigned rows = total * 32u;
     ovf = (!stated || rows > rows_cap) ? 1u : 0u;
     if (lane == 0) {

@@ -40,11 +40,6 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__device__ __forceinline__ unsigned slot_to_row(unsigned slot, unsigned list_cap, const TilePrefix& tp) {
-    const unsigned l = slot / list_cap;
-    return tp.t[l] * 32u + (slot - l * list_cap);
-}
-
 // Sliding-window scatter: consecutive samples of a ray (and consecutive appearance samples of the list) move by less
 // than a texel per step, so their 2x2 plane footprints and 2-row line footprints mostly coincide or shift by one. Each
 // lane (one channel) keeps the footprint's accumulators in registers and issues a global atomic only when a texel leaves
@@ -1040,7 +1035,7 @@ namespace t2n {
 #endif
 
 // Appearance records: one per appearance-list entry and plane. PASS 0 counts, PASS 1 writes (same lane -> entry -> copy map).
-// Row r of the activation buffers <-> list entry: tile r / 32 belongs to sub-list l (tp.t[l] <= tile < tp.t[l + 1]).
+// Row r of the activation buffers <-> list entry: row_to_entry (t2n_lists.h).
 struct AppBinArgs {
     FactorSet S; BinGeom geom; const float4* app_pos; const unsigned* counters; unsigned list_cap; TilePrefix tp; long long rows;
     unsigned* hist; const unsigned* tile_start; float4* recs;
@@ -1053,21 +1048,15 @@ __device__ __forceinline__ void app_bin_body(const AppBinArgs& a, unsigned bx) {
     const long long row = wv * 64 + lane;
     const long long rows = a.plan ? (long long)a.plan->rows : a.rows;
     if (wv * 64 >= rows) return;
-    // (a reference picked between the device plan and the by-value argument: flat loads, but `tp.t[l]` below stays ONE load at a computed
-    // address — a private copy turned it into a dynamically indexed register array and k_app_bin<1> from 12 into 33 us)
+    // (a reference picked between the device plan and the by-value argument: flat loads, but `tp.t[l]` in row_to_entry stays ONE load at a
+    // computed address — a private copy turned it into a dynamically indexed register array and k_app_bin<1> from 12 into 33 us)
     const TilePrefix& tp = a.plan ? a.plan->tp : a.tp;
     int key[3] = {-1, -1, -1};
     float4 rec = make_float4(0.f, 0.f, 0.f, 0.f);
     if (row < rows) {
-        const unsigned tile = (unsigned)(row >> 5);
-        int l = 0;
-#pragma unroll
-        for (int q = 1; q < kLists; ++q) l += (tp.t[q] <= tile) ? 1 : 0;
-        const unsigned slot = (unsigned)(row - (long long)tp.t[l] * 32);
-        unsigned cnt = a.counters[l * kCounterStride];
-        if (cnt > a.list_cap) cnt = a.list_cap;
-        if (slot < cnt) {
-            const float4 p = a.app_pos[(size_t)l * a.list_cap + slot];
+        unsigned idx;
+        if (row_to_entry(row, tp, a.counters, a.list_cap, idx)) {
+            const float4 p = a.app_pos[idx];
             rec = make_float4(p.x, p.y, p.z, __int_as_float((int)row));
             bin_keys(a.S, a.geom, p.x, p.y, p.z, key);
         }
@@ -1137,21 +1126,11 @@ __device__ __forceinline__ void app_scatter_plane(const AppScatterArgs& a, int l
 }
 __global__ __launch_bounds__(256) void k_bwd_app_scatter(const AppScatterArgs a) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned cnt_l = 0;
-    if (lane < kLists) { cnt_l = a.counters[lane * kCounterStride]; if (cnt_l > a.list_cap) cnt_l = a.list_cap; }
-    unsigned incl = (cnt_l + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    const unsigned ntiles = __shfl(incl, kLists - 1);
+    unsigned cnt_l, incl;
+    const unsigned ntiles = list_tiles(a.counters, a.list_cap, kLists, lane, cnt_l, incl);
     for (unsigned tile = blockIdx.x * 4u + wid; tile < ntiles; tile += gridDim.x * 4u) {
-        const int li = (int)__popcll(__ballot((lane < kLists) & (incl <= tile)));
-        const unsigned before = li ? __shfl(incl, li - 1) : 0u;
-        const unsigned lbase = (unsigned)li * a.list_cap;
-        const unsigned base = lbase + (tile - before) * 32u;
-        const unsigned count = lbase + __shfl(cnt_l, li);
+        unsigned base, count;
+        list_locate(tile, cnt_l, incl, a.list_cap, kLists, lane, base, count);
         app_scatter_plane<0>(a, lane, base, count, tile * 32u);
         app_scatter_plane<1>(a, lane, base, count, tile * 32u);
         app_scatter_plane<2>(a, lane, base, count, tile * 32u);
@@ -1462,20 +1441,13 @@ static int read_counts(const void* fwd_ws, int64_t n_rays, int n_samples, hipStr
         T2N_HIP(hipMemcpyAsync(raw, (const char*)fwd_ws + c.counters, sizeof(raw), hipMemcpyDeviceToHost, s));
         T2N_HIP(hipStreamSynchronize(s));
     }
-    for (int l = 0; l < kLists; ++l) counts[l] = raw[l * kCounterStride];
+    for (int l = 0; l < kLists; ++l) counts[l] = list_live(raw, l, c.list_cap);
     if (kept_rows_stated) *kept_rows_stated = raw[kKeptMagicWord] == kKeptMagic ? raw[kKeptRowsWord] : 0u;
     if (consume) {   // the backward overwrites the kept rows in place: a second backward on this workspace must recompute
         if (slot) { std::lock_guard<std::mutex> lock(g_ctx_mutex); if (slot->valid && slot->ws == fwd_ws) slot->host[kKeptMagicWord] = 0u; }
         // (the device word is cleared by the caller's setup kernel: a 4-byte hipMemsetAsync is a 6-us fill kernel of its own on the stream)
     }
-    unsigned t = 0;
-    for (int l = 0; l < kLists; ++l) {
-        if (counts[l] > c.list_cap) counts[l] = c.list_cap;
-        if (tp) tp->t[l] = t;
-        t += (counts[l] + 31u) / 32u;
-    }
-    if (tp) tp->t[kLists] = t;
-    *rows = (int64_t)t * 32;
+    *rows = (int64_t)tile_prefix(raw, c.list_cap, tp) * 32;
     return T2N_OK;
 }
 

@@ -31,41 +31,21 @@ HeadDims head_dims(const t2n_field_desc& d) {
     return h;
 }
 
-struct TilePrefixH { unsigned t[kLists + 1]; };
 // The forward's device-side plan (t2n_render_forward reads no count on the host): tile prefix of the sub-lists and the row count, derived
 // from the march kernel's counters by one wave; the head kernels below take their rows in PASSES of a fixed capacity — pass p covers rows
 // [row0, row0 + cap) of the call, activation row r lives at scratch row r - row0 — and clip to the count on the device. The host issues
 // the passes for the worst case (every sample an appearance sample); a pass beyond the count costs its empty launches.
 __global__ __launch_bounds__(64) void k_head_plan(const unsigned* __restrict__ counters, unsigned list_cap, HeadPlanDev* __restrict__ plan) {
     const int lane = threadIdx.x;
-    unsigned cnt = lane < kLists ? counters[lane * kCounterStride] : 0u;
-    if (cnt > list_cap) cnt = list_cap;
-    unsigned incl = (cnt + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane < kLists) plan->t[lane] = incl - (cnt + 31u) / 32u;
-    if (lane == kLists - 1) { plan->t[kLists] = incl; plan->rows = incl * 32u; }
-}
-
-// row -> appearance-list entry (rows are 32-entry tiles, sub-list by sub-list); returns false for padding rows
-__device__ __forceinline__ bool row_entry(long long row, const TilePrefixH& tp, const unsigned* counters, unsigned list_cap, unsigned& idx) {
-    const unsigned tile = (unsigned)(row >> 5);
-    int l = 0;
-#pragma unroll
-    for (int q = 1; q < kLists; ++q) l += (tp.t[q] <= tile) ? 1 : 0;
-    const unsigned slot = (unsigned)(row - (long long)tp.t[l] * 32);
-    unsigned cnt = counters[l * kCounterStride];
-    if (cnt > list_cap) cnt = list_cap;
-    idx = (unsigned)l * list_cap + slot;
-    return slot < cnt;
+    unsigned cnt, incl;
+    list_tiles(counters, list_cap, kLists, lane, cnt, incl);
+    if (lane < kLists) plan->tp.t[lane] = incl - (cnt + 31u) / 32u;
+    if (lane == kLists - 1) { plan->tp.t[kLists] = incl; plan->rows = incl * 32u; }
 }
 
 struct HeadInArgs {
     HeadDims H; const float* feat32; const float4* app_pos; const int* app_ray; const float* rays; int ray_stride; int ndc;
-    const unsigned* counters; unsigned list_cap; TilePrefixH tp; long long rows; float* x0;
+    const unsigned* counters; unsigned list_cap; TilePrefix tp; long long rows; float* x0;
     const HeadPlanDev* plan; long long row0;   // plan != NULL: tile prefix / row count from device memory, rows = the pass's capacity (see k_head_plan)
 };
 // one thread per (row, column): column c of the reference's torch.cat
@@ -77,8 +57,8 @@ __global__ __launch_bounds__(256) void k_head_in(const HeadInArgs a) {
     const long long row = a.row0 + lrow;
     if (lrow >= a.rows || (a.plan && row >= (long long)a.plan->rows)) return;
     unsigned idx;
-    const bool live = a.plan ? row_entry(row, *reinterpret_cast<const TilePrefixH*>(a.plan->t), a.counters, a.list_cap, idx)
-                             : row_entry(row, a.tp, a.counters, a.list_cap, idx);
+    // (two calls, each on its own prefix: one call on a reference picked between them reads the by-value argument with flat loads)
+    const bool live = a.plan ? row_to_entry(row, a.plan->tp, a.counters, a.list_cap, idx) : row_to_entry(row, a.tp, a.counters, a.list_cap, idx);
     float v = 0.f;
     if (live && c < a.H.K0) {
         const HeadDims& H = a.H;
@@ -144,7 +124,7 @@ __global__ __launch_bounds__(256) void k_head_in_bwd(const HeadDims H, const flo
 // rgb[c] = relu(sum_b sh_b(viewdir) feat[9 c + b] + 0.5) -> gf[9 c + b] = go[c] [rgb[c] > 0] sh_b.
 struct SimpleHeadBwdArgs {
     int shading, ndc; const float4* go; const float4* app_rgb; const int* app_ray; const float* rays; int ray_stride;
-    const unsigned* counters; unsigned list_cap; TilePrefixH tp; long long rows; float* gf;
+    const unsigned* counters; unsigned list_cap; TilePrefix tp; long long rows; float* gf;
 };
 __global__ __launch_bounds__(256) void k_simple_head_bwd(const SimpleHeadBwdArgs a) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -152,7 +132,7 @@ __global__ __launch_bounds__(256) void k_simple_head_bwd(const SimpleHeadBwdArgs
     const int f = (int)(t % 32);
     if (r >= a.rows) return;
     unsigned idx;
-    const bool live = row_entry(r, a.tp, a.counters, a.list_cap, idx);
+    const bool live = row_to_entry(r, a.tp, a.counters, a.list_cap, idx);
     float g = 0.f;
     if (live) {
         const float4 go = a.go[r];
@@ -281,7 +261,7 @@ __global__ __launch_bounds__(256) void k_dense(const float* __restrict__ IN, int
 
 // layer 2 (3 outputs) + sigmoid -> app_rgb of the row's list entry; 4 lanes per row
 struct Dense3Args {
-    const float* h1; const float* w2; const float* b2; const unsigned* counters; unsigned list_cap; TilePrefixH tp; long long rows; float4* app_rgb;
+    const float* h1; const float* w2; const float* b2; const unsigned* counters; unsigned list_cap; TilePrefix tp; long long rows; float4* app_rgb;
     const float4* app_pos;   // the entry's compositing weight (.w) rides along in app_rgb.w: k_composite reads one array
     const HeadPlanDev* plan; long long row0;
 };
@@ -304,7 +284,7 @@ __global__ __launch_bounds__(256) void k_dense3_sigmoid(const Dense3Args a) {
     s2 += dpp_quad_xor1(s2); s2 += dpp_quad_xor2(s2);
     if (in && p == 0) {
         unsigned idx;
-        if (a.plan ? row_entry(row, *reinterpret_cast<const TilePrefixH*>(a.plan->t), a.counters, a.list_cap, idx) : row_entry(row, a.tp, a.counters, a.list_cap, idx)) {
+        if (a.plan ? row_to_entry(row, a.plan->tp, a.counters, a.list_cap, idx) : row_to_entry(row, a.tp, a.counters, a.list_cap, idx)) {
             const float r = 1.f / (1.f + expf(-(s0 + a.b2[0]))), g = 1.f / (1.f + expf(-(s1 + a.b2[1]))), b = 1.f / (1.f + expf(-(s2 + a.b2[2])));
             a.app_rgb[idx] = make_float4(r, g, b, a.app_pos[idx].w);
         }

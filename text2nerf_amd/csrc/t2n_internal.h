@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/t2n.h"
+#include "t2n_lists.h"   // the appearance list: kLists, kCounterStride, TilePrefix and the tile addressing
 
 namespace t2n {
 
@@ -246,12 +247,10 @@ int launch_app_features_vol(t2n_field* f, const float4* app_pos, const unsigned*
 int launch_feature_rows(t2n_field* f, const float4* app_pos, const unsigned* counters_dev, unsigned list_cap, float* feat, unsigned feat_rows,
                         hipStream_t s);   // (t2n_shade.hip) the feature stage alone on caller-made lists, in the form f->dev.avol selects
 int launch_march_tiles(t2n_field* f, const RenderLaunch& L, int img_w, int img_h, float* spill, float4* scratch, hipStream_t s);
-constexpr int kLists = 8;   // appearance sub-lists per sub-launch
 // A tile-marcher launch is FUSED (rows in the marcher's tail, head in slot mode) when the feature rows hold one row per list slot: true of
 // budgeted lists (carve_workspace sizes their rows that way) and of small worst-case launches, never of large worst-case lists (a C2
 // frame's would take 42 GB of rows), which keep the feature stage and its dense rows.
 inline bool fuse_rows(unsigned list_cap, unsigned feat_rows) { return feat_rows && (unsigned long long)list_cap * kLists <= feat_rows; }
-constexpr int kCounterStride = 64;   // unsigned words between sub-list counters: one 256-B line each (same-line atomics serialise)
 // list_cap(n_rays, N): worst-case entries of one sub-list = rays of the largest XCD run x samples
 inline unsigned list_capacity(long long n_rays, int n_samples) {
     const unsigned nblocks = (unsigned)((n_rays + 3) / 4);
@@ -297,7 +296,7 @@ int ss_variant_word(t2n_field* f, unsigned* out, hipStream_t s);   // DIAGNOSTIC
 struct HeadDims { int shading, C, fea_pe, view_pe, pos_pe, o_feat, o_view, o_pe_a, n_pe_a, o_pe_v, n_pe_v, K0, K0pad; };
 HeadDims head_dims(const t2n_field_desc& d);
 inline bool head_is_generic(int shading) { return shading == T2N_SHADE_MLP_FEA || shading == T2N_SHADE_MLP_PE || shading == T2N_SHADE_MLP; }
-struct HeadPlanDev { unsigned t[kLists + 1]; unsigned rows; };   // device-side plan of a general-head forward: tile prefix, row count
+struct HeadPlanDev { TilePrefix tp; unsigned rows; };   // device-side plan of a general-head forward: tile prefix, row count
 int launch_head_plan(const unsigned* counters, unsigned list_cap, HeadPlanDev* plan, hipStream_t s);
 // OUT[rows, N] = act(IN[rows, K] Wt[N, K]^T + bias) on exact-fp32 MFMA (k_dense); rows clipped to plan->rows - row0 on the device
 int launch_dense_rows(const float* IN, int ldin, const float* Wt, int K, int N, const float* bias, int relu, long long rows, float* OUT, int ldo,

@@ -556,24 +556,14 @@ __global__ __launch_bounds__(256) void k_mlp_ss3(const Args a) {
                  reinterpret_cast<const u4v*>(reinterpret_cast<const char*>(lds) + ob2)};
     const float* __restrict__ LBh = reinterpret_cast<const float*>(reinterpret_cast<const char*>(lds) + obb);
 
-    unsigned cnt_l = 0;
-    if (lane < a.nlists) {
-        cnt_l = a.counters[lane * kCounterStride];
-        if (cnt_l > a.list_cap) cnt_l = a.list_cap;
-    }
-    unsigned incl = (cnt_l + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    unsigned ntiles = __shfl(incl, a.nlists - 1);
+    unsigned cnt_l, incl;
+    unsigned ntiles = list_tiles(a.counters, a.list_cap, a.nlists, lane, cnt_l, incl);
     if (ntiles > a.tile_hi) ntiles = a.tile_hi;
     const unsigned nrounds = (ntiles + 11u) / 12u;
     if (blockIdx.x >= nrounds) return;
     if (tid < 8) { LT[tid] = tid < a.nlists ? incl : 0xffffffffu; LT[8 + tid] = cnt_l; }
     // SLOT: the table above stays in lanes 0..7 of two registers (sixteen scalars are more than the kernel's SGPR budget holds: they
-    // spill); a tile is located with one compare and two v_readlane
+    // spill); a tile is located by list_locate_readlane (t2n_lists.h)
     const unsigned incl_m = lane < a.nlists ? incl : 0xffffffffu;
     const unsigned s_ntiles = SLOT ? (unsigned)__builtin_amdgcn_readfirstlane((int)ntiles) : 0u;
 
@@ -598,12 +588,10 @@ __global__ __launch_bounds__(256) void k_mlp_ss3(const Args a) {
             // tile (and a tile past the last one) re-reads a live row, whose outputs SS3_FINAL discards
             unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)((r * 4u + (unsigned)w) * 3u + (unsigned)t));
             tile = tile < s_ntiles ? tile : s_ntiles - 1u;
-            const int li = (int)__popcll(__ballot(incl_m <= tile));   // (tile < the last prefix sum: li <= 7)
-            const unsigned before = li ? (unsigned)__builtin_amdgcn_readlane((int)incl_m, li - 1) : 0u;
-            const unsigned cnt = (unsigned)__builtin_amdgcn_readlane((int)cnt_l, li);
-            const unsigned lbase = (unsigned)li * a.list_cap, lastl = lbase + cnt - 1u;
-            i = lbase + (tile - before) * 32u + (unsigned)j;
-            i = i < lastl ? i : lastl;
+            unsigned base, count;
+            list_locate_readlane(tile, cnt_l, incl_m, a.list_cap, base, count);
+            i = base + (unsigned)j;
+            i = i < count - 1u ? i : count - 1u;
         } else {
             i = ((r * 4u + (unsigned)w) * 3u + (unsigned)t) * 32u + (unsigned)j;
             i = i < last ? i : last;

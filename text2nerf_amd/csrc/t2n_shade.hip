@@ -464,19 +464,8 @@ __global__ __launch_bounds__(256, 2) void k_shade(const ShadeArgs a) {
     float* __restrict__ X = smem + (size_t)wid * kTileFloats;
     float* __restrict__ Fe = X;   // reused after the basis contraction
     const FieldDev& F = a.F;
-    // tile enumeration over the appearance sub-lists (list l occupies [l*list_cap, l*list_cap + counters[l]))
-    unsigned cnt_l = 0;
-    if (lane < a.nlists) {
-        cnt_l = a.counters ? a.counters[lane * kCounterStride] : a.count_max;
-        if (a.counters && cnt_l > a.list_cap) cnt_l = a.list_cap;
-    }
-    unsigned incl = (cnt_l + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    unsigned ntiles = __shfl(incl, a.nlists - 1);
+    unsigned cnt_l, incl;   // tile enumeration over the appearance sub-lists (t2n_lists.h)
+    unsigned ntiles = list_tiles<true>(a.counters, a.list_cap, a.nlists, lane, cnt_l, incl, a.count_max);
     if (ntiles > a.tile_hi) ntiles = a.tile_hi;
     if (a.run_if_nonzero) {
         if (*a.run_if_nonzero == 0u) return;
@@ -490,11 +479,8 @@ __global__ __launch_bounds__(256, 2) void k_shade(const ShadeArgs a) {
     float amax = 0.f;   // largest magnitude handed to an f16 convert (split path): past the f16 range the launch is redone exactly
 
     for (unsigned tile = a.tile_lo + blockIdx.x * 4u + wid; tile < ntiles; tile += wave_stride) {
-        const int li = (int)__popcll(__ballot((lane < a.nlists) & (incl <= tile)));
-        const unsigned before = li ? __shfl(incl, li - 1) : 0u;
-        const unsigned lbase = (unsigned)li * a.list_cap;
-        const unsigned base = lbase + (tile - before) * 32u;
-        const unsigned count = lbase + __shfl(cnt_l, li);      // one past the last live entry of this sub-list
+        unsigned base, count;   // (count: one past the last live entry of this sub-list)
+        list_locate(tile, cnt_l, incl, a.list_cap, a.nlists, lane, base, count);
         // ---- gather: plane x line products for 32 samples x 144 channels -> X ---------------------------------------
         const unsigned row0 = tile * 32u;   // activation row of lane sample 0 (ctx mode)
         const bool keep_rows = row0 + 32u <= a.ctx_rows;
@@ -1234,6 +1220,8 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
     const FieldDev& F = a.F;
     for (int i = threadIdx.x; i < kPairBasisVec; i += 64 * kPairWaves) Wl[i] = F.basisH[i];
     __syncthreads();   // the only workgroup barrier: from here on the waves run on their own
+    // list_tiles / list_locate<true> of t2n_lists.h, written out: with the helper in this prologue the compiler lays out the staged loop's
+    // set-aside branch differently (three scalar instructions more per tile in k_app_features_p<false>; same registers)
     unsigned cnt_l = 0;
     if (lane < a.nlists) {
         cnt_l = a.counters[lane * kCounterStride];
@@ -1592,18 +1580,8 @@ __global__ __launch_bounds__(256, 2) void k_shade_coop(const ShadeArgs a) {
     float* __restrict__ Fe = X;
     float* __restrict__ Hs = X;
     const FieldDev& F = a.F;
-    unsigned cnt_l = 0;
-    if (lane < a.nlists) {
-        cnt_l = a.counters ? a.counters[lane * kCounterStride] : a.count_max;
-        if (a.counters && cnt_l > a.list_cap) cnt_l = a.list_cap;
-    }
-    unsigned incl = (cnt_l + 31u) / 32u;
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    unsigned ntiles = __shfl(incl, a.nlists - 1);
+    unsigned cnt_l, incl;
+    unsigned ntiles = list_tiles<true>(a.counters, a.list_cap, a.nlists, lane, cnt_l, incl, a.count_max);
     if (ntiles > a.tile_hi) ntiles = a.tile_hi;
     if (a.split_unsafe && *a.split_unsafe) {   // weights beyond the fixed pre-scale's range: the exact launch behind this one does the work
         if (a.range_flag && a.tile_lo < ntiles && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(a.range_flag, 1u);
@@ -1616,13 +1594,7 @@ __global__ __launch_bounds__(256, 2) void k_shade_coop(const ShadeArgs a) {
     for (unsigned tile0 = a.tile_lo + blockIdx.x * 4u; tile0 < ntiles; tile0 += block_stride) {
         const unsigned tile = tile0 + wid;
         unsigned base = 0, count = 0;
-        if (tile < ntiles) {
-            const int li = (int)__popcll(__ballot((lane < a.nlists) & (incl <= tile)));
-            const unsigned before = li ? __shfl(incl, li - 1) : 0u;
-            const unsigned lbase = (unsigned)li * a.list_cap;
-            base = lbase + (tile - before) * 32u;
-            count = lbase + __shfl(cnt_l, li);
-        }
+        if (tile < ntiles) list_locate(tile, cnt_l, incl, a.list_cap, a.nlists, lane, base, count);
         [[maybe_unused]] const unsigned row0 = tile * 32u;
         [[maybe_unused]] const bool keep_rows = CTX && tile < ntiles && row0 + 32u <= a.ctx_rows;
         [[maybe_unused]] const ShadeCtx cx = keep_rows ? a.ctx : ShadeCtx{nullptr, nullptr, nullptr, nullptr};
