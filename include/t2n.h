@@ -986,6 +986,72 @@ int t2n_mesh_smooth_pass(const double* pos_in, double* pos_out, const int64_t* o
 int t2n_mesh_vertex_normals(const float* verts, const int32_t* faces, int64_t n_faces, const int64_t* vf_offsets, const int32_t* vf_faces,
                             int64_t n_entries, int64_t n_verts, float* normals, t2n_stream stream);
 
+/* ---- Mesh export: simplification by vertex clustering on a uniform grid with quadric-optimal representatives (Lindstrom's out-of-core
+ * simplification), the decimation that users of TensoRF-family exports run last in MeshLab. No priority queue: keys -> sort -> rows -> one
+ * thread per row, like the stage above. Every output is a function of the input alone: integer keys, float64 sums in a fixed order, no
+ * float atomics, two calls give bit-equal arrays. Clustering does NOT preserve manifoldness. origin3, cell3 (float64) and dims3 (int32)
+ * are host arrays of three. Every float64 operation below is a single IEEE operation (no contraction), in the order written.
+ *   grid           vertex v lies in cell c_k = floor(((double)x_k - o_k) / h_k), k = 0, 1, 2; the cell's id is (c0 n1 + c1) n2 + c2 with
+ *                  n = dims3, n0 n1 n2 < 2^31. t2n_mesh_cluster_keys writes keys [V] = id << 32 | v; a vertex that is not finite or
+ *                  whose cell is outside [0, n) gets the high word 2^31 - 1, behind every cell. The caller sorts the keys ascending.
+ *   t2n_mesh_cluster_rows   over the SORTED keys: clusters are the occupied cells, numbered 0 .. K-1 in ascending id (a flag where the high
+ *                  word changes, per-256 sums, one workgroup's scan with a running carry). vertex_map [V] int32 (-1 for a vertex outside
+ *                  the grid), offsets int64 (room for V + 1, K + 1 written), members [V] int32 (row k = members[offsets[k] :
+ *                  offsets[k+1]], ascending vertex index), cells int32 (room for [V][3], [K][3] written: c0, c1, c2), K to
+ *                  n_clusters_out (device int64 [1]). Workspace: t2n_mesh_cluster_rows_workspace_bytes(n_verts) (0 = bad argument).
+ *   t2n_mesh_cluster_face_keys   keys [3 F] = vertex_map[corner] << 32 | face per corner (INT64_MAX for a face with an index outside
+ *                  [0, n_verts) or a map outside [0, n_clusters)); sorted and given to t2n_mesh_csr with n_rows = K they are the
+ *                  cluster -> face rows: every face with at least one corner in the cluster, once, ascending.
+ *   t2n_mesh_cluster_place   out [K][3] fp32, one thread per cluster. mean_k = (the members' (double)x_k summed from 0.0 in ascending
+ *                  vertex index) / (double)count. quadric = 0: out = (float)mean. quadric = 1: over the cluster's face row in its
+ *                  order, (a, b, c) = the face's corners rotated so that its smallest vertex index (the first of equal ones) comes
+ *                  first; u = x_b - x_a, w = x_c - x_a in float64 from the fp32 positions; n = (u1 w2 - u2 w1, u2 w0 - u0 w2,
+ *                  u0 w1 - u1 w0), unnormalised: faces weigh by squared area and there is no square root; a face whose n is all zero or
+ *                  not finite is skipped; d = x_a - mean; r = (n0 d0 + n1 d1) + n2 d2; A00 += n0 n0, A01 += n0 n1, A02 += n0 n2,
+ *                  A11 += n1 n1, A12 += n1 n2, A22 += n2 n2, b_k += n_k r (product, then sum). t = (A00 + A11) + A22; if t is not > 0 or
+ *                  not finite the result is the mean. Else e = regularisation * t, M_kk = A_kk + e, and (A + e I) x = b by cofactors:
+ *                      C00 = M11 M22 - A12 A12    C01 = A02 A12 - A01 M22    C02 = A01 A12 - A02 M11
+ *                      C11 = M00 M22 - A02 A02    C12 = A01 A02 - M00 A12    C22 = M00 M11 - A01 A01
+ *                      det = (M00 C00 + A01 C01) + A02 C02
+ *                      x_0 = ((C00 b0 + C01 b1) + C02 b2) / det, x_1 with (C01, C11, C12), x_2 with (C02, C12, C22)
+ *                  p = mean + x; lo_k = o_k + (double)c_k h_k, hi_k = o_k + (double)(c_k + 1) h_k with c = cells[cluster]; p is the
+ *                  result iff lo_k <= p_k <= hi_k on every axis (a p that is not finite fails), else the mean. Rounded to fp32 once. The
+ *                  Tikhonov term e pulls flat and creased clusters towards the mean and keeps the system positive definite: no SVD, no
+ *                  threshold. n_members / n_entries = the lengths of members / face_rows; rows are clipped to them, and a member, face
+ *                  or corner outside its range is skipped. With quadric = 0 faces, cells, face_offsets and face_rows may be NULL.
+ *   t2n_mesh_cluster_colors   out [K][3] uint8 = (sum of the members' channel + count / 2) / count in integers.
+ *   t2n_mesh_simplify_face_map   rotated [F][3] int32: every index through vertex_map, the triple rotated so that the smallest index
+ *                  comes first (cyclic order kept); (-1, -1, -1) for a face with two equal mapped indices (dropped) or a bad index.
+ *                  key_hi [F] = the first index (n_clusters for a dropped face), key_lo [F] = second << 32 | third (INT64_MAX for a
+ *                  dropped face). The caller sorts STABLY by key_lo, then stably by key_hi: `order` [F] int64, the faces by rotated
+ *                  triple, equal triples in ascending face index.
+ *   t2n_mesh_simplify_faces   keeps, of the faces with the same rotated triple, the one with the lowest face index (an oppositely
+ *                  oriented twin (a, c, b) is another triple and stays), and writes the kept rotated triples in ascending face index to
+ *                  faces_out (room for [F][3]) and their number to count_out (device int64 [1]). Flags, scan and compaction as above.
+ *                  Workspace: t2n_mesh_simplify_faces_workspace_bytes(n_faces) (0 = bad argument).
+ * T2N_ERR_INVALID (before any HIP call): NULL required pointer, a negative count, n_verts >= 2^31, 3 * n_faces >= 2^31, n_clusters outside
+ * [0, n_verts], a cell that is not finite and positive, an origin that is not finite, a dimension < 1, 2^31 cells and more, a
+ * regularisation that is negative or not finite, quadric outside {0, 1}, workspace_bytes smaller than required. Empty inputs launch no
+ * kernel. */
+int t2n_mesh_cluster_keys(const float* verts, int64_t n_verts, const double* origin3, const double* cell3, const int32_t* dims3, int64_t* keys,
+                          t2n_stream stream);
+size_t t2n_mesh_cluster_rows_workspace_bytes(int64_t n_verts);
+int t2n_mesh_cluster_rows(const int64_t* sorted_keys, int64_t n_verts, const int32_t* dims3, int32_t* vertex_map, int64_t* offsets,
+                          int32_t* members, int32_t* cells, int64_t* n_clusters_out, void* workspace, size_t workspace_bytes, t2n_stream stream);
+int t2n_mesh_cluster_face_keys(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* vertex_map, int64_t n_clusters,
+                               int64_t* keys, t2n_stream stream);
+int t2n_mesh_cluster_place(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int64_t* offsets,
+                           const int32_t* members, int64_t n_members, const int32_t* cells, int64_t n_clusters, const int64_t* face_offsets,
+                           const int32_t* face_rows, int64_t n_entries, const double* origin3, const double* cell3, double regularisation,
+                           int quadric, float* out, t2n_stream stream);
+int t2n_mesh_cluster_colors(const uint8_t* colors, int64_t n_verts, const int64_t* offsets, const int32_t* members, int64_t n_members,
+                            int64_t n_clusters, uint8_t* out, t2n_stream stream);
+int t2n_mesh_simplify_face_map(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* vertex_map, int64_t n_clusters,
+                               int32_t* rotated, int64_t* key_hi, int64_t* key_lo, t2n_stream stream);
+size_t t2n_mesh_simplify_faces_workspace_bytes(int64_t n_faces);
+int t2n_mesh_simplify_faces(const int32_t* rotated, const int64_t* order, int64_t n_faces, int32_t* faces_out, int64_t* count_out,
+                            void* workspace, size_t workspace_bytes, t2n_stream stream);
+
 /* ---- Floaters in the field: connected components of a dense volume on the device and removal of the unwanted ones, the stage users of
  * TensoRF-family code run on the host (alpha volume to the CPU, scipy.ndimage.label, a mask built by hand). All integer: every output is
  * a function of the input alone, two calls give bit-equal arrays. No float atomics, no host read inside the calls.

@@ -182,6 +182,20 @@ SIGNATURES = {
                                        C.c_void_p]),
     "t2n_mesh_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_void_p]),
+    "t2n_mesh_cluster_keys": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p,
+                                        C.c_void_p]),
+    "t2n_mesh_cluster_rows_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "t2n_mesh_cluster_rows": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "t2n_mesh_cluster_face_keys": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "t2n_mesh_cluster_place": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int,
+                                         C.c_void_p, C.c_void_p]),
+    "t2n_mesh_cluster_colors": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "t2n_mesh_simplify_face_map": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "t2n_mesh_simplify_faces_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "t2n_mesh_simplify_faces": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "t2n_volume_components_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "t2n_volume_components_tile": (C.c_int, [C.POINTER(C.c_int)]),
     "t2n_volume_components": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

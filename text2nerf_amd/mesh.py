@@ -11,6 +11,8 @@ writer, in the place of `skimage.measure.marching_cubes` on a host copy followed
     mesh_adjacency               faces, n_verts -> Adjacency(offsets, neighbours): sorted unique CSR rows (csrc/t2n_mesh_smooth.hip)
     smooth_mesh                  Taubin lambda | mu smoothing in float64 over those rows, normals recomputed
     vertex_normals               area-weighted normals of a mesh's faces, float64 sums in ascending face order
+    mesh_clusters                verts, cell -> Clusters(vertex_map, n_clusters, offsets, members, cells): the occupied cells of a uniform grid
+    simplify_mesh                one vertex per cluster at its quadric-optimal point or its mean (csrc/t2n_mesh_simplify.hip); NOT manifold-preserving
 
 The meshes are closed oriented 2-manifolds (the case table is generated from rules, tools/gen_mc_table.py); the right-hand normal of
 every triangle, and every vertex normal, points towards LOWER values: out of the dense region of an alpha volume. Vertex and face order
@@ -21,6 +23,7 @@ A Text2NeRF alpha volume at the export level holds the scene's surface plus deta
     m = tensorf.export_mesh(None)                 # colours and normals as before
     m = filter_components(m, keep_largest=1)      # or min_faces=...
     m = smooth_mesh(m, iterations=10)             # optional: Taubin smoothing, after the floaters have left
+    m = simplify_mesh(m, cell=2 * node_spacing)   # optional: vertex clustering, last (it does not preserve manifoldness)
     write_ply("scene.ply", *m)
 
 Components are all-integer (lock-free union-find whose roots are each component's smallest vertex, integer counts, scans): labels,
@@ -54,6 +57,14 @@ class Components(NamedTuple):
 class Adjacency(NamedTuple):
     offsets: torch.Tensor               # [V+1] int64: row v is neighbours[offsets[v] : offsets[v+1]]
     neighbours: torch.Tensor            # [E] int32, every row sorted ascending and unique
+
+
+class Clusters(NamedTuple):
+    vertex_map: torch.Tensor            # [V] int32: the cluster of every vertex
+    n_clusters: int                     # K: the occupied cells, numbered in ascending cell id
+    offsets: torch.Tensor               # [K+1] int64: cluster k is members[offsets[k] : offsets[k+1]]
+    members: torch.Tensor               # [V] int32, every row in ascending vertex index
+    cells: torch.Tensor                 # [K,3] int32: the cell (c0, c1, c2) of every cluster
 
 
 def _device():
@@ -263,10 +274,17 @@ def _csr(lib, f, V, dev, edges):
     if n == 0:                                                  # nothing is launched
         return torch.zeros(V + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        stream = _lib.current_stream_ptr(dev)
         keys = torch.empty(n, dtype=torch.int64, device=dev)
         name = "t2n_mesh_edge_keys" if edges else "t2n_mesh_face_keys"
-        _lib.check(getattr(lib, name)(_lib.ptr(f), F, V, _lib.ptr(keys), stream), name)
+        _lib.check(getattr(lib, name)(_lib.ptr(f), F, V, _lib.ptr(keys), _lib.current_stream_ptr(dev)), name)
+    return _csr_rows(lib, keys, V, dev)
+
+
+def _csr_rows(lib, keys, n_rows, dev):
+    """(offsets [n_rows+1] int64, values [E] int32) of unsorted keys row << 32 | value: a device sort, t2n_mesh_csr, the 8-byte read of E."""
+    n, V = int(keys.shape[0]), int(n_rows)
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream_ptr(dev)
         keys = torch.sort(keys).values                          # integer keys: the sorted array does not depend on how it was sorted
         nbytes = int(lib.t2n_mesh_csr_workspace_bytes(n))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -415,6 +433,219 @@ def smooth_mesh(mesh, iterations=10, lamb=0.5, mu=-0.53, fixed=None, adjacency=N
         return Mesh(v, f, n, c)
     host = lambda x: None if x is None else x.cpu().numpy()     # noqa: E731
     return Mesh(host(v), host(f), host(n), host(c))
+
+
+# ---- simplification: vertex clustering with quadric placement ---------------------------------------------------------------------------
+def _as_tensor(x):
+    return x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _cluster_grid(verts, cell, origin, who):
+    """(positions as a float32 tensor where they live, o [3], h [3], dims [3]) of a clustering: every refusal of the definition, from
+    the arguments and one aminmax of the positions (six floats on the host); dims is None for V == 0. No launch of the library's."""
+    try:
+        h = [float(t) for t in np.asarray(cell.detach().cpu() if isinstance(cell, torch.Tensor) else cell, dtype=np.float64).reshape(-1)]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: cell {cell!r} (a positive finite scalar or three)") from None
+    if len(h) == 1:
+        h = h * 3
+    if len(h) != 3 or not all(math.isfinite(t) and t > 0 for t in h):
+        raise ValueError(f"{who}: cell {cell!r} (a positive finite scalar or three)")
+    if len(verts.shape) != 2 or verts.shape[1] != 3:
+        raise ValueError(f"{who}: verts of shape {tuple(verts.shape)}, need [V,3]")
+    o = None
+    if origin is not None:
+        o = _three(origin, "origin")
+        if not all(math.isfinite(t) for t in o):
+            raise ValueError(f"{who}: origin {o} is not finite")
+    v = _as_tensor(verts).detach().to(torch.float32)
+    if int(v.shape[0]) >= 2**31:
+        raise ValueError(f"{who}: {v.shape[0]} vertices (need V < 2^31)")
+    if v.shape[0] == 0:
+        return v, o or [0.0, 0.0, 0.0], h, None
+    lo, hi = torch.aminmax(v, dim=0)
+    lo, hi = (([float(t) for t in x]) for x in torch.stack([lo, hi]).cpu().tolist())      # the one read: six floats
+    if not all(math.isfinite(t) for t in lo + hi):
+        raise ValueError(f"{who}: a vertex is not finite (the positions span {lo} to {hi})")
+    if o is None:
+        o = lo
+    elif any(a < b for a, b in zip(lo, o)):
+        raise ValueError(f"{who}: a vertex at {lo} lies below the origin {o}")
+    top = [(b - a) / s for a, b, s in zip(o, hi, h)]           # the device's own operations on the largest coordinate
+    if not all(math.isfinite(t) for t in top):
+        raise ValueError(f"{who}: a cell of {h} over positions up to {hi} gives 2^31 cells and more")
+    dims = [int(math.floor(t)) + 1 for t in top]
+    if dims[0] * dims[1] * dims[2] >= 2**31:
+        raise ValueError(f"{who}: a grid of {dims} cells (need n0 n1 n2 < 2^31)")
+    return v, o, h, dims
+
+
+def _clusters(lib, v, dev, o, h, dims):
+    """Clusters of checked device positions [V,3] float32, V > 0; device tensors. Reads the 8 bytes of K."""
+    V = int(v.shape[0])
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream_ptr(dev)
+        d3 = (C.c_int32 * 3)(*dims)
+        keys = torch.empty(V, dtype=torch.int64, device=dev)
+        _lib.check(lib.t2n_mesh_cluster_keys(_lib.ptr(v), V, (C.c_double * 3)(*o), (C.c_double * 3)(*h), d3, _lib.ptr(keys), stream),
+                   "t2n_mesh_cluster_keys")
+        keys = torch.sort(keys).values                          # integer keys: the sorted array does not depend on how it was sorted
+        nbytes = int(lib.t2n_mesh_cluster_rows_workspace_bytes(V))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        vmap = torch.empty(V, dtype=torch.int32, device=dev)
+        off = torch.empty(V + 1, dtype=torch.int64, device=dev)
+        mem = torch.empty(V, dtype=torch.int32, device=dev)
+        cells = torch.empty(V, 3, dtype=torch.int32, device=dev)
+        k = torch.empty(1, dtype=torch.int64, device=dev)
+        _lib.check(lib.t2n_mesh_cluster_rows(_lib.ptr(keys), V, d3, _lib.ptr(vmap), _lib.ptr(off), _lib.ptr(mem), _lib.ptr(cells), _lib.ptr(k),
+                                             _lib.ptr(ws), nbytes, stream), "t2n_mesh_cluster_rows")
+        K = int(k.cpu().item())                                 # the one 8-byte read
+        return Clusters(vmap, K, off[:K + 1].clone(), mem, cells[:K].clone())
+
+
+def _empty_clusters(dev):
+    return Clusters(torch.empty(0, dtype=torch.int32, device=dev), 0, torch.zeros(1, dtype=torch.int64, device=dev),
+                    torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, 3, dtype=torch.int32, device=dev))
+
+
+def _clusters_to_host(c):
+    return Clusters(c.vertex_map.cpu().numpy(), c.n_clusters, c.offsets.cpu().numpy(), c.members.cpu().numpy(), c.cells.cpu().numpy())
+
+
+@torch.no_grad()
+def mesh_clusters(verts, cell, origin=None):
+    """The clusters of a uniform grid over `verts` [V,3]: Clusters(vertex_map [V] int32, n_clusters K, offsets [K+1] int64, members [V]
+    int32, cells [K,3] int32). `cell` is the grid's spacing in world units, a positive finite scalar or three values; `origin` (three
+    values) defaults to the componentwise minimum of the positions. Vertex v lies in cell c_k = floor(((double)x_k - o_k) / h_k),
+    every step a single float64 operation; with n_k = max c_k + 1 the cell's id is (c0 n1 + c1) n2 + c2. Clusters are the occupied
+    cells, numbered 0 .. K-1 in ascending id, so the numbering is a function of the positions and the grid alone; row k of `members`
+    (members[offsets[k] : offsets[k+1]]) holds cluster k's vertices in ascending index, cells[k] its (c0, c1, c2). V == 0 gives empty
+    arrays and launches nothing. Device tensors in, device tensors out; numpy arrays / CPU tensors in, numpy arrays out, through the
+    device. Host reads: the positions' min / max and the 8 bytes of K. ValueError (before any launch): a cell that is not finite and
+    positive, a vertex that is not finite, a vertex below a given origin, n0 n1 n2 >= 2^31, verts that are not [V,3]. T2NError
+    without a GPU."""
+    v, o, h, dims = _cluster_grid(verts, cell, origin, "mesh_clusters")
+    lib = _lib.load()
+    dev = v.device if v.is_cuda else _device()
+    c = _empty_clusters(dev) if dims is None else _clusters(lib, v.to(dev).contiguous(), dev, o, h, dims)
+    return c if _is_device(verts) else _clusters_to_host(c)
+
+
+def _checked_clusters(clusters, V, dev):
+    """A caller's Clusters on the device, refused (ValueError) unless its rows can be walked: one host read of eight integers."""
+    as_t = lambda x, dt: _as_tensor(x).detach().to(device=dev, dtype=dt).contiguous()      # noqa: E731
+    if len(tuple(clusters)) != 5:
+        raise ValueError("simplify_mesh: clusters is not a Clusters(vertex_map, n_clusters, offsets, members, cells)")
+    K = int(clusters[1])
+    vmap, off, mem, cells = as_t(clusters[0], torch.int32), as_t(clusters[2], torch.int64), as_t(clusters[3], torch.int32), as_t(clusters[4], torch.int32)
+    if not 0 <= K <= V or (K == 0) != (V == 0) or tuple(vmap.shape) != (V,) or tuple(off.shape) != (K + 1,) or tuple(mem.shape) != (V,) or \
+            tuple(cells.shape) != (K, 3):
+        raise ValueError(f"simplify_mesh: clusters of {tuple(vmap.shape)} map entries, {K} clusters, {tuple(off.shape)} offsets, "
+                         f"{tuple(mem.shape)} members and {tuple(cells.shape)} cells do not belong to a mesh of {V} vertices")
+    if V:
+        step = (off[1:] - off[:-1]).amin()
+        (mlo, mhi), (vlo, vhi) = torch.aminmax(mem), torch.aminmax(vmap)
+        first, last, step, mlo, mhi, vlo, vhi, clo = (int(x) for x in torch.stack(
+            [off[0], off[-1], step, mlo.long(), mhi.long(), vlo.long(), vhi.long(), cells.amin().long()]).cpu().tolist())
+        if first != 0 or last != V or step < 1 or mlo < 0 or mhi >= V or vlo < 0 or vhi >= K or clo < 0:
+            raise ValueError(f"simplify_mesh: cluster offsets run from {first} to {last} (smallest step {step}) over members that span "
+                             f"[{mlo}, {mhi}] and a map that spans [{vlo}, {vhi}]: not the {K} clusters of a mesh of {V} vertices")
+    return Clusters(vmap, K, off, mem, cells)
+
+
+@torch.no_grad()
+def simplify_mesh(mesh, cell, origin=None, placement="quadric", regularisation=1e-3, clusters=None):
+    """`mesh` (a Mesh, or (verts, faces[, normals[, colors]])) simplified by vertex clustering on a uniform grid of spacing `cell`
+    (Lindstrom's out-of-core simplification), as a Mesh: one output vertex per occupied cell, in `mesh_clusters`' order (`cell` and
+    `origin` as there). No priority queue, float64 sums in a fixed order, no float atomics: the output is a function of the input
+    alone, two calls give the same bits.
+
+    Position of cluster k. placement="mean": the float64 sum of its members' positions in ascending vertex index, divided by the
+    count, rounded to float32 once. placement="quadric": the point closest (in the squared-area-weighted sense) to the planes of the
+    input faces with at least one corner in the cluster, each face once, in ascending face index: with the face's corners rotated so
+    that the smallest vertex index comes first, n = (x_b - x_a) x (x_c - x_a) in float64 from the float32 positions, unnormalised (no
+    square root anywhere; a face whose n is zero or not finite is skipped), r = n . (x_a - mean), A += n n^T, b += n r; t = trace A;
+    (A + regularisation t I) x = b by cofactors in the order include/t2n.h fixes; p = mean + x. The Tikhonov term pulls flat and
+    creased clusters towards the mean and keeps the system positive definite. p is the representative if it lies in the cluster's
+    cell [o + c h, o + (c + 1) h] on every axis; otherwise, and when t is not > 0 or not finite (a cluster without faces), the mean.
+
+    Faces: every index goes through vertex_map; a face with two equal mapped indices is dropped; the rest are rotated so that the
+    smallest index comes first (cyclic order kept); of faces with the same rotated triple only the one with the lowest input index
+    stays (an oppositely oriented twin (a, c, b) is a different triangle and stays); kept faces keep their relative order. Colours:
+    per channel (sum of the members + count / 2) / count in integers. Normals, if the mesh has them, are `vertex_normals` of the
+    output. The positions do not depend on the rotation of a face's indices; face order enters through the order of the float64 sums.
+
+    Clustering does NOT preserve manifoldness: two sheets that pass through one cell are welded, and an edge may end up with more
+    than two faces. The documented order is `filter_components`, `smooth_mesh`, then `simplify_mesh`. `clusters`: an earlier
+    mesh_clusters(verts, cell, origin) of the same arguments, to skip building it. Device tensors in, device tensors out; numpy
+    arrays / CPU tensors in, numpy arrays out, through the device; normals and colours that are None stay None. Host reads: the
+    positions' min / max, the 8 bytes of K, of the face rows' length and of F', and the index check's min / max. ValueError (before
+    any launch): as `mesh_clusters`; a placement other than "mean" / "quadric"; a regularisation that is negative or not finite; faces
+    that are not [F,3] integer or hold an index outside [0, V); rows that do not match verts; clusters that are not the rows of V
+    vertices. T2NError without a GPU."""
+    parts = tuple(mesh)
+    if not 2 <= len(parts) <= 4:
+        raise ValueError(f"simplify_mesh: a mesh of {len(parts)} parts, need (verts, faces[, normals[, colors]])")
+    verts, faces, normals, colors = parts + (None,) * (4 - len(parts))
+    if placement not in ("mean", "quadric"):
+        raise ValueError(f"simplify_mesh: placement {placement!r} (\"mean\" or \"quadric\")")
+    reg = float(regularisation)
+    if not (reg >= 0.0 and math.isfinite(reg)):
+        raise ValueError(f"simplify_mesh: regularisation {regularisation!r} (finite and >= 0)")
+    v, o, h, dims = _cluster_grid(verts, cell, origin, "simplify_mesh")
+    V = int(v.shape[0])
+    lib = _lib.load()
+    f, dev = _faces_on_device(faces, V, "simplify_mesh")
+    F = int(f.shape[0])
+    v = v.to(dev).contiguous()
+    n = _rows(normals, V, torch.float32, dev, "normals", "simplify_mesh")
+    c = _rows(colors, V, torch.uint8, dev, "colors", "simplify_mesh")
+    if clusters is not None:
+        cl = _checked_clusters(clusters, V, dev)
+    else:
+        cl = _empty_clusters(dev) if V == 0 else _clusters(lib, v, dev, o, h, dims)
+    K = cl.n_clusters
+    out_v = torch.empty(K, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(0, 3, dtype=torch.int32, device=dev)
+    out_c = None if c is None else torch.empty(K, 3, dtype=torch.uint8, device=dev)
+    if K > 0:                                                   # nothing is launched on an empty mesh
+        quadric = placement == "quadric"
+        foff = frow = None
+        if quadric:
+            keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(lib.t2n_mesh_cluster_face_keys(_lib.ptr(f), F, V, _lib.ptr(cl.vertex_map), K, _lib.ptr(keys),
+                                                          _lib.current_stream_ptr(dev)), "t2n_mesh_cluster_face_keys")
+            foff, frow = (_csr_rows(lib, keys, K, dev) if F else
+                          (torch.zeros(K + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev)))
+        with torch.cuda.device(dev):
+            stream = _lib.current_stream_ptr(dev)
+            p = _lib.ptr
+            _lib.check(lib.t2n_mesh_cluster_place(p(v), V, p(f), F, p(cl.offsets), p(cl.members), V, p(cl.cells), K, p(foff), p(frow),
+                                                  int(frow.shape[0]) if quadric else 0, (C.c_double * 3)(*o), (C.c_double * 3)(*h), reg,
+                                                  1 if quadric else 0, p(out_v), stream), "t2n_mesh_cluster_place")
+            if c is not None:
+                _lib.check(lib.t2n_mesh_cluster_colors(p(c), V, p(cl.offsets), p(cl.members), V, K, p(out_c), stream), "t2n_mesh_cluster_colors")
+            if F > 0:
+                rot = torch.empty(F, 3, dtype=torch.int32, device=dev)
+                key_hi = torch.empty(F, dtype=torch.int64, device=dev)
+                key_lo = torch.empty(F, dtype=torch.int64, device=dev)
+                _lib.check(lib.t2n_mesh_simplify_face_map(p(f), F, V, p(cl.vertex_map), K, p(rot), p(key_hi), p(key_lo), stream),
+                           "t2n_mesh_simplify_face_map")
+                # two stable integer sorts, least significant key first: equal triples end up together in ascending face index
+                by_lo = torch.sort(key_lo, stable=True).indices
+                order = by_lo[torch.sort(key_hi[by_lo], stable=True).indices].contiguous()
+                nbytes = int(lib.t2n_mesh_simplify_faces_workspace_bytes(F))
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+                kept = torch.empty(F, 3, dtype=torch.int32, device=dev)
+                count = torch.empty(1, dtype=torch.int64, device=dev)
+                _lib.check(lib.t2n_mesh_simplify_faces(p(rot), p(order), F, p(kept), p(count), p(ws), nbytes, stream), "t2n_mesh_simplify_faces")
+                out_f = kept[:int(count.cpu().item())].clone()          # the one 8-byte read
+    out_n = None if n is None else _vertex_normals(lib, out_v, out_f, dev)
+    if _is_device(verts):
+        return Mesh(out_v, out_f, out_n, out_c)
+    host = lambda x: None if x is None else x.cpu().numpy()     # noqa: E731
+    return Mesh(host(out_v), host(out_f), host(out_n), host(out_c))
 
 
 def _host(x, dtype):
