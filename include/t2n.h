@@ -252,7 +252,7 @@ int t2n_render_list_shape(int64_t n_rays, int n_samples, int entries_per_ray, ui
  * corner box whose density taps the pair read. With staging on, a wave logs its emitting step pairs (box origin, who emitted) in LDS while
  * it marches; its tail then walks the entries in emission order, copies each logged pair's corner box from the feature volume to LDS once
  * and reads every row's eight corners there instead of fetching 8 x 128 B per entry. Slots, entries and rows are the direct tail's, bit for
- * bit. A wave runs the direct tail when it emitted on a step pair outside the table path, logged more than 32 pairs or its list region did
+ * bit. A wave runs the direct tail when it emitted on a step pair whose taps do not fit one box, logged more than 32 pairs or its list region did
  * not fit; rays handed to k_compact_list and voided regions keep the direct rows. A launch is staged only when the appearance and density
  * factor sets have the same grid (the box is the box of the density taps) of fewer than 1024 texels per axis. Default of a new handle: on.
  * t2n_field_row_staging_counts: out[0] / out[1] = waves of the handle's LAST fused tile-marcher launch whose tail wrote its rows from LDS

@@ -20,10 +20,15 @@
 // Outputs per ray: acc, depth, (slot0, n_app, n_valid, first | Lw << 11) and the ray's contiguous, sample-ordered slice of
 // the appearance list (in-kernel compaction, see TileArgs); with weights requested (DENSE) also the weights of the wave's sampled
 // window (k_dense_fill writes the z_vals rows and the zeros of the weights rows beforehand).
-// Steps whose rectangles do not fit the table (incoherent rays, huge field of view) fall back to direct gathers.
+// EVERY sample reads its density feature from S. A step pair whose taps do not fit one 4 x 4 x 4 table (incoherent rays, huge field of
+// view) is served by a wave-uniform loop over boxes: the box at the low taps of the first sample not yet served is built, every
+// unserved sample whose cell lies in it reads it, until none is left (a sparse frame can give every lane a box of its own:
+// profiles/march_table_every_pair_ab.txt). An entry of S is a function of its texel alone, so a sample gets the same bits whichever
+// box serves it.
 // S is a function of the density factors alone: a field rendered more than once keeps S of its WHOLE grid in a per-field buffer
 // (k_density_sum_table, density_cache_prepare) and the CACHED instantiations read a cell's eight entries there — the same bits,
-// without the per-step-pair loads, MFMAs, LDS table and fences (C2 frame: 0.51 -> 0.38 ms; profiles/march_density_cache_ab.txt).
+// without the per-step-pair loads, MFMAs, LDS table and fences (C2 frame: 0.51 -> 0.38 ms; profiles/march_density_cache_ab.txt), and
+// with nothing to decide per step pair: no tap bit set, no reduction over the wave, no branch.
 // Replaces the same reference lines as k_march (see t2n_march.hip).
 #include <type_traits>
 #include "t2n_device.h"
@@ -111,6 +116,35 @@ __device__ __forceinline__ unsigned wave_or_u(unsigned v) {
     const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)v, 15), b = (unsigned)__builtin_amdgcn_readlane((int)v, 31);
     const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)v, 47), d = (unsigned)__builtin_amdgcn_readlane((int)v, 63);
     return (a | b) | (c | d);
+}
+
+// The tap box of a step pair: the low-tap indices of its live samples (ok[q]) over the wave, per axis, as ONE or-reduced bit set —
+// 10 bits per axis around the first live lane's index (bit 5); an index outside [-5, +4] of it raises bit 30. amn[a] = the lowest
+// low tap of axis a. True when the pair fits ONE 4 x 4 x 4 table: at most three low taps per axis (the high tap is at most one above
+// the highest low tap, and inside the grid). okm = the ballot of the lanes with a live sample, not zero.
+__device__ __forceinline__ bool pair_box(const Axes3 (&A)[2], const bool (&ok)[2], unsigned long long okm, int (&amn)[3]) {
+    int sel0 = 0, sel1 = 0, sel2 = 0;
+#pragma unroll
+    for (int q = 1; q >= 0; --q)
+        if (ok[q]) { sel0 = A[q].a[0].i0; sel1 = A[q].a[1].i0; sel2 = A[q].a[2].i0; }
+    const int lead = (int)__builtin_ctzll(okm);
+    const int ref0 = __builtin_amdgcn_readlane(sel0, lead), ref1 = __builtin_amdgcn_readlane(sel1, lead),
+              ref2 = __builtin_amdgcn_readlane(sel2, lead);
+    unsigned bits = 0u;
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+        if (ok[q]) {
+            const unsigned d0 = (unsigned)(A[q].a[0].i0 - ref0 + 5), d1 = (unsigned)(A[q].a[1].i0 - ref1 + 5),
+                           d2 = (unsigned)(A[q].a[2].i0 - ref2 + 5);
+            bits |= (d0 < 10u ? 1u << d0 : 0x40000000u) | (d1 < 10u ? 1u << (10u + d1) : 0x40000000u) |
+                    (d2 < 10u ? 1u << (20u + d2) : 0x40000000u);
+        }
+    bits = wave_or_u(bits);
+    const unsigned f0 = bits & 1023u, f1 = (bits >> 10) & 1023u, f2 = (bits >> 20) & 1023u;
+    amn[0] = ref0 - 5 + __builtin_ctz(f0); amn[1] = ref1 - 5 + __builtin_ctz(f1); amn[2] = ref2 - 5 + __builtin_ctz(f2);
+    const int span = max(max(32 - __builtin_clz(f0) - __builtin_ctz(f0), 32 - __builtin_clz(f1) - __builtin_ctz(f1)),
+                         32 - __builtin_clz(f2) - __builtin_ctz(f2)) + 1;
+    return !(bits & 0x40000000u) && span <= 4;
 }
 
 // The dot-product tables of one wave step (see the file header). amn[a] = lowest tap index of axis a over the wave; every axis
@@ -220,29 +254,6 @@ __device__ __forceinline__ float cached_read3(const Axes3& A, const CellTaps& t)
     return fmaf(v1, az.w1, v0 * az.w0);
 }
 
-template <int K>
-__device__ __forceinline__ float pair_dot_global(const FactorSet& S, const Axes3& A, float part) {
-    const Axis& ax = A.a[mat0(K)];
-    const Axis& ay = A.a[mat1(K)];
-    const Axis& al = A.a[vecm(K)];
-    const float4* __restrict__ P = reinterpret_cast<const float4*>(S.plane[K]);
-    const float4* __restrict__ L = reinterpret_cast<const float4*>(S.line[K]);
-    const unsigned W = (unsigned)S.W[K];
-    const unsigned nw = ((unsigned)ay.i0 * W + ax.i0) * 4, ne = ((unsigned)ay.i0 * W + ax.i1) * 4;
-    const unsigned sw = ((unsigned)ay.i1 * W + ax.i0) * 4, se = ((unsigned)ay.i1 * W + ax.i1) * 4;
-#pragma unroll 1   // the rare direct-gather step: keep its register footprint below the table path's (occupancy)
-    for (int q = 0; q < 4; ++q) {
-        float4 v = f4_mul(P[nw + q], ay.w0 * ax.w0);
-        v = f4_fma(P[ne + q], ay.w0 * ax.w1, v);
-        v = f4_fma(P[sw + q], ay.w1 * ax.w0, v);
-        v = f4_fma(P[se + q], ay.w1 * ax.w1, v);
-        float4 l = f4_mul(L[al.i0 * 4 + q], al.w0);
-        l = f4_fma(L[al.i1 * 4 + q], al.w1, l);
-        part = fmaf(v.x, l.x, part); part = fmaf(v.y, l.y, part); part = fmaf(v.z, l.z, part); part = fmaf(v.w, l.w, part);
-    }
-    return part;
-}
-
 // A reservation that did not fit leaves its sub-list counter raised over entries nobody writes (the readers clamp the counter to
 // list_cap, so the part of the region inside the list IS walked by the shading kernels): those entries get a defined content — the
 // volume centre, weight 0, ray 0 — whatever the scratch held before (the SH head reads the entry's ray for its view direction).
@@ -271,7 +282,7 @@ __device__ __forceinline__ void slot_rows(const FieldDev& F, const float4* __res
 // emitted at step 0 / step 1) in a wave-private LDS log; the tail then walks its entries in EMISSION order instead of list order: per
 // logged pair it copies the box's corners from the volume to LDS once (8 coalesced wave loads instead of 8 x 128 B per entry) and
 // every row pass reads its eight corners there — no pass holds a dependent global load. Slots, entries and rows are what the direct
-// tail writes, bit for bit. A wave whose log overflowed, or that emitted on a pair outside the table path, runs the direct tail.
+// tail writes, bit for bit. A wave whose log overflowed, or that emitted on a pair that does not fit one box, runs the direct tail.
 // Per wave: the box | count, direct flag | the log.
 constexpr int kRsLogMax = 32;
 constexpr unsigned kRsBoxBytes = 64u * kAvBoxCornerBytes;
@@ -378,9 +389,10 @@ struct __attribute__((aligned(4))) F4U { float x, y, z, w; };   // row segments 
 // sends NDC renders here): the step loop of the driver's configuration (no mask, softplus) carries neither the mask's eight-tap
 // gather with its 64-bit address arithmetic nor a run-time test per sample and option.
 // CACHED: the field carries the summed table of its whole grid (FieldDev::dsum): a step pair inside the table's reach reads its entries
-// there instead of building its 4 x 4 x 4 piece (same bits, see cached_read3). Which step pairs take the table form and which the direct
-// gathers is decided exactly as without the cache (the two forms round differently, and the frame is the same bit for bit either way),
-// so the tap bit set stays; the operand loads, the MFMAs, the LDS table, its sum pass and the three fences go.
+// there instead of building its 4 x 4 x 4 piece (same bits, see cached_read3). The uncached kernel serves every sample from a table as
+// well (one build for a pair that fits a box, the loop over boxes for one that does not), so the cached one decides nothing: the tap
+// bit set, its reduction and the branch go with the operand loads, the MFMAs, the LDS table, its sum pass and the three fences. Only an
+// EMITTING pair of a STAGE frame still works out its tap box (pair_box, for the log).
 constexpr int mt_waves(bool dense, bool cached) { return cached ? (dense ? T2N_MTCD_WAVES : T2N_MTC_WAVES) : (dense ? T2N_MTD_WAVES : T2N_MT_WAVES); }
 // ROWS (CACHED && !DENSE frames that hold the current feature volume and a row per list slot, launch_march_tiles): the wave's tail
 // also produces the feature rows of the slots it filled or voided — eight corner fetches and 64 multiply-adds per entry, work bound by
@@ -493,39 +505,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
 #pragma unroll
         for (int q = 0; q < kSteps; ++q) part[q] = 0.f;
         unsigned emv = 0u;           // STAGE: bit q = the lane stored an entry at step q (one register: masks kept per step cost four scalars)
-        unsigned bo = 0u;            // STAGE: the pair took the table path (bit 30) and its box origin, 10 bits per axis, in ONE scalar
         if (okm) {
 #pragma unroll
             for (int q = 0; q < kSteps; ++q) A[q] = sample_axes_inbox(F.den, xn[q], yn[q], zn[q]);   // used by samples inside the box only (ok[q])
-            // the low-tap indices present in the wave, per axis, as ONE or-reduced bit set: 10 bits per axis around the first
-            // live lane's index (bit 5); an index outside [-5, +4] of it raises bit 30 (the steps then gather directly)
-            int sel0 = 0, sel1 = 0, sel2 = 0;
-#pragma unroll
-            for (int q = kSteps - 1; q >= 0; --q)
-                if (ok[q]) { sel0 = A[q].a[0].i0; sel1 = A[q].a[1].i0; sel2 = A[q].a[2].i0; }
-            const int lead = (int)__builtin_ctzll(okm);
-            const int ref0 = __builtin_amdgcn_readlane(sel0, lead), ref1 = __builtin_amdgcn_readlane(sel1, lead),
-                      ref2 = __builtin_amdgcn_readlane(sel2, lead);
-            unsigned bits = 0u;
-#pragma unroll
-            for (int q = 0; q < kSteps; ++q)
-                if (ok[q]) {
-                    const unsigned d0 = (unsigned)(A[q].a[0].i0 - ref0 + 5), d1 = (unsigned)(A[q].a[1].i0 - ref1 + 5),
-                                   d2 = (unsigned)(A[q].a[2].i0 - ref2 + 5);
-                    bits |= (d0 < 10u ? 1u << d0 : 0x40000000u) | (d1 < 10u ? 1u << (10u + d1) : 0x40000000u) |
-                            (d2 < 10u ? 1u << (20u + d2) : 0x40000000u);
-                }
-            bits = wave_or_u(bits);
-            const unsigned f0 = bits & 1023u, f1 = (bits >> 10) & 1023u, f2 = (bits >> 20) & 1023u;
-            const int amn[3] = {ref0 - 5 + __builtin_ctz(f0), ref1 - 5 + __builtin_ctz(f1), ref2 - 5 + __builtin_ctz(f2)};
-            // taps per axis: the high tap is at most one above the highest low tap (and inside the grid)
-            const int span = max(max(32 - __builtin_clz(f0) - __builtin_ctz(f0), 32 - __builtin_clz(f1) - __builtin_ctz(f1)),
-                                 32 - __builtin_clz(f2) - __builtin_ctz(f2)) + 1;
-            const bool ranged = !(bits & 0x40000000u);
-            MT_T(p_axes);
-            if (CACHED && ranged && span <= 4) {
-                if constexpr (STAGE) bo = 0x40000000u | (unsigned)amn[0] | (unsigned)amn[1] << 10 | (unsigned)amn[2] << 20;
-                // both samples' eight loads in flight together; a lane without a sample reads the table's first cell
+            if constexpr (CACHED) {
+                MT_T(p_axes);
+                // every sample reads its cell in the table of the whole grid: nothing to decide. Both samples' eight loads in flight
+                // together; a lane without a sample reads the table's first cell
                 unsigned off[kSteps];
                 CellTaps ct[kSteps];
 #pragma unroll
@@ -537,35 +523,81 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
                 for (int q = 0; q < kSteps; ++q)
                     if (ok[q]) part[q] = cached_read3(A[q], ct[q]);
                 MT_T(p_read);
-            } else if (ranged && span <= 4) {
-                table_build<2>(F.den, amn, stD, l15, lq);
-                lds_fence_w();
-                {
-                    // (the lane index behind an opaque copy, per build: visible, the sum pass's three lane offsets are hoisted out of
-                    // the step loop and spilled)
-                    int ln = lane;
-                    asm volatile("" : "+v"(ln));
-                    table_sum<2>(stD, ln);
-                }
-                lds_fence_w();
-                MT_T(p_build);
-                // (the origin's offset as ONE scalar the compiler cannot take apart again: left visible it subtracts the three
-                // amn[] from the three tap indices of every sample, one vector instruction each)
-                int org = (amn[2] << 4) + (amn[1] << 2) + amn[0];
-                asm volatile("" : "+s"(org));
-#pragma unroll
-                for (int q = 0; q < kSteps; ++q)
-                    if (ok[q]) part[q] = table_read3(A[q], org, stD);
-                lds_fence_w();
-                MT_T(p_read);
             } else {
-#pragma unroll   // (a rolled loop would index A[] dynamically and push the per-sample arrays to scratch)
-                for (int q = 0; q < kSteps; ++q)
-                    if (ok[q]) {
-                        float pq = pair_dot_global<0>(F.den, A[q], 0.f);
-                        pq = pair_dot_global<1>(F.den, A[q], pq);
-                        part[q] = pair_dot_global<2>(F.den, A[q], pq);
+                // the table of the box at amn[] -> the wave's LDS area; returns the origin's part of a sample's offset
+                auto build_at = [&](const int (&amn)[3]) {
+                    table_build<2>(F.den, amn, stD, l15, lq);
+                    lds_fence_w();
+                    {
+                        // (the lane index behind an opaque copy, per build: visible, the sum pass's three lane offsets are hoisted out of
+                        // the step loop and spilled)
+                        int ln = lane;
+                        asm volatile("" : "+v"(ln));
+                        table_sum<2>(stD, ln);
                     }
+                    lds_fence_w();
+                    // (the origin's offset as ONE scalar the compiler cannot take apart again: left visible it subtracts the three
+                    // amn[] from the three tap indices of every sample, one vector instruction each)
+                    int org = (amn[2] << 4) + (amn[1] << 2) + amn[0];
+                    asm volatile("" : "+s"(org));
+                    return org;
+                };
+                int amn[3];
+                const bool fits = pair_box(A, ok, okm, amn);
+                MT_T(p_axes);
+                if (fits) {
+                    const int org = build_at(amn);
+                    MT_T(p_build);
+#pragma unroll
+                    for (int q = 0; q < kSteps; ++q)
+                        if (ok[q]) part[q] = table_read3(A[q], org, stD);
+                    lds_fence_w();
+                    MT_T(p_read);
+                } else {
+                    // a pair wider than one table: a wave-uniform loop over boxes. The box at the low taps of the first sample not yet
+                    // served is built as above; every unserved sample whose cell lies in it (low taps origin .. origin + 2 per axis)
+                    // reads its feature there. An entry of S is a function of its texel alone, so the samples get the bits of the
+                    // one-build form and of the whole-grid table, whichever box serves them. The lead lane's sample is served by
+                    // its own box: every trip serves at least one sample.
+                    // (the taps are computed again from the coordinates on both sides of a build, behind opaque copies: the eighteen
+                    // values of A[] kept across the builds and the loop's back edge push loop-carried values of the step loop to
+                    // scratch; a trip's 70 VALU more are nothing beside its build)
+                    unsigned todo = (ok[0] ? 1u : 0u) | (ok[1] ? 2u : 0u);
+                    unsigned long long tm = okm;
+#pragma unroll 1
+                    do {
+                        const int lead = (int)__builtin_ctzll(tm);
+                        int bx[3];
+                        {
+                            const bool s1 = !(todo & 1u);   // the lane's first unserved sample
+                            float x = s1 ? xn[1] : xn[0], y = s1 ? yn[1] : yn[0], zz = s1 ? zn[1] : zn[0];
+                            asm volatile("" : "+v"(x), "+v"(y), "+v"(zz));
+                            const Axes3 B = sample_axes_inbox(F.den, x, y, zz);
+                            // (opaque again: the compiler moves a readlane in front of the arithmetic that feeds it, and the taps of
+                            // the lead lane's coordinates come out of vector instructions, not in scalars)
+                            int b0 = B.a[0].i0, b1 = B.a[1].i0, b2 = B.a[2].i0;
+                            asm volatile("" : "+v"(b0), "+v"(b1), "+v"(b2));
+                            bx[0] = __builtin_amdgcn_readlane(b0, lead); bx[1] = __builtin_amdgcn_readlane(b1, lead);
+                            bx[2] = __builtin_amdgcn_readlane(b2, lead);
+                        }
+                        const int org = build_at(bx);
+#pragma unroll   // (a rolled loop would index the per-sample arrays dynamically and push them to scratch)
+                        for (int q = 0; q < kSteps; ++q) {
+                            float x = xn[q], y = yn[q], zz = zn[q];
+                            asm volatile("" : "+v"(x), "+v"(y), "+v"(zz));
+                            const Axes3 B = sample_axes_inbox(F.den, x, y, zz);
+                            const bool in = (unsigned)(B.a[0].i0 - bx[0]) <= 2u && (unsigned)(B.a[1].i0 - bx[1]) <= 2u &&
+                                            (unsigned)(B.a[2].i0 - bx[2]) <= 2u;
+                            if (((todo >> q) & 1u) && in) {
+                                part[q] = table_read3(B, org, stD);
+                                todo &= ~(1u << q);
+                            }
+                        }
+                        lds_fence_w();   // the reads of this box are done before the next build overwrites it
+                        tm = __ballot(todo != 0u);
+                    } while (tm);
+                    MT_T(p_read);
+                }
             }
         }
 #pragma unroll
@@ -624,8 +656,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(mt_waves(DE
             }
         }
         if constexpr (STAGE) {
-            // an emitting pair: one record (lane 0), or the wave's tail turns direct (pair outside the table path, log full)
+            // an emitting pair: one record (lane 0), or the wave's tail turns direct (pair wider than one box, log full)
             if (__any(emv != 0u)) {
+                // the pair's tap box, needed here alone (a few pairs per wave emit): over ALL live samples of the pair, emitting or
+                // not, by the uncached kernel's rule. The taps are computed again from the coordinates, behind opaque copies: kept
+                // from the step's own computation they would stay in registers across the compositing.
+                unsigned bo = 0u;    // the pair fits one 4 x 4 x 4 box (bit 30) and the box origin, 10 bits per axis, in ONE scalar
+                {
+                    Axes3 B[kSteps];
+#pragma unroll
+                    for (int q = 0; q < kSteps; ++q) {
+                        float x = xn[q], y = yn[q], zz = zn[q];
+                        asm volatile("" : "+v"(x), "+v"(y), "+v"(zz));
+                        B[q] = sample_axes_inbox(F.den, x, y, zz);
+                    }
+                    int amn[3];
+                    if (pair_box(B, ok, okm, amn)) bo = 0x40000000u | (unsigned)amn[0] | (unsigned)amn[1] << 10 | (unsigned)amn[2] << 20;
+                }
                 const unsigned long long b0 = __ballot((emv & 1u) != 0u), b1 = __ballot((emv & 2u) != 0u);
                 if (lane == 0) {
                     const unsigned c = rs_hdr[0];
