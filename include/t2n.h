@@ -952,6 +952,60 @@ int t2n_mesh_filter_emit(const int32_t* faces, int64_t n_faces, const int32_t* l
                          void* workspace, size_t workspace_bytes, float* verts_out, float* normals_out_or_null,
                          uint8_t* colors_out_or_null, int32_t* faces_out, t2n_stream stream);
 
+/* ---- Mesh export: selection by per-face flags, the generic form of the filter above. keep [F] uint8: face t stays iff keep[t] != 0 (a
+ * face with an index outside [0, n_verts) never stays); a vertex stays iff a kept face references it. Kept faces and kept vertices keep
+ * their input order, the verts / normals / colors rows move together, faces are re-indexed. The vertices' "used" flags are idempotent
+ * byte stores of 1; everything else is scans and one pass: all integer, no float operation, two calls give bit-equal arrays.
+ *   t2n_mesh_select_faces_count   marks the used vertices, scans both flag arrays into the workspace
+ *                  (t2n_mesh_select_faces_workspace_bytes(n_verts, n_faces) bytes of device memory, 0 = bad argument) and writes the
+ *                  totals to totals_out (device int64 [2]: vertices, faces).
+ *   t2n_mesh_select_faces_emit    takes the workspace as the count call left it for the same arguments and writes the kept rows and the
+ *                  kept faces (normals / colors: in and out NULL together). With zero kept vertices nothing is written.
+ * T2N_ERR_INVALID (before any HIP call): NULL required pointer, a negative count, n_verts >= 2^31, 3 * n_faces >= 2^31, workspace_bytes
+ * smaller than required. */
+size_t t2n_mesh_select_faces_workspace_bytes(int64_t n_verts, int64_t n_faces);
+int t2n_mesh_select_faces_count(const int32_t* faces, int64_t n_faces, int64_t n_verts, const uint8_t* keep, void* workspace,
+                                size_t workspace_bytes, int64_t* totals_out, t2n_stream stream);
+int t2n_mesh_select_faces_emit(const int32_t* faces, int64_t n_faces, int64_t n_verts, const uint8_t* keep, const float* verts,
+                               const float* normals_or_null, const uint8_t* colors_or_null, void* workspace, size_t workspace_bytes,
+                               float* verts_out, float* normals_out_or_null, uint8_t* colors_out_or_null, int32_t* faces_out,
+                               t2n_stream stream);
+
+/* ---- Mesh export: TSDF fusion of depth views (csrc/t2n_tsdf.hip). The volume is a frame of nodes, node (a,b,c) at x_k = (double)o_k +
+ * (double)idx_k * (double)s_k (origin3, spacing3: host float [3], the values t2n_mc_emit takes), and its state is float32: tsdf
+ * [n0][n1][n2], weight [n0][n1][n2], optionally color [n0][n1][n2][3]; untouched = tsdf 1, weight 0, colour 0. All arithmetic is double,
+ * one IEEE operation per written operation in the written order; the state is rounded to float32 AFTER EVERY VIEW, so V calls of one
+ * view equal one call of V views bit for bit. No atomics: a node is owned by one thread.
+ *   t2n_tsdf_integrate   depth [V][H][W] fp32, rgb [V][H][W][3] fp32 or NULL (rgb and color: NULL together), pixel_weight [V][H][W] fp32
+ *     or NULL, w2c [V][12] double in DEVICE memory: the rows of the 3x4 world-to-camera matrices M. kind 0: depth is the distance along
+ *     the ray, kind 1: the camera-space z. For every node, views v = 0 .. V-1 in order:
+ *       1. p_k = ((M_k0 x_0 + M_k1 x_1) + M_k2 x_2) + M_k3; skip unless p_2 > near
+ *       2. u = (fx p_0) / p_2 + cx, v = (fy p_1) / p_2 + cy; skip unless 0 <= u < W and 0 <= v < H; i = floor(u), j = floor(v): the
+ *          nearest pixel (pixel i spans [i, i+1), centre i + 0.5: t2n_generate_rays' convention)
+ *       3. d = depth[v][j][i], skip unless finite and > 0; w = 1 or pixel_weight[v][j][i], skip unless finite and > 0
+ *       4. r = sqrt((p_0 p_0 + p_1 p_1) + p_2 p_2) (kind 0) or p_2 (kind 1); sdf = d - r; skip if sdf < -trunc; s = min(1, sdf / trunc)
+ *       5. Wn = (double)W + w; T <- (float)(((double)W (double)T + w s) / Wn), every colour channel the same with rgb in s's place;
+ *          W <- (float)min(Wn, max_weight) (max_weight = +inf: no cap)
+ *     n_views == 0 launches nothing.
+ *   t2n_tsdf_face_flags  the observed-cells rule, keep [F] uint8 for t2n_mesh_select_faces: c_k = (((double)x_a,k + x_b,k) + x_c,k) / 3.0,
+ *     g_k = (c_k - (double)o_k) / (double)s_k, cell_k = clamp(floor(g_k), 0, n_k - 2) (a NaN: 0), keep = 1 iff all eight corners of that
+ *     cell have (double)weight > min_weight. A face with an index outside [0, n_verts): 0.
+ *   t2n_tsdf_sample_colors  colors_out [V][3] uint8: g_k = ((double)x_k - o_k) / s_k, cell_k as above, f_k = clamp(g_k - cell_k, 0, 1);
+ *     the eight corners in the order (0,0,0), (0,0,1), (0,1,0), ... (axis 2 fastest), trilinear weight ((a_0 a_1) a_2) with a_k = f_k or
+ *     1 - f_k; only corners with weight > min_weight enter sum w and sum w c (both from 0.0 in that order); colour = sum wc / sum w (0
+ *     unless sum w > 0), clamped to [0,1], times 255, rounded half to even.
+ * T2N_ERR_INVALID (before any HIP call): NULL required pointer, a dimension < 1 (integrate) or < 2 (the other two), a negative count,
+ * n_verts >= 2^31, 3 * n_faces >= 2^31, a spacing or trunc that is not finite and positive, an origin or intrinsic that is not finite,
+ * fx or fy zero, max_weight not > 0, a NaN min_weight, an unknown kind. T2N_ERR_UNSUPPORTED: n0 * n1 * n2 >= 2^31. */
+int t2n_tsdf_integrate(float* tsdf, float* weight, float* color_or_null, int n0, int n1, int n2, const float* depth,
+                       const float* rgb_or_null, const float* pixel_weight_or_null, const double* w2c, int n_views, int H, int W, double fx,
+                       double fy, double cx, double cy, const float* origin3, const float* spacing3, double trunc, double near,
+                       double max_weight, int kind, t2n_stream stream);
+int t2n_tsdf_face_flags(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* weight, int n0, int n1,
+                        int n2, const float* origin3, const float* spacing3, double min_weight, uint8_t* keep, t2n_stream stream);
+int t2n_tsdf_sample_colors(const float* verts, int64_t n_verts, const float* weight, const float* color, int n0, int n1, int n2,
+                           const float* origin3, const float* spacing3, double min_weight, uint8_t* colors_out, t2n_stream stream);
+
 /* ---- Mesh export: Taubin (lambda | mu) smoothing and vertex normals on the device, the stage users of TensoRF-family exports run
  * afterwards in MeshLab. Every output is a function of the face SET and the positions alone (not of face order, corner order or thread
  * order): no float atomics, two calls give bit-equal arrays. faces [F][3] int32 into n_verts vertices, 6 * n_faces < 2^31.

@@ -16,5 +16,7 @@ from .mesh import Mesh, marching_cubes, convert_sdf_samples_to_ply, write_ply  #
 from .mesh import Components, mesh_components, filter_components  # noqa: F401
 from .mesh import Adjacency, mesh_adjacency, smooth_mesh, vertex_normals  # noqa: F401
 from .mesh import Clusters, mesh_clusters, simplify_mesh  # noqa: F401
+from .mesh import select_faces  # noqa: F401
+from .tsdf import TSDFVolume, tsdf_integrate, tsdf_mesh  # noqa: F401
 from .volume import VolumeComponents, volume_components, filter_volume  # noqa: F401
 from .tensorf import PruneReport  # noqa: F401

@@ -8,6 +8,7 @@ writer, in the place of `skimage.measure.marching_cubes` on a host copy followed
     Mesh                         what `TensorBase.export_mesh` returns: verts, faces, normals, colors
     mesh_components              faces, n_verts -> Components(labels, n_components, vert_counts, face_counts)
     filter_components            a Mesh without its unwanted components ("floaters"): min_faces and / or keep_largest
+    select_faces                 a Mesh reduced to the faces a per-face flag array keeps (what text2nerf_amd.tsdf's observed-cells rule uses)
     mesh_adjacency               faces, n_verts -> Adjacency(offsets, neighbours): sorted unique CSR rows (csrc/t2n_mesh_smooth.hip)
     smooth_mesh                  Taubin lambda | mu smoothing in float64 over those rows, normals recomputed
     vertex_normals               area-weighted normals of a mesh's faces, float64 sums in ascending face order
@@ -263,6 +264,62 @@ def filter_components(mesh, min_faces=0, keep_largest=None, components=None):
         return Mesh(out_v, out_f, out_n, out_c)
     host = lambda x: None if x is None else x.cpu().numpy()
     return Mesh(host(out_v), host(out_f), host(out_n), host(out_c))
+
+
+def _select_faces(lib, v, f, n, c, keep, dev):
+    """select_faces on checked device tensors (keep [F] uint8); a Mesh of device tensors. Reads the 16 bytes of the new totals."""
+    V, F = int(v.shape[0]), int(f.shape[0])
+    Vk = Fk = 0
+    with torch.cuda.device(dev):
+        if V > 0 and F > 0:                                     # nothing is launched on an empty mesh
+            nbytes = int(lib.t2n_mesh_select_faces_workspace_bytes(V, F))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            totals = torch.empty(2, dtype=torch.int64, device=dev)
+            stream = _lib.current_stream_ptr(dev)
+            _lib.check(lib.t2n_mesh_select_faces_count(_lib.ptr(f), F, V, _lib.ptr(keep), _lib.ptr(ws), nbytes, _lib.ptr(totals), stream),
+                       "t2n_mesh_select_faces_count")
+            Vk, Fk = (int(x) for x in totals.cpu().tolist())    # the one 16-byte read
+        out_v = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+        out_f = torch.empty(Fk, 3, dtype=torch.int32, device=dev)
+        out_n = None if n is None else torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+        out_c = None if c is None else torch.empty(Vk, 3, dtype=torch.uint8, device=dev)
+        if Vk > 0:
+            _lib.check(lib.t2n_mesh_select_faces_emit(_lib.ptr(f), F, V, _lib.ptr(keep), _lib.ptr(v), _lib.ptr(n), _lib.ptr(c), _lib.ptr(ws),
+                                                      nbytes, _lib.ptr(out_v), _lib.ptr(out_n), _lib.ptr(out_c), _lib.ptr(out_f), stream),
+                       "t2n_mesh_select_faces_emit")
+    return Mesh(out_v, out_f, out_n, out_c)
+
+
+@torch.no_grad()
+def select_faces(mesh, keep):
+    """`mesh` (a Mesh, or (verts, faces[, normals[, colors]])) reduced to the faces whose flag in `keep` ([F], bool or any integer
+    dtype: nonzero = stay) is set, as a Mesh. A vertex stays iff a kept face references it; kept vertices and kept faces keep their
+    relative order, the verts / normals / colors rows move together, faces are re-indexed. All integer (the vertices' flags are
+    idempotent byte stores, the rest scans): two calls give bit-equal arrays. All flags set returns the mesh without its unreferenced
+    vertices; none set returns empty arrays. `filter_components` is this stage with flags that are constant on a component. Device
+    tensors in, device tensors out; numpy arrays / CPU tensors in, numpy arrays out, through the device. Host reads: the index check's
+    min / max and the 16 bytes of the new totals. ValueError (before any launch): faces that are not [F,3] integer or hold an index
+    outside [0, V), rows or a `keep` that do not match. T2NError without a GPU."""
+    lib = _lib.load()
+    parts = tuple(mesh)
+    if not 2 <= len(parts) <= 4:
+        raise ValueError(f"select_faces: a mesh of {len(parts)} parts, need (verts, faces[, normals[, colors]])")
+    verts, faces, normals, colors = parts + (None,) * (4 - len(parts))
+    if len(verts.shape) != 2 or verts.shape[1] != 3:
+        raise ValueError(f"select_faces: verts of shape {tuple(verts.shape)}, need [V,3]")
+    V = int(verts.shape[0])
+    if tuple(keep.shape) != (int(faces.shape[0]),):
+        raise ValueError(f"select_faces: keep of shape {tuple(keep.shape)} for faces of shape {tuple(faces.shape)}, need [F]")
+    f, dev = _faces_on_device(faces, V, "select_faces")
+    v = _rows(verts, V, torch.float32, dev, "verts", "select_faces")
+    n = _rows(normals, V, torch.float32, dev, "normals", "select_faces")
+    c = _rows(colors, V, torch.uint8, dev, "colors", "select_faces")
+    k = (_as_tensor(keep).detach().to(dev) != 0).to(torch.uint8).contiguous()
+    out = _select_faces(lib, v, f, n, c, k, dev)
+    if _is_device(verts):
+        return out
+    host = lambda x: None if x is None else x.cpu().numpy()     # noqa: E731
+    return Mesh(*(host(x) for x in out))
 
 
 # ---- adjacency, Taubin smoothing, vertex normals -----------------------------------------------------------------------------------------

@@ -1478,6 +1478,68 @@ class TensorBase(nn.Module):
             M.write_ply(path, out.verts, out.faces, out.normals, out.colors)
         return out
 
+    TSDF_VIEW_CHUNK = 8      # views rendered before they are integrated: no stack larger than this exists
+
+    @torch.no_grad()
+    def tsdf_volume(self, poses, intrinsic, H, W, gridSize=None, trunc=None, depth="median", quantile=0.5, min_acc=0.5, carve=True,
+                    colors=True, N_samples=-1, white_bg=True):
+        """A `text2nerf_amd.tsdf.TSDFVolume` of this field's RENDERED depth from `poses` ([V,3,4] or [V,4,4] camera-to-world) at H x W
+        with `intrinsic` (fx, fy, cx, cy): the surface the pipeline itself trusts (warp, inpaint, depth merge are built on rendered
+        depth), fused only where the views look, in the place of a level set of the dense field with its fog and floaters. Per pose:
+        `generate_rays` -> `render_geometry` (depth="median": the depth at `quantile` of the ray's weight; depth="depth": forward's
+        expected depth) and, with `colors`, the render's rgb (`white_bg` as in forward); TSDF_VIEW_CHUNK views at a time go to
+        `tsdf_integrate(depth_kind="ray")`. A pixel whose accumulated weight is below `min_acc` gets depth near_far[1] with `carve`
+        (free space is carved along the whole ray, floaters lose the vote) and 0 (no measurement) without. The frame is getDenseAlpha's
+        nodes: origin aabb[0], spacing (aabb[1] - aabb[0]) / (g - 1), g = gridSize or the field's own; `trunc` defaults to 4 x the
+        largest spacing. What `render_geometry` refuses (NDC, general-shape fields) is refused here with its error; ValueError for an
+        unknown `depth` and for what `tsdf_integrate` refuses."""
+        from . import tsdf as Ts
+        from .ray_utils import generate_rays
+        if depth not in ("median", "depth"):
+            raise ValueError(f"tsdf_volume: depth={depth!r} ('median' or 'depth')")
+        if self._is_general():
+            raise T2NError("render_geometry: unsupported for a general-shape field (no native field handle)")
+        dev = self.basis_mat.weight.device
+        g = [int(x) for x in (self.gridSize if gridSize is None else gridSize)]
+        a = self.aabb.detach().float().cpu()
+        spacing = ((a[1] - a[0]) / (torch.tensor(g, dtype=torch.float32) - 1)).tolist()
+        origin = a[0].tolist()
+        if trunc is None:
+            trunc = 4.0 * max(spacing)
+        H, W = int(H), int(W)
+        p = poses.detach().cpu() if isinstance(poses, torch.Tensor) else torch.as_tensor(np.asarray(poses))
+        Ts.world_to_camera(p)                                    # every pose is refused before the first render
+        fill = float(self.near_far[1]) if carve else 0.0
+        vol = Ts.tsdf_integrate(torch.empty(0, H, W, device=dev), p[:0], intrinsic, origin, spacing, g, trunc,
+                                colors=torch.empty(0, H, W, 3, device=dev) if colors else None)
+        for lo in range(0, p.shape[0], self.TSDF_VIEW_CHUNK):
+            chunk = p[lo:lo + self.TSDF_VIEW_CHUNK]
+            ds, cs = [], []
+            for c2w in chunk:
+                rays = generate_rays(H, W, intrinsic, c2w, device=dev)
+                geo = self.render_geometry(rays, N_samples=N_samples, quantile=quantile, want=(depth,))
+                d = geo.depth_median if depth == "median" else geo.depth
+                ds.append(torch.where(geo.acc >= float(min_acc), d, torch.full_like(d, fill)).reshape(H, W))
+                if colors:
+                    cs.append(self(rays, white_bg=white_bg, is_train=False, N_samples=N_samples, frame_width=W)[0].reshape(H, W, 3))
+            vol = Ts.tsdf_integrate(torch.stack(ds), chunk, intrinsic, origin, spacing, g, trunc, colors=torch.stack(cs) if colors else None,
+                                    depth_kind="ray", volume=vol)
+        return vol
+
+    @torch.no_grad()
+    def export_tsdf_mesh(self, path, poses, intrinsic, H, W, gridSize=None, trunc=None, depth="median", quantile=0.5, min_acc=0.5,
+                         carve=True, colors=True, N_samples=-1, white_bg=True, normals=True):
+        """`tsdf_volume(...)`, `tsdf.tsdf_mesh(vol, normals=normals, colors=colors)` and, when `path` is given, `mesh.write_ply`: nothing
+        else. Returns the `mesh.Mesh`; it composes with `filter_components`, `smooth_mesh` and `simplify_mesh` like export_mesh's."""
+        from . import mesh as M
+        from . import tsdf as Ts
+        vol = self.tsdf_volume(poses, intrinsic, H, W, gridSize=gridSize, trunc=trunc, depth=depth, quantile=quantile, min_acc=min_acc,
+                               carve=carve, colors=colors, N_samples=N_samples, white_bg=white_bg)
+        out = Ts.tsdf_mesh(vol, normals=normals, colors=colors)
+        if path is not None:
+            M.write_ply(path, out.verts, out.faces, out.normals, out.colors)
+        return out
+
     # ---- the render call ----------------------------------------------------------------------------------------------------
     def forward(self, rays_chunk, white_bg=True, is_train=False, ndc_ray=False, N_samples=-1, frame_width=None):
         """models/tensorBase.py:436-507: returns (rgb_map [R,3], depth_map [R], z_vals [R,N], weight [R,N]). `frame_width` (not in
